@@ -16,7 +16,7 @@ configs[2] as written ("Batch=512 independent N=1024 GP fits fp32 sharded across
 and call at --gpus 8).  CGP_BENCH_FORCE_DIST=1 runs the RCCL rendezvous / barrier / all_gather / all_reduce
 with a world of ONE rank (the collective path on a one-GPU box).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -63,6 +63,9 @@ def parse_args(argv=None):
                          "speed-up of one sweep); 0 = 1, the single-context figure")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --batch fits per GPU and step; strong: --batch fits per step over ALL ranks (contiguous shards)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them left in the caller's output buffers to DIR/mean.npy, "
+                         "var.npy, logml.npy (rank 0's fits; a fixed sample of them beyond 64 MB)")
     return ap.parse_args(argv)
 
 
@@ -148,6 +151,8 @@ def run_rank(args):
     # "step" is a sleep and the line says "dry_run": true -- never a measurement.
     backend = os.environ.get("CGP_BENCH_BACKEND", "nccl")
     dry = bool(os.environ.get("CGP_BENCH_DRY"))
+    if dry and args.dump_outputs:
+        raise SystemExit("--dump-outputs: a dry run (CGP_BENCH_DRY) computes nothing")
     if os.environ.get("CGP_BENCH_SAME_DEVICE"):
         local = 0
     dev = torch.device("cpu")
@@ -257,6 +262,8 @@ def run_rank(args):
             assert all(int(ln.dinfo.abs().sum().item()) == 0 for ln in lanes)
             W.stream = torch.cuda.current_stream().cuda_stream   # what follows is lane 0 alone, on the default stream
             torch.cuda.synchronize()
+        if args.dump_outputs and rank == 0:   # nothing has touched the output buffers since the last timed step
+            dump_outputs(args.dump_outputs, W if depth == 1 else lanes[(turn[0] - 1) % depth])
         single_ms = W.single_fit_latency_ms()
         # per-fit summaries gathered over RCCL (the only collective on the path: SURVEY.md 8e)
         summ = torch.stack([W.dlogml, 2.0 * W.dvar.to(torch.float64).max(1).values.sqrt(), W.dinfo.to(torch.float64)], 1)
@@ -384,6 +391,28 @@ def cfg3_strong_line(args, dry, world, rank, local, dev, cdev, use_dist, sync, t
             "n_gpus": world, "scaling": "strong", "pipeline_depth": 1, "streams": "engine default", "steps": steps,
             "workload": f"BASELINE configs[2] as written: {total} x N=1024 d=6 SE-ARD fp32, M={M_TEST}, sharded over {world} ranks, "
                         "one context per GPU; divide by config.extra.cfg3_fits_per_s of the --gpus 1 line for the speed-up"}
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, W):
+    """--dump-outputs: the output buffers of workload `W` as the step that just ran left them -- what a caller of
+    cgp_fit_predict_batch_device receives: mean and var [fits][M] in the context's precision, logml [fits].  The fourth buffer,
+    info, is a status code per fit that this run itself requires to be zero everywhere (run_rank), so it says nothing that
+    tells two builds apart and is not written.  The windows are seeded (synth.config), so two builds run with the same
+    arguments are compared array by array.  Beyond DUMP_MAX_BYTES in all, a fixed seeded sample of the fits (in ascending
+    order) is written instead of every one."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"mean": W.dmean, "var": W.dvar, "logml": W.dlogml}
+    per_fit = sum(t[0].numel() * t.element_size() for t in arrays.values())
+    keep = (DUMP_MAX_BYTES - 128 * len(arrays)) // per_fit      # 128: the .npy header
+    rows = None
+    if W.B > keep:
+        rows = W.torch.from_numpy(np.sort(np.random.default_rng(0).choice(W.B, keep, replace=False))).to(W.dmean.device)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), (t if rows is None else t[rows]).cpu().numpy())
 
 
 class Workload:

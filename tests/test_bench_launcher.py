@@ -113,3 +113,37 @@ def test_tools_never_profile_bench_with_live_pmc():
         for line in open(f):
             if "rocprofv3" in line and "bench.py" in line:
                 assert re.search(r"bench\.py\s+--no-pmc", line), (f, line)
+
+
+def test_dump_outputs_writes_the_output_buffers_and_samples_beyond_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: mean / var / logml in the buffers' precision (not the per-fit status codes, which a run requires to be
+    zero), every fit while they fit the byte cap and the same ascending sample of fits, run after run, beyond it (buffers on
+    the CPU here; the GPU run is in tests/test_gpu_bench_contract.py).  A dry run has no outputs to write and says so."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B, M, names = 40, bench.M_TEST, ("mean", "var", "logml")
+    g = torch.Generator().manual_seed(3)
+    W = types.SimpleNamespace(torch=torch, B=B, dmean=torch.randn(B, M, generator=g), dvar=torch.rand(B, M, generator=g),
+                              dlogml=torch.arange(B, dtype=torch.float64), dinfo=torch.zeros(B, dtype=torch.int32))
+    bench.dump_outputs(str(tmp_path / "all"), W)
+    assert sorted(os.listdir(tmp_path / "all")) == ["logml.npy", "mean.npy", "var.npy"]
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in names}
+    assert got["mean"].dtype == got["var"].dtype == np.float32 and got["logml"].dtype == np.float64
+    assert np.array_equal(got["mean"], W.dmean.numpy()) and np.array_equal(got["var"], W.dvar.numpy())
+    assert np.array_equal(got["logml"], np.arange(B))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 60_000)      # room for 12 of the 40 fits
+    bench.dump_outputs(str(tmp_path / "s1"), W)
+    bench.dump_outputs(str(tmp_path / "s2"), W)
+    rows = np.load(tmp_path / "s1" / "logml.npy").astype(int)     # logml = the fit's index in this stand-in
+    assert len(rows) == 12 and np.all(np.diff(rows) > 0)
+    size = 0
+    for n in names:
+        a = np.load(tmp_path / "s1" / (n + ".npy"))
+        assert np.array_equal(a, got[n][rows]) and np.array_equal(a, np.load(tmp_path / "s2" / (n + ".npy")))
+        size += os.path.getsize(tmp_path / "s1" / (n + ".npy"))
+    assert size <= 60_000
+    r = run_bench("--steps", "1", "--warmup", "0", "--batch", "4", "--dump-outputs", str(tmp_path / "dry"))
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not (tmp_path / "dry").exists()

@@ -36,6 +36,35 @@ def test_bench_line_contract():
     assert j["value"] > 0 and j["config"]["single_fit_latency_ms"] > 0
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's mean / var / logml of every fit as DIR/<name>.npy, bit for bit the same
+    from run to run of the same command (seeded windows, --steps really run: one step or three leave the same buffers), and
+    what a caller gets for the same windows through the host-buffer entry of a context of its own."""
+    import numpy as np
+    import corenav_gp_amd.engine as engine
+    import corenav_gp_amd.synth as synth
+    runs = []
+    for tag, steps in (("a", "1"), ("b", "3")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "8", "--steps", steps, "--warmup", "1",
+                            "--no-cpu", "--no-extra", "--no-pmc", "--dump-outputs", str(tmp_path / tag)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["steps"] == int(steps)
+        assert sorted(os.listdir(tmp_path / tag)) == ["logml.npy", "mean.npy", "var.npy"]
+        runs.append({n: np.load(tmp_path / tag / (n + ".npy")) for n in ("mean", "var", "logml")})
+    a, b = runs
+    assert a["mean"].shape == a["var"].shape == (8, 599) and a["logml"].shape == (8,)
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    assert all(np.isfinite(v).all() and v.any() for v in a.values()) and np.all(a["var"] > 0)
+    kid, X, y, Xs, th, _ = synth.config(2, batch=8, M=599)
+    ctx = engine.Context(device=0, max_n=X.shape[1], max_m=599, max_d=X.shape[2], max_batch=8)
+    rc, mean, var, logml, info = ctx.fit_predict_batch(X, y, Xs, th, kid)
+    assert rc == 0 and not info.any()
+    assert np.max(np.abs(a["mean"] - mean)) <= 1e-9 * np.max(np.abs(mean)) and np.max(np.abs(a["var"] - var) / var) < 1e-9
+    assert np.max(np.abs(a["logml"] - logml) / np.abs(logml)) < 1e-12
+
+
 def test_bench_extra_lines():
     """config.extra of the same driver command: the PCIe-inclusive rate, BASELINE configs[2] (512 x N=1024
     fp32) on its own schedule, configs[3] (sliding window) and the batched look-ahead."""

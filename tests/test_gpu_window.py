@@ -131,7 +131,8 @@ def test_growing_pushes_of_a_fresh_context_under_load(engine):
     used to come back, about once in a hundred under load, with the outputs of a push untouched (the kernels access that block in
     place; it was freed and allocated again between pushes), and cgp_window_init's asynchronous fill of the windows' state words
     was not ordered before the first push on the context's non-blocking stream (a memory access fault).  Here: the failing case
-    of the sweep, 300 fresh contexts, while six other processes keep the GPU busy with fits."""
+    of the sweep, 300 fresh contexts, while five other processes keep the GPU busy with fits (six on the GPU with this
+    one, never more: the GPU may be shared with other jobs)."""
     import os
     import subprocess
     import sys
@@ -146,7 +147,7 @@ def test_growing_pushes_of_a_fresh_context_under_load(engine):
     ref = [go.sliding_window_stream(kid, theta, N, X[w], y[w], include_noise=False) for w in range(nwin)]
     env = dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1")
     load = [subprocess.Popen([sys.executable, os.path.join(root, "tests", "fuzz", "fuzz_parity.py"), "25", str(40 + i)], env=env, cwd=root,
-                             stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) for i in range(6)]
+                             stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) for i in range(5)]
     try:
         bad = 0
         for rep in range(300):
