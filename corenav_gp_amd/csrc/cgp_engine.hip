@@ -5,6 +5,7 @@
 #include "cgp_kernels.hpp"
 #include "cgp_kernels_fused.hpp"
 #include "cgp_window.hpp"
+#include "cgp_window_forecast.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
 #include "cgp_refine.hpp"
@@ -2394,7 +2395,11 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
   if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_pairs<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_pairs<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_pairs<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_multi<kWinMulti>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_multi<kWinMulti>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+      // the forecast keeps a chunk's V = L^-1 K* in LDS: 128 KB + the waves' partial tiles in every form (cgp_window_forecast.hpp)
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<2, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return CGP_EHIP;
   // the old windows are gone from here on: a failure below must leave the context without windows,
   // not with stale pointers (cgp_window_push checks nwin)
@@ -2412,9 +2417,10 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
 #endif
   const int CAP = 2 * N + CGP_WIN_CAP_PAD;   // ring capacity = leading dimension of the windows' slabs
   const size_t W = nwin;
-  size_t sizes[6] = {W * CAP * CAP * 8, W * CAP * 8, W * d * CAP * 8, W * CAP * 8, W * 4 * sizeof(int),
-                     W * (PREP_N + MAX_THETA) * 8};
-  for (int i = 0; i < 6; ++i)
+  // [6]: cgp_window_predict's inverses of the factors' 16 x 16 diagonal blocks (allocated here: no allocation between launches of a call)
+  size_t sizes[7] = {W * CAP * CAP * 8, W * CAP * 8, W * d * CAP * 8, W * CAP * 8, W * 4 * sizeof(int),
+                     W * (PREP_N + MAX_THETA) * 8, W * cdiv(N, WPB) * WPB * WPB * 8};
+  for (int i = 0; i < 7; ++i)
     if (hipMalloc(&c->winbuf[i], sizes[i]) != hipSuccess) {
       c->winbuf[i] = nullptr;
       drop();
@@ -2635,6 +2641,65 @@ extern "C" int cgp_window_push(cgp_ctx *c, int T, const double *xs, const double
   memcpy(pm, h + nx + ny, ny * 8);
   memcpy(pv, h + nx + 2 * ny, ny * 8);
   memcpy(logml, h + nx + 3 * ny, ny * 8);
+  for (size_t w = 0; w < W; ++w)
+    if (hst[w * 4 + 2] != 0) return hst[w * 4 + 2];
+  return CGP_OK;
+}
+
+// ---- forecast from the windows as they stand (cgp_window_forecast.hpp) ----------------------------------------------
+extern "C" int cgp_window_predict_device(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dvar,
+                                         void *hip_stream) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (M < 1 || !dxs || !dmean || !dvar) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  const WindowArgs &wa = c->win;
+  ForecastArgs a{};
+  a.L = wa.L; a.z = wa.z; a.xw = wa.xw; a.state = wa.state; a.prep = wa.prep; a.theta = wa.theta;
+  a.xs = dxs; a.mean = dmean; a.var = dvar;
+  a.dinv = static_cast<double *>(c->winbuf[6]);
+  a.N = wa.N; a.CAP = wa.CAP; a.d = wa.d; a.kernel_id = wa.kernel_id;
+  a.M = M; a.include_noise = include_noise; a.nwin = c->nwin;
+  a.NB = cdiv(wa.N, WPB);
+  // Origin and size are read from the windows' state words on the device (the kernels run after every earlier push of the
+  // stream), so the launches are sized by the capacity N and need no host mirror.  The form depends on N alone.
+  const int mc = wa.N <= 512 ? 32 : (wa.N <= 1024 ? 16 : 8);
+  a.nchunk = cdiv(M, mc);
+  const size_t lds = ((size_t)a.NB * WPB * mc + WF_WAVES * 256) * sizeof(double);   // the chunk's V + the waves' partial tiles
+  const long long total = (long long)c->nwin * a.nchunk;
+  if (total > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
+  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
+  if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  else hipLaunchKernelGGL((k_window_forecast<1, 8>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  if (!hip_ok(c, hipGetLastError(), "window forecast launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_predict(cgp_ctx *c, int M, const double *xs, int include_noise, double *mean, double *var) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (M < 1 || !xs || !mean || !var) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // staged like a push: one pinned block [xs | mean var | state] and its device twin; a small call is read and written in
+  // place by the kernels (no copy command), a large one is one H2D and two D2H
+  const size_t W = c->nwin, nx = W * M * c->win.d, ny = W * M;
+  const size_t ndbl = nx + 2 * ny, bytes = ndbl * 8 + W * 4 * sizeof(int);
+  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(bytes, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
+  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
+  int *hst = reinterpret_cast<int *>(h + ndbl);
+  memcpy(h, xs, nx * 8);
+  hipStream_t s = c->stream;
+  const bool inplace = bytes <= kWinZeroCopyBytes;
+  if (!inplace) HIP_TRY(c, hipMemcpyAsync(d, h, nx * 8, hipMemcpyHostToDevice, s));
+  double *io = inplace ? h : d;
+  int rc = cgp_window_predict_device(c, M, io, include_noise, io + nx, io + nx + ny, s);
+  if (rc != CGP_OK) return rc;
+  if (!inplace) HIP_TRY(c, hipMemcpyAsync(h + nx, d + nx, 2 * ny * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(hst, c->win.state, W * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  memcpy(mean, h + nx, ny * 8);
+  memcpy(var, h + nx + ny, ny * 8);
   for (size_t w = 0; w < W; ++w)
     if (hst[w * 4 + 2] != 0) return hst[w * 4 + 2];
   return CGP_OK;

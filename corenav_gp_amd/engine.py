@@ -66,6 +66,8 @@ _SIGS = {
     "cgp_window_push": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
     "cgp_window_push_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "cgp_window_state": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip]),
+    "cgp_window_predict": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp]),
+    "cgp_window_predict_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "cgp_set_streams": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_set_refine": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_debug_read": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong)]),
@@ -326,6 +328,25 @@ class Context:
     def window_push_device(self, T, dxs, dys, include_noise, dpm, dpv, dlm, stream=0):
         return self._chk(self.lib.cgp_window_push_device(self.h, T, dxs, dys, int(include_noise), dpm, dpv, dlm,
                                                          ctypes.c_void_p(stream)))
+
+    def window_predict(self, xs, include_noise=True, check=True):
+        """Forecast from the windows as they stand: xs (nwin, M, d) (or (M, d) for one window) -> mean, variance, each
+        (nwin, M).  A window that failed in an earlier push raises CgpError (check=False: returns (mean, var, code), that
+        window's outputs NaN)."""
+        nwin, d = self._win
+        xs = _d(xs).reshape(nwin, -1, d)
+        M = xs.shape[1]
+        mean, var = np.empty((nwin, M)), np.empty((nwin, M))
+        rc = self._chk(self.lib.cgp_window_predict(self.h, M, _p(xs), int(include_noise), _p(mean), _p(var)))
+        if not check:
+            return mean, var, rc
+        if rc > 0:
+            raise CgpError(rc)
+        return mean, var
+
+    def window_predict_device(self, M, dxs, include_noise, dmean, dvar, stream=0):
+        return self._chk(self.lib.cgp_window_predict_device(self.h, M, dxs, int(include_noise), dmean, dvar,
+                                                            ctypes.c_void_p(stream)))
 
     def window_state(self, w=0):
         n, info = ctypes.c_int(0), ctypes.c_int(0)

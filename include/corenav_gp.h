@@ -75,7 +75,9 @@ const char *cgp_last_error(const cgp_ctx *ctx);
  * against.  2: cgp_debug_read writes CGP_DEBUG_SLOTS = 512 slots (version 1: 64), and a NULL `hip_stream` is the legacy
  * default stream (version 1: the context's private stream, now CGP_STREAM_CTX).  3 (this header): cgp_set_streams accepts 0
  * (the engine decides; the default, was one group) and cgp_create_ex, cgp_lbfgs_minimize, cgp_sweep_fit_predict_device,
- * cgp_sweep_synchronize, cgp_sweep_context, cgp_set_refine exist; fp32 windows of d <= 3 get a refined mean by default. */
+ * cgp_sweep_synchronize, cgp_sweep_context, cgp_set_refine exist; fp32 windows of d <= 3 get a refined mean by default.
+ * Revision 3 libraries built after the sliding-window forecast was added also export cgp_window_predict and
+ * cgp_window_predict_device (symbols added only: no signature, struct or default moved); probe with dlsym. */
 #define CGP_ABI_VERSION 3
 int cgp_abi_version(void);
 /* How the library was built: 0 for the shipped library.  CGP_BUILD_ABLATION (-DCGP_ABLATION): env
@@ -295,6 +297,23 @@ int cgp_window_push_device(cgp_ctx *ctx, int T, const double *dxs, const double 
                            double *dpred_mean, double *dpred_var, double *dlogml, void *hip_stream);
 /* Current size of window `w` and the first failing tick (0 = none). */
 int cgp_window_state(cgp_ctx *ctx, int w, int *n, int *info);
+/* Forecast from the windows as they stand after the last push: predictive mean and variance of every window at M test
+ * points of its own, xs (nwin, M, d) row-major, outputs (nwin, M).  What the reference's producer publishes per recording
+ * window (gp_slip_node.py:45-61: mean and variance over the next 600 ticks; sigma = 2 sqrt(var) feeds cgp_predict_stop),
+ * computed from the factor, z = L^-1 y and inputs the pushes maintain instead of from a refit:
+ *   V = L^-1 k(X, xs),  mean_j = sum_i V_ij z_i,  var_j = max(k(xs_j, xs_j) - sum_i V_ij^2, 1e-15) (+ sigma_n^2 when include_noise)
+ * (cgp_predict's conventions), always in fp64, n^2 M flops per window on the fp64 matrix cores.  The windows are not modified:
+ * a push after a forecast gives bitwise what it gives without it.  An empty window (no sample pushed yet) answers with the
+ * prior: mean 0, var k(xs_j, xs_j) (+ sigma_n^2).  A window that lost positive definiteness in an earlier push gets NaN in all
+ * of its outputs; the other windows are unaffected.  Returns CGP_ESTATE without windows, CGP_EINVAL for M < 1 or a NULL
+ * pointer, else 0 or, like cgp_window_push, the 1-based tick at which a window failed.  Blocks until the outputs are in the
+ * caller's arrays. */
+int cgp_window_predict(cgp_ctx *ctx, int M, const double *xs, int include_noise, double *mean, double *var);
+/* Device-resident variant: dxs / dmean / dvar are device pointers; two launches enqueued on hip_stream (NULL = legacy
+ * default stream, CGP_STREAM_CTX = the context's own) after the pushes enqueued there earlier, without allocation or
+ * synchronisation (capturable into a hipGraph).  It cannot see a failed window: its NaN outputs and cgp_window_state do. */
+int cgp_window_predict_device(cgp_ctx *ctx, int M, const double *dxs, int include_noise, double *dmean, double *dvar,
+                              void *hip_stream);
 
 /* ---- fp32 contexts: mixed-precision refinement of alpha and the predictive mean -----------------
  * After the single-precision factorisation: alpha_0 = L^-T L^-1 y from the factor, then `steps` times

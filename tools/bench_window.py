@@ -12,6 +12,9 @@ ap.add_argument("--n", type=int, default=512)
 ap.add_argument("--d", type=int, default=3)
 ap.add_argument("--windows", type=int, default=256)
 ap.add_argument("--ticks", type=int, default=2000)
+ap.add_argument("--forecast", type=int, default=0, metavar="M",
+                help="after the pushes: time cgp_window_predict_device at M test points per window (device-resident, events on the stream)")
+ap.add_argument("--reps", type=int, default=20)
 args = ap.parse_args()
 import torch
 import corenav_gp_amd.engine as engine
@@ -42,3 +45,26 @@ print(json.dumps({"metric": "window-ticks/s", "value": W * T / dt, "windows": W,
                   "us_per_tick_per_window": dt / T * 1e6, "algorithmic_GBps": W * T * bytes_tick / dt / 1e9,
                   "hbm_peak_GBps": 8000, "frac": W * T * bytes_tick / dt / 8e12, "info": ctx.window_state(0)[1],
                   "logml_last": float(out[2, 0, -1])}))
+if args.forecast > 0:
+    # n^2 M flops per window on the fp64 matrix cores (78.6 TFLOP/s); the factor (n^2/2 x 8 B) is read once per window from HBM when
+    # the chunks of a window share their XCD's L2
+    M = args.forecast
+    Xs = np.empty((W, M, d))
+    Xs[:, :, 0] = ((t[-1] + 1 + np.arange(M)) - t.mean()) / t.std()
+    Xs[:, :, 1:] = rng.normal(size=(W, M, d - 1))
+    dXs = torch.from_numpy(Xs).to(dev)
+    dm, dv = torch.empty((W, M), device=dev, dtype=torch.float64), torch.empty((W, M), device=dev, dtype=torch.float64)
+    s = torch.cuda.current_stream().cuda_stream
+    for _ in range(3):
+        ctx.window_predict_device(M, dXs.data_ptr(), True, dm.data_ptr(), dv.data_ptr(), s)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.reps):
+        ctx.window_predict_device(M, dXs.data_ptr(), True, dm.data_ptr(), dv.data_ptr(), s)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / args.reps
+    print(json.dumps({"metric": "window-forecasts/s", "value": W / (ms * 1e-3), "windows": W, "N": N, "d": d, "M": M, "ms_per_call": ms,
+                      "frac_of_fp64_mfma_peak": W * float(N) * N * M / (ms * 1e-3) / 78.6e12,
+                      "factor_bytes_once_over_hbm_peak": W * N * N / 2 * 8 / (ms * 1e-3) / 8e12,
+                      "finite": bool(torch.isfinite(dm).all().item() and torch.isfinite(dv).all().item())}))
