@@ -6,6 +6,7 @@
 #include "cgp_kernels_fused.hpp"
 #include "cgp_window.hpp"
 #include "cgp_window_forecast.hpp"
+#include "cgp_window_adapt.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
 #include "cgp_refine.hpp"
@@ -2418,9 +2419,10 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
   const int CAP = 2 * N + CGP_WIN_CAP_PAD;   // ring capacity = leading dimension of the windows' slabs
   const size_t W = nwin;
   // [6]: cgp_window_predict's inverses of the factors' 16 x 16 diagonal blocks (allocated here: no allocation between launches of a call)
-  size_t sizes[7] = {W * CAP * CAP * 8, W * CAP * 8, W * d * CAP * 8, W * CAP * 8, W * 4 * sizeof(int),
-                     W * (PREP_N + MAX_THETA) * 8, W * cdiv(N, WPB) * WPB * WPB * 8};
-  for (int i = 0; i < 7; ++i)
+  // [7]: cgp_window_nll_grad's alpha, per-chunk partial sums and values (cgp_window_adapt.hpp): 28 N / 16 + 1 doubles per window
+  size_t sizes[8] = {W * CAP * CAP * 8, W * CAP * 8, W * d * CAP * 8, W * CAP * 8, W * 4 * sizeof(int),
+                     W * (PREP_N + MAX_THETA) * 8, W * cdiv(N, WPB) * WPB * WPB * 8, W * ((size_t)cdiv(N, WPB) * (WPB + GRAD_N) + 1) * 8};
+  for (int i = 0; i < 8; ++i)
     if (hipMalloc(&c->winbuf[i], sizes[i]) != hipSuccess) {
       c->winbuf[i] = nullptr;
       drop();
@@ -2714,6 +2716,211 @@ extern "C" int cgp_window_state(cgp_ctx *c, int w, int *n, int *info) {
   HIP_TRY(c, hipMemcpy(st, c->win.state + w * 4, sizeof(st), hipMemcpyDeviceToHost));
   if (n) *n = st[1];
   if (info) *info = st[2];
+  return CGP_OK;
+}
+
+// ---- hyper-parameters of the resident windows replaced / re-estimated in place (cgp_window_adapt.hpp) -----------------
+namespace {
+AdaptArgs adapt_args(cgp_ctx *c) {
+  const WindowArgs &wa = c->win;
+  AdaptArgs a{};
+  a.L = wa.L; a.z = wa.z; a.xw = wa.xw; a.yw = wa.yw; a.state = wa.state;
+  a.prep = const_cast<double *>(wa.prep);
+  a.theta = const_cast<double *>(wa.theta);
+  a.N = wa.N; a.CAP = wa.CAP; a.d = wa.d; a.kernel_id = wa.kernel_id; a.nwin = c->nwin;
+  a.NB = cdiv(wa.N, WPB);
+  a.dinv = static_cast<double *>(c->winbuf[6]);
+  double *sc = static_cast<double *>(c->winbuf[7]);
+  a.alpha = sc;
+  a.gpart = sc + (size_t)c->nwin * a.NB * WPB;
+  a.nllv = a.gpart + (size_t)c->nwin * a.NB * GRAD_N;
+  return a;
+}
+}  // namespace
+
+extern "C" int cgp_window_set_theta_device(cgp_ctx *c, const double *dtheta, int theta_stride, const unsigned char *dselect,
+                                           double *dlogml, int *dinfo, void *hip_stream) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (!dtheta || theta_stride < ntheta(c->win.kernel_id, c->win.d)) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  AdaptArgs a = adapt_args(c);
+  a.new_theta = dtheta; a.theta_stride = theta_stride; a.select = dselect; a.logml = dlogml; a.info = dinfo;
+  // origin and size come from the windows' state words; the form (accumulators per wave) depends on N alone
+  if (a.N <= 512) hipLaunchKernelGGL(k_window_refactor<4>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
+  else if (a.N <= 1024) hipLaunchKernelGGL(k_window_refactor<8>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
+  else hipLaunchKernelGGL(k_window_refactor<16>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
+  if (!hip_ok(c, hipGetLastError(), "window refactor launch")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_set_theta(cgp_ctx *c, const double *theta, int theta_stride, const unsigned char *select, double *logml,
+                                    int *info) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  const int nth = ntheta(c->win.kernel_id, c->win.d);
+  if (!theta || theta_stride < nth) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one pinned block [theta | logml | info | select] and its device twin: one H2D, the launch, one D2H, one synchronisation
+  const size_t W = c->nwin, nt = W * nth, ni = (W + 1) / 2, ns = (W + 7) / 8, ndbl = nt + W + ni + ns;
+  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(ndbl * 8, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
+  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
+  for (size_t w = 0; w < W; ++w) memcpy(h + w * nth, theta + w * theta_stride, nth * sizeof(double));
+  unsigned char *hs = reinterpret_cast<unsigned char *>(h + nt + W + ni);
+  for (size_t w = 0; w < W; ++w) hs[w] = select ? (select[w] ? 1 : 0) : 1;
+  int *hi = reinterpret_cast<int *>(h + nt + W);
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemsetAsync(d + nt, 0, (W + ni) * 8, s));   // unselected windows report logML 0, info 0
+  HIP_TRY(c, hipMemcpyAsync(d, h, nt * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d + nt + W + ni, hs, ns * 8, hipMemcpyHostToDevice, s));
+  int rc = cgp_window_set_theta_device(c, d, nth, reinterpret_cast<unsigned char *>(d + nt + W + ni), d + nt, reinterpret_cast<int *>(d + nt + W), s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h + nt, d + nt, (W + ni) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (logml) memcpy(logml, h + nt, W * sizeof(double));
+  if (info) memcpy(info, hi, W * sizeof(int));
+  for (size_t w = 0; w < W; ++w)
+    if (hi[w] != 0) return (int)w + 1;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_nll_grad_device(cgp_ctx *c, double *dnll, double *dgrad, int grad_stride, void *hip_stream) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (!dnll || !dgrad || grad_stride < ntheta(c->win.kernel_id, c->win.d)) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  AdaptArgs a = adapt_args(c);
+  a.nll = dnll; a.grad = dgrad; a.grad_stride = grad_stride;
+  const WindowArgs &wa = c->win;
+  ForecastArgs f{};   // k_window_diag_inv reads the windows and writes the inverses only
+  f.L = wa.L; f.state = wa.state; f.dinv = static_cast<double *>(c->winbuf[6]);
+  f.N = wa.N; f.CAP = wa.CAP; f.d = wa.d; f.kernel_id = wa.kernel_id; f.nwin = c->nwin; f.NB = a.NB;
+  const long long chunks = (long long)c->nwin * a.NB;
+  if (chunks > (1ll << 30)) return CGP_EINVAL;
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, f);
+  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, a);
+  hipLaunchKernelGGL(k_window_kinv_grad, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a);
+  hipLaunchKernelGGL(k_window_grad_finish, dim3((unsigned)cdiv(c->nwin, 64)), dim3(64), 0, ws, a);
+  if (!hip_ok(c, hipGetLastError(), "window gradient launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_nll_grad(cgp_ctx *c, double *nll, double *grad, int grad_stride) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  const int nth = ntheta(c->win.kernel_id, c->win.d);
+  if (!nll || !grad || grad_stride < nth) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t W = c->nwin, ndbl = W * (1 + nth);
+  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(ndbl * 8, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
+  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
+  hipStream_t s = c->stream;
+  int rc = cgp_window_nll_grad_device(c, d, d + W, nth, s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h, d, ndbl * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  memcpy(nll, h, W * sizeof(double));
+  for (size_t w = 0; w < W; ++w) memcpy(grad + w * grad_stride, h + W + w * nth, nth * sizeof(double));
+  return CGP_OK;
+}
+
+// m.optimize() on the resident windows: cgp_optimize_batch's host loop (one batched evaluation per round, every window its own
+// LbfgsStepper and line search) with set_theta + nll_grad on the windows themselves as the evaluation.
+extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
+                                   double *logml_out, int *n_evals) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  const int nth = ntheta(c->win.kernel_id, c->win.d);
+  if (theta_out && theta_stride < nth) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const size_t W = c->nwin;
+  const int cap = max_evals > 0 ? max_evals : 1000;
+  std::vector<double> cur(W * MAX_THETA);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipMemcpy(cur.data(), c->win.theta, cur.size() * sizeof(double), hipMemcpyDeviceToHost));
+  auto sel = [&](size_t w) { return !select || select[w] != 0; };
+  for (size_t w = 0; w < W; ++w)
+    for (int i = 0; i < nth; ++i)
+      if (sel(w) && !(cur[w * MAX_THETA + i] > 0.0)) return CGP_EINVAL;
+  auto to_theta = [](double x) { return x > 35.0 ? x : std::log1p(std::exp(x)); };
+  auto to_x = [](double th) { return th > 35.0 ? th : std::log(std::expm1(th)); };
+  std::vector<corenav::LbfgsStepper> st;
+  st.reserve(W);
+  for (size_t w = 0; w < W; ++w) {
+    std::vector<double> x0(nth);
+    for (int i = 0; i < nth; ++i) x0[i] = sel(w) ? to_x(cur[w * MAX_THETA + i]) : 0.0;
+    st.emplace_back(x0, cap, 1e-5, 1e7);
+  }
+  // staging: [theta | nll | grad | logml | info | select], pinned and on the device
+  const size_t nt = W * nth, ni = (W + 1) / 2, ns = (W + 7) / 8, ndbl = 2 * nt + 2 * W + ni + ns;
+  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(ndbl * 8, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
+  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
+  double *hth = h, *hnll = h + nt, *hgrad = hnll + W, *hlm = hgrad + nt;
+  int *hinfo = reinterpret_cast<int *>(hlm + W);
+  unsigned char *hsel = reinterpret_cast<unsigned char *>(hlm + W + ni);
+  const size_t o_nll = nt, o_grad = nt + W, o_lm = 2 * nt + W, o_info = o_lm + W, o_sel = o_info + ni;
+  std::vector<double> gx(nth);
+  std::vector<char> at_best(W, 1);   // the window holds the factor of its stepper's best point
+  auto set_theta = [&]() -> int {    // the windows marked in hsel take hth
+    HIP_TRY(c, hipMemcpyAsync(d, hth, nt * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d + o_sel, hsel, ns * 8, hipMemcpyHostToDevice, s));
+    return cgp_window_set_theta_device(c, d, nth, reinterpret_cast<unsigned char *>(d + o_sel), d + o_lm, reinterpret_cast<int *>(d + o_info), s);
+  };
+  for (int round = 0; round < cap + 40; ++round) {
+    bool any = false;
+    for (size_t w = 0; w < W; ++w) {
+      const bool act = sel(w) && !st[w].done();
+      hsel[w] = act ? 1 : 0;
+      any = any || act;
+      const std::vector<double> &xx = st[w].trial();
+      for (int i = 0; i < nth; ++i) hth[w * nth + i] = act ? std::max(to_theta(xx[i]), 1e-300) : cur[w * MAX_THETA + i];
+    }
+    if (!any) break;
+    int rc = set_theta();
+    if (rc != CGP_OK) return rc;
+    rc = cgp_window_nll_grad_device(c, d + o_nll, d + o_grad, nth, s);
+    if (rc != CGP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(hnll, d + o_nll, (2 * W + nt + ni) * 8, hipMemcpyDeviceToHost, s));   // nll | grad | logml | info
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (size_t w = 0; w < W; ++w) {
+      if (!hsel[w]) continue;
+      const double *tb = hth + w * nth;
+      for (int i = 0; i < nth; ++i) cur[w * MAX_THETA + i] = tb[i];
+      double f = INFINITY;
+      if (hinfo[w] == 0 && std::isfinite(hnll[w])) {   // a trial point that is not positive definite is infeasible (no jitter ladder)
+        const std::vector<double> &xx = st[w].trial();
+        for (int i = 0; i < nth; ++i) gx[i] = hgrad[w * nth + i] * (xx[i] > 35.0 ? 1.0 : -std::expm1(-tb[i]));
+        f = hnll[w];
+      } else {
+        std::fill(gx.begin(), gx.end(), 0.0);
+      }
+      const std::vector<double> xt = st[w].trial();
+      st[w].tell(f, gx);
+      at_best[w] = st[w].best() == xt;
+    }
+  }
+  // a window whose last trial was not its best point gets the best theta's factor back
+  bool again = false;
+  for (size_t w = 0; w < W; ++w) {
+    hsel[w] = 0;
+    if (!sel(w)) continue;
+    const std::vector<double> &xb = st[w].best();
+    for (int i = 0; i < nth; ++i) hth[w * nth + i] = std::max(to_theta(xb[i]), 1e-300);
+    if (!at_best[w]) {
+      hsel[w] = 1;
+      again = true;
+    }
+  }
+  if (again) {
+    int rc = set_theta();
+    if (rc != CGP_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));
+  }
+  for (size_t w = 0; w < W; ++w) {
+    if (!sel(w)) continue;
+    const corenav::LbfgsResult r = st[w].result();
+    if (theta_out) memcpy(theta_out + w * theta_stride, hth + w * nth, nth * sizeof(double));
+    if (logml_out) logml_out[w] = -r.f;
+    if (n_evals) n_evals[w] = r.evals;
+  }
   return CGP_OK;
 }
 

@@ -68,6 +68,11 @@ _SIGS = {
     "cgp_window_state": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip]),
     "cgp_window_predict": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp]),
     "cgp_window_predict_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    "cgp_window_set_theta": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _vp, _dp, _ip]),
+    "cgp_window_set_theta_device": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "cgp_window_nll_grad": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int]),
+    "cgp_window_nll_grad_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp]),
+    "cgp_window_optimize": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, ctypes.c_int, _dp, _ip]),
     "cgp_set_streams": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_set_refine": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_debug_read": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong)]),
@@ -312,6 +317,7 @@ class Context:
         if theta.ndim == 1:
             theta = np.tile(theta, (nwin, 1))
         self._win = (nwin, d)
+        self._win_nth = 3 if kernel_id == KERNEL_SE_ISO else (d + 2 if kernel_id == KERNEL_SE_ARD else 4)
         self._chk(self.lib.cgp_window_init(self.h, nwin, N, d, kernel_id, _p(theta), theta.shape[1]))
 
     def window_push(self, xs, ys, include_noise=True):
@@ -347,6 +353,55 @@ class Context:
     def window_predict_device(self, M, dxs, include_noise, dmean, dvar, stream=0):
         return self._chk(self.lib.cgp_window_predict_device(self.h, M, dxs, int(include_noise), dmean, dvar,
                                                             ctypes.c_void_p(stream)))
+
+    def _select(self, select):
+        if select is None:
+            return None, None
+        sel = np.ascontiguousarray(np.asarray(select).astype(bool).astype(np.uint8).reshape(self._win[0]))
+        return sel, sel.ctypes.data_as(ctypes.c_void_p)
+
+    def window_set_theta(self, theta, select=None, check=True):
+        """Replaces theta of the selected windows (all when select is None) and rebuilds their factors from the resident
+        samples: theta (nwin, nth) or (nth,) -> (logml, info), each (nwin,).  A window whose matrix is not positive definite
+        under the new theta raises CgpError with that window's 1-based index (check=False: returns (logml, info, code))."""
+        nwin, _ = self._win
+        theta = _d(theta)
+        if theta.ndim == 1:
+            theta = np.ascontiguousarray(np.tile(theta, (nwin, 1)))
+        sel, selp = self._select(select)
+        logml, info = np.empty(nwin), np.zeros(nwin, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_window_set_theta(self.h, _p(theta), theta.shape[1], selp, _p(logml), info.ctypes.data_as(_ip)))
+        if not check:
+            return logml, info, rc
+        if rc > 0:
+            raise CgpError(rc)
+        return logml, info
+
+    def window_set_theta_device(self, dtheta, theta_stride, dselect, dlogml, dinfo, stream=0):
+        return self._chk(self.lib.cgp_window_set_theta_device(self.h, dtheta, theta_stride, dselect, dlogml, dinfo,
+                                                              ctypes.c_void_p(stream)))
+
+    def window_nll_grad(self, nth=None):
+        """Negative log marginal likelihood and its gradient wrt the natural parameters of every window at the theta it
+        holds: (nll (nwin,), grad (nwin, nth))."""
+        nwin, _ = self._win
+        stride = self._win_nth if nth is None else nth
+        nll, grad = np.empty(nwin), np.zeros((nwin, stride))
+        self._chk(self.lib.cgp_window_nll_grad(self.h, _p(nll), _p(grad), stride))
+        return nll, grad
+
+    def window_nll_grad_device(self, dnll, dgrad, grad_stride, stream=0):
+        return self._chk(self.lib.cgp_window_nll_grad_device(self.h, dnll, dgrad, grad_stride, ctypes.c_void_p(stream)))
+
+    def window_optimize(self, max_evals=1000, select=None, nth=None):
+        """m.optimize() on the resident windows, started at the theta each holds: (theta (nwin, nth), logml, n_evals);
+        rows of unselected windows are NaN / 0."""
+        nwin, _ = self._win
+        stride = self._win_nth if nth is None else nth
+        sel, selp = self._select(select)
+        theta, logml, nev = np.full((nwin, stride), np.nan), np.full(nwin, np.nan), np.zeros(nwin, dtype=np.int32)
+        self._chk(self.lib.cgp_window_optimize(self.h, max_evals, selp, _p(theta), stride, _p(logml), nev.ctypes.data_as(_ip)))
+        return theta, logml, nev
 
     def window_state(self, w=0):
         n, info = ctypes.c_int(0), ctypes.c_int(0)

@@ -77,7 +77,9 @@ const char *cgp_last_error(const cgp_ctx *ctx);
  * (the engine decides; the default, was one group) and cgp_create_ex, cgp_lbfgs_minimize, cgp_sweep_fit_predict_device,
  * cgp_sweep_synchronize, cgp_sweep_context, cgp_set_refine exist; fp32 windows of d <= 3 get a refined mean by default.
  * Revision 3 libraries built after the sliding-window forecast was added also export cgp_window_predict and
- * cgp_window_predict_device (symbols added only: no signature, struct or default moved); probe with dlsym. */
+ * cgp_window_predict_device (symbols added only: no signature, struct or default moved); probe with dlsym.  The same holds
+ * for cgp_window_set_theta, cgp_window_set_theta_device, cgp_window_nll_grad, cgp_window_nll_grad_device and
+ * cgp_window_optimize (hyper-parameters of the resident windows replaced / re-estimated in place): revision 3, symbols added only. */
 #define CGP_ABI_VERSION 3
 int cgp_abi_version(void);
 /* How the library was built: 0 for the shipped library.  CGP_BUILD_ABLATION (-DCGP_ABLATION): env
@@ -314,6 +316,56 @@ int cgp_window_predict(cgp_ctx *ctx, int M, const double *xs, int include_noise,
  * synchronisation (capturable into a hipGraph).  It cannot see a failed window: its NaN outputs and cgp_window_state do. */
 int cgp_window_predict_device(cgp_ctx *ctx, int M, const double *dxs, int include_noise, double *dmean, double *dvar,
                               void *hip_stream);
+
+/* ---- hyper-parameters of the resident windows, replaced and re-estimated in place ----------------
+ * The reference re-estimates its hyper-parameters on every window (gp_slip_node.py:36, m.optimize()); cgp_window_init fixes
+ * theta.  The three entry points below change it on the windows a context holds, from what is resident on the device (the
+ * factor, z = L^-1 y, the inputs, the targets): no host mirror of the samples, no re-init, no ticks pushed again.
+ *
+ * cgp_window_set_theta: for every selected window (select[w] != 0; select == NULL: all) store theta (nwin, theta_stride; the
+ * layout of cgp_window_init) and the record derived from it, form Ky = K + (sigma_n^2 + 1e-8) I from the window's resident
+ * inputs, factor it in place at the window's current origin and write z = L^-1 y and the window's log marginal likelihood
+ * (logml[w]; 0 for an empty window).  Origin, size and tick count do not change; a window still filling or empty works (its size
+ * is read from the device state).  The window's failure word is SET from the result: 0 when the factorisation succeeded -- this
+ * is how a window that lost positive definiteness in a push (cgp_window_state info != 0, NaN forecasts) is revived, e.g. with a
+ * larger sigma_n^2 -- and otherwise the LAPACK-style 1-based index of the first non-positive pivot, which info[w] also
+ * receives: cgp_window_state, the forecast's NaN rule and later pushes then treat the window exactly like one a push failed
+ * (logml[w] is NaN).  No jitter ladder (the pushes have none).  theta is validated no more than cgp_window_init validates it:
+ * a theta under which Ky is not positive definite, or a non-finite one, shows up as a failed window, not as an argument error.
+ * Unselected windows are not touched, bit for bit (their logml / info entries are 0); a window's result depends neither on
+ * its slot nor on its neighbours nor on select.  logml and info may be NULL.  Returns CGP_ESTATE without windows, CGP_EINVAL for
+ * a NULL theta or theta_stride < ntheta, else 0 or the 1-based index of the first window that failed.  Blocks.
+ * n^3 / 3 flops per window on the fp64 matrix cores. */
+int cgp_window_set_theta(cgp_ctx *ctx, const double *theta, int theta_stride, const unsigned char *select, double *logml,
+                         int *info);
+/* Device-resident variant: dtheta (nwin, theta_stride), dselect (nwin bytes or NULL), dlogml (nwin or NULL) and dinfo (nwin
+ * or NULL) are device pointers; one launch on hip_stream (NULL = legacy default stream, CGP_STREAM_CTX = the context's own)
+ * without allocation or synchronisation (capturable into a hipGraph).  Entries of unselected windows are not written.
+ * Returns 0 or an argument / runtime error; failed windows show in dinfo and cgp_window_state. */
+int cgp_window_set_theta_device(cgp_ctx *ctx, const double *dtheta, int theta_stride, const unsigned char *dselect,
+                                double *dlogml, int *dinfo, void *hip_stream);
+/* cgp_window_nll_grad: the NEGATIVE log marginal likelihood of every window and its gradient with respect to the natural
+ * parameters (cgp_nll_grad's conventions and theta layout) AT THE THETA THE WINDOW HOLDS, from the factor, z and the inputs as
+ * they stand after any number of pushes: dL/dK = 0.5 (alpha alpha^T - Ky^-1), alpha = L^-T z, contracted with dK/dtheta; Ky^-1
+ * is never stored (2 n^3 / 3 flops per window on the fp64 matrix cores).  nll (nwin), grad (nwin, grad_stride).  A failed
+ * window answers NaN, an empty one 0 and a zero gradient.  The factor (lower triangle and diagonal), z, the samples and the
+ * state words are not written: a push after the call gives bitwise what it gives without it.  Shares a scratch buffer with
+ * cgp_window_predict: the two are not to run concurrently on different streams.  Returns CGP_ESTATE without windows,
+ * CGP_EINVAL for a NULL pointer or grad_stride < ntheta, else 0.  Blocks. */
+int cgp_window_nll_grad(cgp_ctx *ctx, double *nll, double *grad, int grad_stride);
+/* Device-resident variant: four launches on hip_stream, no allocation, no synchronisation (capturable into a hipGraph). */
+int cgp_window_nll_grad_device(cgp_ctx *ctx, double *dnll, double *dgrad, int grad_stride, void *hip_stream);
+/* cgp_window_optimize: m.optimize() on the resident windows.  One L-BFGS (the optimiser of cgp_optimize_batch: Logexp-
+ * transformed parameters, pgtol 1e-5, factr 1e7, at most max_evals evaluations per window, <= 0 meaning 1000) per selected
+ * window, started at the theta the window holds -- every entry must be > 0, else CGP_EINVAL before anything is changed.  One
+ * round = cgp_window_set_theta_device at the trial points + cgp_window_nll_grad_device on the context's stream and one copy
+ * back; each window keeps its own line search, finished windows are deselected.  A trial point whose Ky is not positive
+ * definite is an infeasible point for the line search (no jitter ladder: the pushes that follow would not carry one).  On
+ * return every selected window holds its best theta and the factor that belongs to it; unselected windows are untouched;
+ * pushes and forecasts simply continue.  theta_out (nwin, theta_stride), logml_out (nwin), n_evals (nwin) may be NULL; only
+ * the entries of selected windows are written.  Returns CGP_ESTATE / CGP_EINVAL / 0.  Blocks. */
+int cgp_window_optimize(cgp_ctx *ctx, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
+                        double *logml_out, int *n_evals);
 
 /* ---- fp32 contexts: mixed-precision refinement of alpha and the predictive mean -----------------
  * After the single-precision factorisation: alpha_0 = L^-T L^-1 y from the factor, then `steps` times
