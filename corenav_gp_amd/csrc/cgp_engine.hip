@@ -7,6 +7,7 @@
 #include "cgp_window.hpp"
 #include "cgp_window_forecast.hpp"
 #include "cgp_window_adapt.hpp"
+#include "cgp_window_joint.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
 #include "cgp_refine.hpp"
@@ -120,6 +121,10 @@ struct cgp_ctx {
   int nwin = 0;
   int win_o = 0, win_n = 0;   // origin / size of the windows (they advance in lock-step), mirrored on the host to cut a push into launches
   void *winbuf[8] = {nullptr};
+  // joint forecast (cgp_window_joint_reserve): V kept [nwin][mt][NB * 16][16], the matrix / its factor [nwin][(mt * 16)^2],
+  // mean | variance [2][nwin][max_m], failure words [nwin]
+  void *jointbuf[4] = {nullptr};
+  int joint_max_m = 0;
   // cgp_window_push staging, grown on demand and kept: one pinned host block and one device block per direction
   void *win_pin = nullptr, *win_dev = nullptr;
   size_t win_pin_cap = 0, win_dev_cap = 0;
@@ -1346,6 +1351,8 @@ void cgp_destroy(cgp_ctx *c) {
     if (e) (void)hipEventDestroy(e);
   for (void *wb : c->winbuf)
     if (wb) (void)hipFree(wb);
+  for (void *jb : c->jointbuf)
+    if (jb) (void)hipFree(jb);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -2400,7 +2407,11 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
       // the forecast keeps a chunk's V = L^-1 K* in LDS: 128 KB + the waves' partial tiles in every form (cgp_window_forecast.hpp)
       hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<2, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+      // the same solve with V kept for the joint forecast (cgp_window_joint.hpp)
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<2, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return CGP_EHIP;
   // the old windows are gone from here on: a failure below must leave the context without windows,
   // not with stale pointers (cgp_window_push checks nwin)
@@ -2411,6 +2422,11 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
       if (wb) (void)hipFree(wb);
       wb = nullptr;
     }
+    for (void *&jb : c->jointbuf) {   // the joint forecast's scratch goes with the windows it was sized for
+      if (jb) (void)hipFree(jb);
+      jb = nullptr;
+    }
+    c->joint_max_m = 0;
   };
   drop();
 #ifndef CGP_WIN_CAP_PAD
@@ -2704,6 +2720,158 @@ extern "C" int cgp_window_predict(cgp_ctx *c, int M, const double *xs, int inclu
   memcpy(var, h + nx + ny, ny * 8);
   for (size_t w = 0; w < W; ++w)
     if (hst[w * 4 + 2] != 0) return hst[w * 4 + 2];
+  return CGP_OK;
+}
+
+// ---- joint forecast: full posterior covariance and sample paths (cgp_window_joint.hpp) -------------------------------
+extern "C" int cgp_window_joint_reserve(cgp_ctx *c, int max_m) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (max_m < 1 || max_m > 1024) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());   // an earlier joint forecast may still read the buffers that go
+  for (void *&jb : c->jointbuf) {
+    if (jb) (void)hipFree(jb);
+    jb = nullptr;
+  }
+  c->joint_max_m = 0;
+  const size_t W = c->nwin, mpad = (size_t)cdiv(max_m, WPB) * WPB, nrow = (size_t)cdiv(c->win.N, WPB) * WPB;
+  const size_t sizes[4] = {W * nrow * mpad * 8, W * mpad * mpad * 8, 2 * W * (size_t)max_m * 8, W * sizeof(int)};
+  for (int i = 0; i < 4; ++i)
+    if (hipMalloc(&c->jointbuf[i], sizes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      c->jointbuf[i] = nullptr;
+      for (void *&jb : c->jointbuf) {
+        if (jb) (void)hipFree(jb);
+        jb = nullptr;
+      }
+      return CGP_ENOMEM;
+    }
+  c->joint_max_m = max_m;
+  return CGP_OK;
+}
+
+namespace {
+// the launches both entry points share: diagonal inverses, the solve with V kept (mean to dmean, variance to the scratch), and
+// the contraction -- into the caller's dcov, or (dcov == nullptr) into the scratch matrix for the factorisation
+int window_joint_launch(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dcov, JointArgs &j, hipStream_t ws) {
+  const WindowArgs &wa = c->win;
+  ForecastArgs a{};
+  a.L = wa.L; a.z = wa.z; a.xw = wa.xw; a.state = wa.state; a.prep = wa.prep; a.theta = wa.theta;
+  a.xs = dxs; a.mean = dmean;
+  a.var = static_cast<double *>(c->jointbuf[2]) + (size_t)c->nwin * c->joint_max_m;
+  a.dinv = static_cast<double *>(c->winbuf[6]);
+  a.N = wa.N; a.CAP = wa.CAP; a.d = wa.d; a.kernel_id = wa.kernel_id;
+  a.M = M; a.include_noise = include_noise; a.nwin = c->nwin;
+  a.NB = cdiv(wa.N, WPB);
+  a.vkeep = static_cast<double *>(c->jointbuf[0]);
+  a.mt = cdiv(M, WPB);
+  const int mc = wa.N <= 512 ? 32 : (wa.N <= 1024 ? 16 : 8);   // the forecast's forms, by N alone
+  a.nchunk = cdiv(M, mc);
+  const size_t lds = ((size_t)a.NB * WPB * mc + WF_WAVES * 256) * sizeof(double);
+  j = JointArgs{};
+  j.state = wa.state; j.prep = wa.prep; j.theta = wa.theta; j.xs = dxs;
+  j.V = a.vkeep; j.mean = dmean; j.var = a.var; j.cov = dcov;
+  j.C = static_cast<double *>(c->jointbuf[1]);
+  j.jinfo = static_cast<int *>(c->jointbuf[3]);
+  j.d = wa.d; j.kernel_id = wa.kernel_id; j.M = M; j.nwin = c->nwin;
+  j.mt = a.mt; j.nrow = a.NB * WPB;
+  j.nsup = cdiv(j.mt, WJ_ST);
+  j.npair = j.nsup * (j.nsup + 1) / 2;
+  j.per_win = cdiv(j.npair, WJ_WAVES);
+  const long long total = (long long)c->nwin * a.nchunk, jtotal = (long long)c->nwin * j.per_win;
+  if (total > (1ll << 30) || jtotal > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
+  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS), jgrid = (unsigned)(cdiv((int)jtotal, WF_XCDS) * WF_XCDS);
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
+  if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  else hipLaunchKernelGGL((k_window_forecast<1, 8, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  if (dcov) hipLaunchKernelGGL(k_window_joint_cov<false>, dim3(jgrid), dim3(WJ_THREADS), 0, ws, j);
+  else hipLaunchKernelGGL(k_window_joint_cov<true>, dim3(jgrid), dim3(WJ_THREADS), 0, ws, j);
+  return CGP_OK;
+}
+}  // namespace
+
+extern "C" int cgp_window_predict_cov_device(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dcov,
+                                             void *hip_stream) {
+  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
+  if (M < 1 || !dxs || !dmean || !dcov) return CGP_EINVAL;
+  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  HIP_TRY(c, hipSetDevice(c->device));
+  JointArgs j;
+  int rc = window_joint_launch(c, M, dxs, include_noise, dmean, dcov, j, pick_stream(c, hip_stream));
+  if (rc != CGP_OK) return rc;
+  if (!hip_ok(c, hipGetLastError(), "window joint covariance launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_sample_device(cgp_ctx *c, int M, const double *dxs, int S, const double *dxi, int include_noise,
+                                        double jitter_rel, double *dout, int *dinfo, void *hip_stream) {
+  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
+  if (M < 1 || S < 1 || !dxs || !dxi || !dout || !(jitter_rel >= 0.0)) return CGP_EINVAL;
+  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  JointArgs j;
+  int rc = window_joint_launch(c, M, dxs, include_noise, static_cast<double *>(c->jointbuf[2]), nullptr, j, ws);
+  if (rc != CGP_OK) return rc;
+  j.xi = dxi; j.out = dout; j.S = S; j.info = dinfo; j.jitter_rel = jitter_rel;
+  if (j.mt <= 4 * WA_WAVES) hipLaunchKernelGGL(k_window_joint_chol<4>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, j);
+  else hipLaunchKernelGGL(k_window_joint_chol<8>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, j);
+  const long long per_win = ((long long)j.mt * cdiv(S, WPB) + WJ_WAVES - 1) / WJ_WAVES;   // one wave per 16 x 16 tile of the paths
+  if (per_win * c->nwin > (1ll << 30)) return CGP_EINVAL;
+  j.per_win = (int)per_win;
+  hipLaunchKernelGGL(k_window_joint_paths, dim3((unsigned)(j.per_win * c->nwin)), dim3(WJ_THREADS), 0, ws, j);
+  if (!hip_ok(c, hipGetLastError(), "window sample launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_predict_cov(cgp_ctx *c, int M, const double *xs, int include_noise, double *mean, double *cov) {
+  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
+  if (M < 1 || !xs || !mean || !cov) return CGP_EINVAL;
+  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // device block [xs | mean | cov]; the copies are ordered on the context's stream with the launches
+  const size_t W = c->nwin, nx = W * M * c->win.d, ny = W * M, nc = W * M * M;
+  if (!grow_device(c->win_dev, c->win_dev_cap, (nx + ny + nc) * 8) || !grow_pinned(c->win_pin, c->win_pin_cap, std::max(W * 4 * sizeof(int), kWinZeroCopyBytes)))
+    return CGP_ENOMEM;
+  double *d = static_cast<double *>(c->win_dev);
+  int *hst = static_cast<int *>(c->win_pin);
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(d, xs, nx * 8, hipMemcpyHostToDevice, s));
+  int rc = cgp_window_predict_cov_device(c, M, d, include_noise, d + nx, d + nx + ny, s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(mean, d + nx, ny * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(cov, d + nx + ny, nc * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(hst, c->win.state, W * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  for (size_t w = 0; w < W; ++w)
+    if (hst[w * 4 + 2] != 0) return hst[w * 4 + 2];
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_sample(cgp_ctx *c, int M, const double *xs, int S, const double *xi, int include_noise, double jitter_rel,
+                                 double *out, int *info) {
+  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
+  if (M < 1 || S < 1 || !xs || !xi || !out || !(jitter_rel >= 0.0)) return CGP_EINVAL;
+  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // device block [xs | xi | out | info]
+  const size_t W = c->nwin, nx = W * M * c->win.d, np = W * (size_t)S * M, ni = (W + 1) / 2;
+  if (!grow_device(c->win_dev, c->win_dev_cap, (nx + 2 * np + ni) * 8) || !grow_pinned(c->win_pin, c->win_pin_cap, std::max(W * sizeof(int), kWinZeroCopyBytes)))
+    return CGP_ENOMEM;
+  double *d = static_cast<double *>(c->win_dev);
+  int *hi = static_cast<int *>(c->win_pin);
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(d, xs, nx * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d + nx, xi, np * 8, hipMemcpyHostToDevice, s));
+  int rc = cgp_window_sample_device(c, M, d, S, d + nx, include_noise, jitter_rel, d + nx + np, reinterpret_cast<int *>(d + nx + 2 * np), s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(out, d + nx + np, np * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(hi, d + nx + 2 * np, W * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (info) memcpy(info, hi, W * sizeof(int));
+  for (size_t w = 0; w < W; ++w)
+    if (hi[w] != 0) return (int)w + 1;
   return CGP_OK;
 }
 

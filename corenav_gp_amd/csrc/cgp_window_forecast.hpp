@@ -49,6 +49,9 @@ struct ForecastArgs {
   double *dinv;               // [nwin][NB][16 * 16] inverses of the diagonal blocks, element (row m, column k) at k * 16 + m
   int N, CAP, d, kernel_id, M, include_noise;
   int nwin, nchunk, NB;       // NB = ceil(N / 16) block rows the buffers are sized for
+  // KEEP form only (cgp_window_joint.hpp): V is also stored, [nwin][mt][NB * 16][16] (test-point tile, row, column of the tile)
+  double *vkeep;
+  int mt;                     // test-point tiles of 16 the store is sized for: ceil(M / 16)
 };
 
 // Inverse of every 16 x 16 diagonal block of the windows' factors (blocks counted from the window's origin).  Rows past the
@@ -87,7 +90,9 @@ __global__ __launch_bounds__(64) void k_window_diag_inv(ForecastArgs p) {
 }
 
 // NCT column tiles per workgroup (the waves of a tile split the sum over J WF_WAVES / NCT ways); VW = columns of a tile in use
-template <int NCT, int VW>
+// KEEP: every finished V(I) block is also stored for the joint forecast (cgp_window_joint.hpp); the forms cgp_window_predict
+// launches are the KEEP = false ones
+template <int NCT, int VW, bool KEEP = false>
 __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs p) {
   static_assert((NCT == 1 || NCT == 2) && (VW == 16 || VW == 8), "forms of the forecast kernel");
   constexpr int SPLIT = WF_WAVES / NCT, MC = NCT * VW;
@@ -233,6 +238,11 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
       for (int r = 0; r < 4; ++r) {
         const int row = I * WPB + lq + 4 * r;
         if (VW == 16 || l15 < VW) Vt[(size_t)row * VW + l15] = v[r];
+        if constexpr (KEEP) {   // rows lq + 4 r of the four lane groups are consecutive: 512 contiguous bytes per store
+          const int gc = ch * MC + ct * VW + l15;
+          if ((VW == 16 || l15 < VW) && (gc >> 4) < p.mt)
+            p.vkeep[(((size_t)w * p.mt + (gc >> 4)) * nrow + row) * WPB + (gc & 15)] = v[r];
+        }
         const double zr = row < n ? z[row] : 0.0;
         svz = __builtin_fma(v[r], zr, svz);
         sv2 = __builtin_fma(v[r], v[r], sv2);

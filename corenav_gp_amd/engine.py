@@ -68,6 +68,12 @@ _SIGS = {
     "cgp_window_state": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip]),
     "cgp_window_predict": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp]),
     "cgp_window_predict_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    "cgp_window_joint_reserve": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "cgp_window_predict_cov": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp]),
+    "cgp_window_predict_cov_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    "cgp_window_sample": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_double, _dp, _ip]),
+    "cgp_window_sample_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_double, _vp, _vp,
+                                                _vp]),
     "cgp_window_set_theta": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _vp, _dp, _ip]),
     "cgp_window_set_theta_device": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "cgp_window_nll_grad": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int]),
@@ -353,6 +359,53 @@ class Context:
     def window_predict_device(self, M, dxs, include_noise, dmean, dvar, stream=0):
         return self._chk(self.lib.cgp_window_predict_device(self.h, M, dxs, int(include_noise), dmean, dvar,
                                                             ctypes.c_void_p(stream)))
+
+    def window_joint_reserve(self, max_m):
+        """Scratch for joint forecasts (window_predict_cov / window_sample) of up to max_m test points per window; once
+        after window_init."""
+        return self._chk(self.lib.cgp_window_joint_reserve(self.h, int(max_m)))
+
+    def window_predict_cov(self, xs, include_noise=True, check=True):
+        """Joint forecast from the windows as they stand: xs (nwin, M, d) (or (M, d) for one window) -> mean (nwin, M) and the
+        full posterior covariance (nwin, M, M); include_noise adds the noise variance to the diagonal only.  A window that
+        failed in an earlier push raises CgpError (check=False: returns (mean, cov, code), that window's outputs NaN)."""
+        nwin, d = self._win
+        xs = _d(xs).reshape(nwin, -1, d)
+        M = xs.shape[1]
+        mean, cov = np.empty((nwin, M)), np.empty((nwin, M, M))
+        rc = self._chk(self.lib.cgp_window_predict_cov(self.h, M, _p(xs), int(include_noise), _p(mean), _p(cov)))
+        if not check:
+            return mean, cov, rc
+        if rc > 0:
+            raise CgpError(rc)
+        return mean, cov
+
+    def window_predict_cov_device(self, M, dxs, include_noise, dmean, dcov, stream=0):
+        return self._chk(self.lib.cgp_window_predict_cov_device(self.h, M, dxs, int(include_noise), dmean, dcov,
+                                                                ctypes.c_void_p(stream)))
+
+    def window_sample(self, xs, xi, include_noise=False, jitter_rel=1e-6, check=True):
+        """Sample paths of the joint forecast: xs (nwin, M, d), xi (nwin, S, M) standard normals drawn by the caller ->
+        paths (nwin, S, M) = mean + C xi and info (nwin,), C the Cholesky factor of the posterior covariance (+ noise) +
+        jitter_rel x its mean diagonal.  A window whose matrix is not positive definite gets NaN paths and its 1-based pivot
+        in info, and raises CgpError with the window's 1-based index (check=False: returns (paths, info, code))."""
+        nwin, d = self._win
+        xs = _d(xs).reshape(nwin, -1, d)
+        M = xs.shape[1]
+        xi = _d(xi).reshape(nwin, -1, M)
+        S = xi.shape[1]
+        out, info = np.empty((nwin, S, M)), np.zeros(nwin, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_window_sample(self.h, M, _p(xs), S, _p(xi), int(include_noise), float(jitter_rel), _p(out),
+                                                  info.ctypes.data_as(_ip)))
+        if not check:
+            return out, info, rc
+        if rc > 0:
+            raise CgpError(rc)
+        return out, info
+
+    def window_sample_device(self, M, dxs, S, dxi, include_noise, jitter_rel, dout, dinfo, stream=0):
+        return self._chk(self.lib.cgp_window_sample_device(self.h, M, dxs, S, dxi, int(include_noise), float(jitter_rel), dout,
+                                                           dinfo, ctypes.c_void_p(stream)))
 
     def _select(self, select):
         if select is None:

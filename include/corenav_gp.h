@@ -79,7 +79,9 @@ const char *cgp_last_error(const cgp_ctx *ctx);
  * Revision 3 libraries built after the sliding-window forecast was added also export cgp_window_predict and
  * cgp_window_predict_device (symbols added only: no signature, struct or default moved); probe with dlsym.  The same holds
  * for cgp_window_set_theta, cgp_window_set_theta_device, cgp_window_nll_grad, cgp_window_nll_grad_device and
- * cgp_window_optimize (hyper-parameters of the resident windows replaced / re-estimated in place): revision 3, symbols added only. */
+ * cgp_window_optimize (hyper-parameters of the resident windows replaced / re-estimated in place): revision 3, symbols added only;
+ * and for cgp_window_joint_reserve, cgp_window_predict_cov, cgp_window_predict_cov_device, cgp_window_sample and
+ * cgp_window_sample_device (the joint forecast: full posterior covariance and sample paths). */
 #define CGP_ABI_VERSION 3
 int cgp_abi_version(void);
 /* How the library was built: 0 for the shipped library.  CGP_BUILD_ABLATION (-DCGP_ABLATION): env
@@ -366,6 +368,54 @@ int cgp_window_nll_grad_device(cgp_ctx *ctx, double *dnll, double *dgrad, int gr
  * the entries of selected windows are written.  Returns CGP_ESTATE / CGP_EINVAL / 0.  Blocks. */
 int cgp_window_optimize(cgp_ctx *ctx, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
                         double *logml_out, int *n_evals);
+
+/* ---- joint forecast from the resident windows: full posterior covariance and sample paths ---------
+ * cgp_window_predict answers with the marginals (the diagonal of the posterior).  The reference's model also offers the JOINT
+ * posterior over the horizon -- predict(Xnew, full_cov=True) and posterior_samples_f(Xnew, size) -- which is what a
+ * Monte-Carlo trajectory ensemble needs: one realisation of the whole slip curve per member, correlated from tick to tick.
+ *
+ * cgp_window_joint_reserve: once after cgp_window_init, scratch for joint forecasts of up to max_m test points per window
+ * (V = L^-1 K(X, xs): nwin x N x max_m doubles, and the posterior covariance / its factor: nwin x max_m^2 doubles, both with
+ * max_m and N rounded up to 16; 1 024 windows x N = 512 x max_m = 599 is 2.5 GB + 3.0 GB: the caller decides).
+ * 1 <= max_m <= 1024, else CGP_EINVAL.  CGP_ESTATE without windows, CGP_ENOMEM when the device cannot hold it (an earlier
+ * reservation is gone then).  Calling it again replaces the reservation; a later cgp_window_init drops it with the windows.
+ * Blocks (it synchronises the device). */
+int cgp_window_joint_reserve(cgp_ctx *ctx, int max_m);
+/* cgp_window_predict_cov: mean (nwin, M) and the FULL posterior covariance cov (nwin, M, M) of every window at M test points
+ * of its own, xs (nwin, M, d), all row-major:
+ *   cov = K(xs, xs) - V^T V,  V = L^-1 K(X, xs)
+ * Both triangles are written and are exactly equal.  mean and diag(cov) come from the solve cgp_window_predict runs and are
+ * bitwise its mean / var: the diagonal is clipped at 1e-15 and include_noise != 0 adds sigma_n^2 to the DIAGONAL only (GPy's
+ * predict(full_cov=True, include_likelihood=True)).  n^2 M + n M^2 flops per window on the fp64 matrix cores.  The windows are
+ * not modified.  An empty window answers with the prior: mean 0, cov = K(xs, xs) (+ noise); a failed window gets NaN in all of
+ * its outputs, the others are unaffected.  CGP_ESTATE without windows or without a reservation, CGP_EINVAL for M < 1 or a NULL
+ * pointer, CGP_ECAPACITY for M > max_m, else 0 or, like cgp_window_predict, the 1-based tick at which a window failed.  Blocks.
+ * Shares the scratch of the diagonal blocks' inverses with cgp_window_predict and cgp_window_nll_grad, and its own scratch with
+ * cgp_window_sample: none of these are to run concurrently on different streams of one context. */
+int cgp_window_predict_cov(cgp_ctx *ctx, int M, const double *xs, int include_noise, double *mean, double *cov);
+/* Device-resident variant: device pointers, three launches enqueued one after the other on hip_stream (NULL = legacy default
+ * stream, CGP_STREAM_CTX = the context's own), no allocation, no synchronisation (capturable into a hipGraph).  It cannot see
+ * a failed window: its NaN outputs and cgp_window_state do. */
+int cgp_window_predict_cov_device(cgp_ctx *ctx, int M, const double *dxs, int include_noise, double *dmean, double *dcov,
+                                  void *hip_stream);
+/* cgp_window_sample: S sample paths per window at its M test points, out (nwin, S, M) = mean + C xi, where C is the lower
+ * Cholesky factor of
+ *   A = cov_latent (+ sigma_n^2 I when include_noise)  +  jitter_rel * mean(diag(cov_latent (+ sigma_n^2 I))) * I
+ * and xi (nwin, S, M) are standard normals SUPPLIED BY THE CALLER (torch.randn on the device, numpy on the host): the library
+ * holds no random state, a call is a pure function of its arguments, reproducible across runs and shardings.  xi = unit vectors
+ * returns C's columns (+ mean).  jitter_rel >= 0; a dense grid under a smooth kernel makes cov_latent numerically singular, so
+ * callers should pass 1e-6 (the first rung of GPy's jitchol) unless they know better.  There is no ladder: a window whose A
+ * is still not positive definite gets NaN paths and info[w] = the 1-based failing pivot (0 otherwise; a window that had
+ * failed in an earlier push reports pivot 1); info may be NULL.  The dense covariance is never written to the caller.  Returns
+ * 0 or the 1-based index of the first such window; CGP_ESTATE / CGP_EINVAL (also S < 1, jitter_rel < 0 or NaN) / CGP_ECAPACITY
+ * as cgp_window_predict_cov.  Blocks. */
+int cgp_window_sample(cgp_ctx *ctx, int M, const double *xs, int S, const double *xi, int include_noise, double jitter_rel,
+                      double *out, int *info);
+/* Device-resident variant: five launches on hip_stream, no allocation, no synchronisation (capturable into a hipGraph);
+ * dinfo (nwin ints on the device) may be NULL.  Returns 0 or an argument / state / runtime error; failed factorisations show
+ * in dinfo and as NaN paths. */
+int cgp_window_sample_device(cgp_ctx *ctx, int M, const double *dxs, int S, const double *dxi, int include_noise,
+                             double jitter_rel, double *dout, int *dinfo, void *hip_stream);
 
 /* ---- fp32 contexts: mixed-precision refinement of alpha and the predictive mean -----------------
  * After the single-precision factorisation: alpha_0 = L^-T L^-1 y from the factor, then `steps` times
