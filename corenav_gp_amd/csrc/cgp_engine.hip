@@ -179,7 +179,7 @@ int node_callback_small(cgp_ctx *c, const double *time_array, const double *slip
 bool grow_pinned(void *&p, size_t &cap, size_t bytes);
 bool grow_device(void *&p, size_t &cap, size_t bytes);
 
-inline int ntheta(int kid, int d) { return kid == CGP_KERNEL_SE_ISO ? 3 : (kid == CGP_KERNEL_SE_ARD ? d + 2 : 4); }
+inline int ntheta(int kid, int d) { return k_ntheta(kid, d); }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 bool hip_ok(cgp_ctx *c, hipError_t e, const char *what) {
@@ -336,6 +336,18 @@ template <typename T> int set_lds_attrs(int device) {
   bool ok = true;
   ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, false>), panel_lds_bytes<T>());
   ok = ok && set(reinterpret_cast<const void *>(&k_grad<T>), upd);
+  if constexpr (sizeof(T) == 8) {   // the Matern instantiations (fp64 only)
+    ok = ok && set(reinterpret_cast<const void *>(&k_grad<T, 1>), upd);
+    ok = ok && set(reinterpret_cast<const void *>(&k_grad<T, 2>), upd);
+    ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, false, true, false, true>), panel_lds_bytes<T>());
+    ok = ok && set(reinterpret_cast<const void *>(&k_tile_sk<T, true>), tile);
+    ok = ok && set(reinterpret_cast<const void *>(&k_diag_lean<T, false, true>), paneldiag_lds_bytes<T>());
+    ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, true, true, false, true>), paneldiag_lds_bytes<T>());
+    ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, true, true, true, true>), paneldiag_mid_lds_bytes<T>());
+#ifdef CGP_AB
+    ok = ok && set(reinterpret_cast<const void *>(&k_diag<T, true>), tile);
+#endif
+  }
   ok = ok && set(reinterpret_cast<const void *>(&k_tile_sk<T>), tile);
   ok = ok && set(reinterpret_cast<const void *>(&k_trmm_sk<T>), upd);
   ok = ok && set(reinterpret_cast<const void *>(&k_diag_lean<T>), paneldiag_lds_bytes<T>());
@@ -464,20 +476,34 @@ const SchedSwitches &sched_switches() {
   return sw;
 }
 
+// A launch of a kernel that builds Gram tiles: a Matern fit (fp64 contexts only, check_shape) runs the kernel's MAT = true
+// instantiation, every other kernel id the instantiation it ran before the Matern kernels existed.
+#define CGP_LAUNCH_GRAM(T, A, KERN, KERN_MAT, ...)                    \
+  do {                                                                \
+    bool cgp_matern_ = false;                                         \
+    if constexpr (sizeof(T) == 8) {                                   \
+      if (k_is_matern((A).kernel_id)) {                               \
+        hipLaunchKernelGGL(KERN_MAT, __VA_ARGS__);                    \
+        cgp_matern_ = true;                                           \
+      }                                                               \
+    }                                                                 \
+    if (!cgp_matern_) hipLaunchKernelGGL(KERN, __VA_ARGS__);          \
+  } while (0)
+
 // k_panel<T, true> has two builds: the full-batch one, and the one for calls that leave CUs underfilled (kinds C /
 // image-A compiled in; fp32: deep-prefetch loops)
 template <typename T> void launch_panel_diag(bool mid, dim3 grid, hipStream_t s, const FitArgs &a, int k) {
   if (mid) {
-    hipLaunchKernelGGL((k_panel<T, true, true, true>), grid, dim3(256), paneldiag_mid_lds_bytes<T>(), s, a, k);
+    CGP_LAUNCH_GRAM(T, a, (k_panel<T, true, true, true>), (k_panel<T, true, true, true, true>), grid, dim3(256), paneldiag_mid_lds_bytes<T>(), s, a, k);
     return;
   }
   if constexpr (CGP_F32_FULL_DEEP && sizeof(T) == 4) hipLaunchKernelGGL((k_panel<T, true, true, false>), grid, dim3(256), paneldiag_lds_bytes<T>(), s, a, k);
-  else hipLaunchKernelGGL((k_panel<T, true>), grid, dim3(256), paneldiag_lds_bytes<T>(), s, a, k);
+  else CGP_LAUNCH_GRAM(T, a, (k_panel<T, true>), (k_panel<T, true, true, false, true>), grid, dim3(256), paneldiag_lds_bytes<T>(), s, a, k);
 }
 
 // The extra-row tiles of block step k alone (rows_from_extra), in the loop flavour of the mid-size build
 template <typename T> void launch_panel_rows(dim3 grid, hipStream_t s, const FitArgs &a, int k) {
-  hipLaunchKernelGGL((k_panel<T, false, true, false>), grid, dim3(256), panel_lds_bytes<T>(), s, a, k);
+  CGP_LAUNCH_GRAM(T, a, (k_panel<T, false, true, false>), (k_panel<T, false, true, false, true>), grid, dim3(256), panel_lds_bytes<T>(), s, a, k);
 }
 
 template <typename T> void launch_diag(const FitArgs &a, int nfits, int k, bool fat, hipStream_t s, bool mid = false) {
@@ -489,12 +515,12 @@ template <typename T> void launch_diag(const FitArgs &a, int nfits, int k, bool 
   }
 #ifdef CGP_AB
   if (fat) {
-    hipLaunchKernelGGL(k_diag<T>, dim3(nfits), dim3(256), potf2_lds_bytes<T>(), s, a, k);
+    CGP_LAUNCH_GRAM(T, a, (k_diag<T>), (k_diag<T, true>), dim3(nfits), dim3(256), potf2_lds_bytes<T>(), s, a, k);
     return;
   }
 #endif
   (void)fat;
-  hipLaunchKernelGGL(k_diag_lean<T>, dim3(nfits), dim3(256), paneldiag_lds_bytes<T>(), s, a, k);
+  CGP_LAUNCH_GRAM(T, a, (k_diag_lean<T>), (k_diag_lean<T, false, true>), dim3(nfits), dim3(256), paneldiag_lds_bytes<T>(), s, a, k);
 }
 
 // A mid-size fit call as ONE persistent launch (k_sched, cgp_kernels_fused.hpp): the tile programs of the NT + 1 launches
@@ -846,7 +872,7 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
     }
   }
   const int panel_lds = panel_lds_bytes<T>();
-  if (mid && !latency && in_rows && !c->prof && a.NT >= 2 && sched_enabled() && !sw.split_diag && !sw.overlap) {
+  if (mid && !latency && in_rows && !c->prof && a.NT >= 2 && sched_enabled() && !k_is_matern(a.kernel_id) && !sw.split_diag && !sw.overlap) {
     launch_diag<T>(ga[0], batch, 0, sw.fat_diag, s, true);   // diagonal tile 0: nothing to run beside it yet
     int rc = run_sched<T>(c, ga[0], batch, s);
     if (rc != CGP_OK) return rc;
@@ -880,13 +906,13 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
       const int n2 = (has_p1 ? nin - 1 : 0) + a.ET;                // P2: everything but the first tile
       if (has_p1) {
         if (k > 0) HIP_TRY(c, hipStreamWaitEvent(sA, ev(3 * (k - 1) + 2), 0));  // P2(k-1)
-        hipLaunchKernelGGL((k_panel<T, false>), dim3(1, B), dim3(256), panel_lds, sA, a1, k);
+        CGP_LAUNCH_GRAM(T, a1, (k_panel<T, false>), (k_panel<T, false, true, false, true>), dim3(1, B), dim3(256), panel_lds, sA, a1, k);
         HIP_TRY(c, hipEventRecord(ev(3 * k + 1), sA));             // evP1[k]
       }
       HIP_TRY(c, hipStreamWaitEvent(sB, ev(3 * k), 0));            // diag(k)
       if (k > 0 && NT - k >= 1) HIP_TRY(c, hipStreamWaitEvent(sB, ev(3 * (k - 1) + 1), 0));  // P1(k-1)
       FitArgs ap = has_p1 ? a2 : a1;
-      hipLaunchKernelGGL((k_panel<T, false>), dim3(n2, B), dim3(256), panel_lds, sB, ap, k);
+      CGP_LAUNCH_GRAM(T, ap, (k_panel<T, false>), (k_panel<T, false, true, false, true>), dim3(n2, B), dim3(256), panel_lds, sB, ap, k);
       HIP_TRY(c, hipEventRecord(ev(3 * k + 2), sB));               // evP2[k]
       if (k + 1 < NT) {
         if (!has_p1 && k > 0) HIP_TRY(c, hipStreamWaitEvent(sA, ev(3 * (k - 1) + 2), 0));
@@ -922,7 +948,7 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
       L[0].begin(0, panel_flops(a.N, a.M, a.d, k, in_rows, batch) + (in_rows ? diag_flops(a.N, a.d, k, batch) : 0.0), k);
       // z also carries the pre-update workgroups of the NEXT diagonal tile (1 + images of tile k + 1)
       const int gz = in_rows ? std::max(sk, 1 + (k + 1 < a.NT ? lat_images(k + 1) : 0)) : sk;
-      hipLaunchKernelGGL(k_tile_sk<T>, dim3(nslots, batch, gz), dim3(256), in_rows ? tile_lds : upd_lds, s, ga[0], q, k);
+      CGP_LAUNCH_GRAM(T, ga[0], (k_tile_sk<T>), (k_tile_sk<T, true>), dim3(nslots, batch, gz), dim3(256), in_rows ? tile_lds : upd_lds, s, ga[0], q, k);
       L[0].end();
       if (split_trmm) {
         L[0].begin(2, trsm_flops(a.N, a.M, k, in_rows, batch));
@@ -981,7 +1007,7 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
       }
       if (split_diag) {
         L[g].begin(0, panel_flops(a.N, a.M, a.d, k, in_rows, gb[g]), k);
-        hipLaunchKernelGGL((k_panel<T, false>), dim3(gx_t, gb[g]), dim3(256), panel_lds, gs[g], ga[g], k);
+        CGP_LAUNCH_GRAM(T, ga[g], (k_panel<T, false>), (k_panel<T, false, true, false, true>), dim3(gx_t, gb[g]), dim3(256), panel_lds, gs[g], ga[g], k);
         L[g].end();
         continue;
       }
@@ -1077,8 +1103,9 @@ FitArgs base_args(cgp_ctx *c, int N, int d, int M, int kid, int include_noise) {
 int check_shape(const cgp_ctx *c, int batch, int N, int d, int M, int kid) {
   if (!c) return CGP_EINVAL;
   if (batch < 1 || N < 1 || d < 1 || M < 0) return CGP_EINVAL;
-  if (kid < 0 || kid > 2) return CGP_EINVAL;
+  if (kid < 0 || kid > CGP_KERNEL_MATERN52_ARD) return CGP_EINVAL;
   if (kid == CGP_KERNEL_RBF_BROWNIAN && d != 1) return CGP_EINVAL;
+  if (k_is_matern(kid) && c->dtype != CGP_F64) return CGP_EINVAL;   // the Matern kernels are fp64 paths (corenav_gp.h)
   if (batch > c->max_batch || N > c->max_n || M > c->max_m || d > c->max_d) return CGP_ECAPACITY;
   return CGP_OK;
 }
@@ -1490,7 +1517,7 @@ int cgp_fit_predict_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int
   a.info = dinfo;
   c->have_fit = false;
   c->lazy_fit = false;
-  if (small_batch_predict_ok(c, batch, N, d, M)) {   // short windows: fit + predictions of the whole batch in ONE launch, factors in LDS
+  if (!k_is_matern(kid) && small_batch_predict_ok(c, batch, N, d, M)) {   // short windows: fit + predictions of the whole batch in ONE launch, factors in LDS
     const SmallDev dev{static_cast<const double *>(dX), static_cast<const double *>(dy), static_cast<const double *>(dXs), dtheta, djitter, dlogml, dinfo};
     const int tab = c->pending_tab;   // only the host-buffer entry point knows whether the inputs are tick counts
     c->pending_tab = 0;
@@ -1866,6 +1893,21 @@ int cgp_gppredictor_callback(const double *mean, const double *sigma, int M, con
 
 namespace {
 // One gradient-mode evaluation on the device for the window already uploaded to slot 0.
+// k_grad of the fit's kernel: the Matern pair has instantiations of its own (fp64; check_shape refuses them in fp32 contexts)
+template <typename T> void launch_grad(const FitArgs &a, int npairs, int batch, hipStream_t s) {
+  if constexpr (sizeof(T) == 8) {
+    if (a.kernel_id == K_MATERN32_ARD) {
+      hipLaunchKernelGGL((k_grad<T, 1>), dim3(npairs, batch), dim3(256), upd_lds_bytes<T>(), s, a, npairs);
+      return;
+    }
+    if (a.kernel_id == K_MATERN52_ARD) {
+      hipLaunchKernelGGL((k_grad<T, 2>), dim3(npairs, batch), dim3(256), upd_lds_bytes<T>(), s, a, npairs);
+      return;
+    }
+  }
+  hipLaunchKernelGGL(k_grad<T>, dim3(npairs, batch), dim3(256), upd_lds_bytes<T>(), s, a, npairs);
+}
+
 template <typename T>
 int grad_eval(cgp_ctx *c, int N, int d, int kid, double *logml, double sums[GRAD_N], int *info) {
   hipStream_t s = c->stream;
@@ -1887,7 +1929,7 @@ int grad_eval(cgp_ctx *c, int N, int d, int kid, double *logml, double sums[GRAD
   a.info = reinterpret_cast<int *>(c->dgpart + npart + 1);
   int rc = run(c, a, 1, true, true, s);
   if (rc != CGP_OK) return rc;
-  hipLaunchKernelGGL(k_grad<T>, dim3(npairs, 1), dim3(256), upd_lds_bytes<T>(), s, a, npairs);
+  launch_grad<T>(a, npairs, 1, s);
   HIP_TRY(c, hipGetLastError());
   if (!grow_pinned(c->opt_pin, c->opt_pin_cap, (kOptPinIn + npart + 2) * sizeof(double))) return CGP_ENOMEM;
   double *part = static_cast<double *>(c->opt_pin) + kOptPinIn, *hl = part + npart;
@@ -1961,6 +2003,9 @@ bool small_enabled() {   // CGP_SMALL=off: the large-window machinery for every 
   return !off;
 }
 inline bool small_ok(const cgp_ctx *c, int N) { return c->dtype == CGP_F64 && N <= SM_MAX_N && c->dsmall && small_enabled(); }
+// k_small / k_small_predict hold the squared-exponential and Brownian forms only: a Matern call of any length takes the tiled
+// schedules and the host optimiser over device gradients (which form runs stays a function of (kernel, N, d, M) alone)
+inline bool small_ok(const cgp_ctx *c, int N, int kid) { return !k_is_matern(kid) && small_ok(c, N); }
 
 // Tick-grid table of the short-window kernels (SmallArgs::tab_n): entries needed when every input is integer-valued and small
 // enough for r^2 to be exact, 0 otherwise.  ad hoc off-switch for A/B and the bitwise test: CGP_TICKTAB=off.
@@ -2245,7 +2290,7 @@ extern "C" int cgp_nll_grad(cgp_ctx *c, const double *X, const double *y, int N,
   if (rc != CGP_OK) return rc;
   if (!X || !y || !theta || !nll || !grad) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (small_ok(c, N)) return small_nll_grad(c, X, y, N, d, kid, theta, nll, grad);
+  if (small_ok(c, N, kid)) return small_nll_grad(c, X, y, N, d, kid, theta, nll, grad);
   c->lazy_fit = false;
   rc = upload_window(c, X, y, N, d, c->stream);
   if (rc != CGP_OK) return rc;
@@ -2268,7 +2313,7 @@ extern "C" int cgp_optimize(cgp_ctx *c, const double *X, const double *y, int N,
   }
   int hard_error = CGP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (small_ok(c, N)) return small_optimize(c, X, y, N, d, kid, theta, max_evals, logml, n_evals);
+  if (small_ok(c, N, kid)) return small_optimize(c, X, y, N, d, kid, theta, max_evals, logml, n_evals);
   c->lazy_fit = false;
   rc = upload_window(c, X, y, N, d, c->stream);   // the window does not change between evaluations: only theta travels
   if (rc != CGP_OK) return rc;
@@ -2302,7 +2347,7 @@ namespace {
 int node_callback_small(cgp_ctx *c, const double *time_array, const double *slip_array, int n, int kid, double *theta, int max_evals,
                         double *mean, double *sigma, int cap, int *m_out) {
   const int ntr = (int)(0.9 * (double)n);  // gp_slip_node.py:27-29
-  if (ntr < 1 || !small_ok(c, ntr) || check_shape(c, 1, ntr, 1, ntr, kid) != CGP_OK) return CGP_ESTATE;
+  if (ntr < 1 || !small_ok(c, ntr, kid) || check_shape(c, 1, ntr, 1, ntr, kid) != CGP_OK) return CGP_ESTATE;
   const int nth = ntheta(kid, 1);
   for (int i = 0; i < nth; ++i)
     if (!(theta[i] > 0.0)) return max_evals > 0 ? CGP_EINVAL : CGP_ESTATE;
@@ -2394,8 +2439,9 @@ extern "C" int cgp_slip_node_callback_opt(cgp_ctx *c, const double *time_array, 
 }
 
 extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, const double *theta, int theta_stride) {
-  if (!c || nwin < 1 || N < 2 || N > 2048 || d < 1 || d > CGP_MAX_D || !theta || kid < 0 || kid > 2) return CGP_EINVAL;
+  if (!c || nwin < 1 || N < 2 || N > 2048 || d < 1 || d > CGP_MAX_D || !theta || kid < 0 || kid > CGP_KERNEL_MATERN52_ARD) return CGP_EINVAL;
   if (kid == CGP_KERNEL_RBF_BROWNIAN && d != 1) return CGP_EINVAL;
+  if (k_is_matern(kid) && c->dtype != CGP_F64) return CGP_EINVAL;
   const int nth = ntheta(kid, d);
   if (theta_stride < nth) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2413,6 +2459,17 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
       hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return CGP_EHIP;
+  if (k_is_matern(kid)) {   // the same limits for the Matern instantiations of those kernels
+    const void *fn150[] = {reinterpret_cast<const void *>(&k_window_pairs<1, true>), reinterpret_cast<const void *>(&k_window_pairs<2, true>),
+                           reinterpret_cast<const void *>(&k_window_pairs<4, true>)};
+    const void *fn160[] = {reinterpret_cast<const void *>(&k_window_forecast<2, 16, false, true>), reinterpret_cast<const void *>(&k_window_forecast<1, 16, false, true>),
+                           reinterpret_cast<const void *>(&k_window_forecast<1, 8, false, true>), reinterpret_cast<const void *>(&k_window_forecast<2, 16, true, true>),
+                           reinterpret_cast<const void *>(&k_window_forecast<1, 16, true, true>), reinterpret_cast<const void *>(&k_window_forecast<1, 8, true, true>)};
+    for (const void *fn : fn150)
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return CGP_EHIP;
+    for (const void *fn : fn160)
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CGP_EHIP;
+  }
   // the old windows are gone from here on: a failure below must leave the context without windows,
   // not with stale pointers (cgp_window_push checks nwin)
   c->nwin = 0;
@@ -2461,7 +2518,7 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
   for (size_t w = 0; w < W; ++w) {
     const double *th = theta + w * theta_stride;
     double *o = h.data() + w * PREP_N;
-    for (int q = 0; q < d; ++q) o[q] = (kid == CGP_KERNEL_SE_ARD) ? 1.0 / th[1 + q] : 1.0 / th[1];
+    for (int q = 0; q < d; ++q) o[q] = k_is_ard(kid) ? 1.0 / th[1 + q] : 1.0 / th[1];
     o[9] = th[0];
     o[10] = (kid == CGP_KERNEL_RBF_BROWNIAN) ? th[2] : 0.0;
     for (int q = 0; q < nth; ++q) h[W * PREP_N + w * MAX_THETA + q] = th[q];
@@ -2562,7 +2619,11 @@ int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, in
     for (int oo = o; pair_ok(oo, n, T - t - 2 * np); oo += 2) ++np;
     if (np > 0) {
       a.nt = 2 * np;
-      if (wpw == 4) hipLaunchKernelGGL(k_window_pairs<4>, dim3(c->nwin / 4), dim3(256), 4 * lds2 + kWinPairStage, ws, a);
+      if (k_is_matern(a.kernel_id)) {
+        if (wpw == 4) hipLaunchKernelGGL((k_window_pairs<4, true>), dim3(c->nwin / 4), dim3(256), 4 * lds2 + kWinPairStage, ws, a);
+        else if (wpw == 2) hipLaunchKernelGGL((k_window_pairs<2, true>), dim3(c->nwin / 2), dim3(256), 2 * lds2 + kWinPairStage, ws, a);
+        else hipLaunchKernelGGL((k_window_pairs<1, true>), dim3(c->nwin), dim3(256), lds2 + kWinPairStage, ws, a);
+      } else if (wpw == 4) hipLaunchKernelGGL(k_window_pairs<4>, dim3(c->nwin / 4), dim3(256), 4 * lds2 + kWinPairStage, ws, a);
       else if (wpw == 2) hipLaunchKernelGGL(k_window_pairs<2>, dim3(c->nwin / 2), dim3(256), 2 * lds2 + kWinPairStage, ws, a);
       else hipLaunchKernelGGL(k_window_pairs<1>, dim3(c->nwin), dim3(256), lds2 + kWinPairStage, ws, a);
       o += 2 * np;
@@ -2688,7 +2749,11 @@ extern "C" int cgp_window_predict_device(cgp_ctx *c, int M, const double *dxs, i
   if (total > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
   const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
   hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
-  if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  if (k_is_matern(a.kernel_id)) {
+    if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16, false, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+    else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16, false, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+    else hipLaunchKernelGGL((k_window_forecast<1, 8, false, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  } else if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
   else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
   else hipLaunchKernelGGL((k_window_forecast<1, 8>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
   if (!hip_ok(c, hipGetLastError(), "window forecast launches")) return CGP_EHIP;
@@ -2782,7 +2847,11 @@ int window_joint_launch(cgp_ctx *c, int M, const double *dxs, int include_noise,
   if (total > (1ll << 30) || jtotal > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
   const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS), jgrid = (unsigned)(cdiv((int)jtotal, WF_XCDS) * WF_XCDS);
   hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
-  if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  if (k_is_matern(a.kernel_id)) {
+    if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16, true, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+    else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16, true, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+    else hipLaunchKernelGGL((k_window_forecast<1, 8, true, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
+  } else if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
   else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
   else hipLaunchKernelGGL((k_window_forecast<1, 8, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
   if (dcov) hipLaunchKernelGGL(k_window_joint_cov<false>, dim3(jgrid), dim3(WJ_THREADS), 0, ws, j);
@@ -2915,7 +2984,11 @@ extern "C" int cgp_window_set_theta_device(cgp_ctx *c, const double *dtheta, int
   AdaptArgs a = adapt_args(c);
   a.new_theta = dtheta; a.theta_stride = theta_stride; a.select = dselect; a.logml = dlogml; a.info = dinfo;
   // origin and size come from the windows' state words; the form (accumulators per wave) depends on N alone
-  if (a.N <= 512) hipLaunchKernelGGL(k_window_refactor<4>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
+  if (k_is_matern(a.kernel_id)) {
+    if (a.N <= 512) hipLaunchKernelGGL((k_window_refactor<4, true>), dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
+    else if (a.N <= 1024) hipLaunchKernelGGL((k_window_refactor<8, true>), dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
+    else hipLaunchKernelGGL((k_window_refactor<16, true>), dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
+  } else if (a.N <= 512) hipLaunchKernelGGL(k_window_refactor<4>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
   else if (a.N <= 1024) hipLaunchKernelGGL(k_window_refactor<8>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
   else hipLaunchKernelGGL(k_window_refactor<16>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
   if (!hip_ok(c, hipGetLastError(), "window refactor launch")) return CGP_EHIP;
@@ -3270,7 +3343,7 @@ int grad_eval_batch(cgp_ctx *c, int batch, int N, int d, int kid, std::vector<do
   int rc = run(c, a, batch, true, true, s);
   if (rc != CGP_OK) return rc;
   const int npairs = a.NT * (a.NT + 1) / 2;
-  hipLaunchKernelGGL(k_grad<T>, dim3(npairs, batch), dim3(256), upd_lds_bytes<T>(), s, a, npairs);
+  launch_grad<T>(a, npairs, batch, s);
   HIP_TRY(c, hipGetLastError());
   std::vector<double> part((size_t)batch * npairs * GRAD_N);
   logml.resize(batch);
@@ -3294,7 +3367,7 @@ void grad_from_sums(int kid, int d, const double *theta, const double *sums, dou
     grad[0] = -0.5 * sums[0] / theta[0];
     grad[1] = -0.5 * se / theta[1];
     grad[2] = -0.5 * sums[9];
-  } else if (kid == CGP_KERNEL_SE_ARD) {
+  } else if (k_is_ard(kid)) {   // Matern: k_grad<T, MAT> put -2 dk/dr^2 where the squared exponential has k, so the formulas are SE_ARD's
     grad[0] = -0.5 * sums[0] / theta[0];
     for (int q = 0; q < d; ++q) grad[1 + q] = -0.5 * sums[1 + q] / theta[1 + q];
     grad[d + 1] = -0.5 * sums[9];
@@ -3325,7 +3398,7 @@ extern "C" int cgp_optimize_batch(cgp_ctx *c, int batch, int N, int d, int kid, 
   HIP_TRY(c, hipMemcpyAsync(c->dX, hx.data(), hx.size(), hipMemcpyHostToDevice, s));
   HIP_TRY(c, hipMemcpyAsync(c->dy, hy.data(), hy.size(), hipMemcpyHostToDevice, s));
   c->lazy_fit = false;
-  if (small_ok(c, N)) {
+  if (small_ok(c, N, kid)) {
     // short windows: ONE launch, one workgroup per window, each running its own L-BFGS loop on the device (cgp_small.hpp)
     for (int b = 0; b < batch; ++b)
       for (int i = 0; i < nth; ++i)

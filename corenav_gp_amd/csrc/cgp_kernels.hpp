@@ -50,7 +50,11 @@ constexpr int WIMG = NCB * (NCB + 1) / 2 * DB * DB;
 constexpr double RF_RHO = 12.0;
 __host__ __device__ __forceinline__ constexpr int wimg_blk(int cb, int qb) { return (cb * (cb + 1) / 2 + qb) * DB * DB; }
 
-enum { K_SE_ISO = 0, K_SE_ARD = 1, K_RBF_BROWNIAN = 2 };
+enum { K_SE_ISO = 0, K_SE_ARD = 1, K_RBF_BROWNIAN = 2, K_MATERN32_ARD = 3, K_MATERN52_ARD = 4 };
+// kernels with one length-scale per input dimension (theta = [sigma_f^2, ell_1 .. ell_d, sigma_n^2]), and the Matern pair (fp64 only)
+__host__ __device__ __forceinline__ constexpr bool k_is_ard(int kid) { return kid == K_SE_ARD || kid >= K_MATERN32_ARD; }
+__host__ __device__ __forceinline__ constexpr bool k_is_matern(int kid) { return kid >= K_MATERN32_ARD; }
+__host__ __device__ __forceinline__ constexpr int k_ntheta(int kid, int d) { return kid == K_SE_ISO ? 3 : (k_is_ard(kid) ? d + 2 : 4); }
 
 struct FitArgs {
   void *Lw;              // [batch][NT*128 cols][ld rows]
@@ -263,6 +267,32 @@ __device__ __forceinline__ double exp_nonpos(double x, const ExpC &e) {
   return __builtin_amdgcn_ldexp(q, (int)n);
 }
 __device__ __forceinline__ float exp_nonpos(float x, const ExpC &) { return __expf(fmaxf(x, -104.f)); }
+
+// The Matern radial functions of the scaled squared distance r2 = sum_q ((x_q - x'_q) / ell_q)^2, amplitude 1:
+//   nu = 3/2: k = (1 + s) e^-s, s = sqrt(3 r2)          -2 dk/dr2 = 3 e^-s
+//   nu = 5/2: k = (1 + s + s^2 / 3) e^-s, s = sqrt(5 r2)  -2 dk/dr2 = (5/3) (1 + s) e^-s
+// Both are Lipschitz in r2 (no quotient by r anywhere), so a rounding error in r2 -- which is a difference of inner products in
+// the tile schedules -- reaches k with a factor of at most 1.5, as it does for the squared exponential (0.5).  `g`, the factor
+// the length-scale gradient carries where the squared exponential has k itself (dk/dell_q = g d_q^2 / ell_q^3), is formed
+// only where WITH_G asks for it.  `ex` is the exponential to use (exp_nonpos with the caller's coefficients, or exp).
+template <bool M52, bool WITH_G, typename EX>
+__device__ __forceinline__ double matern_radial(double r2, double &g, EX ex) {
+  r2 = r2 < 0.0 ? 0.0 : r2;
+  const double s = __builtin_sqrt((M52 ? 5.0 : 3.0) * r2);
+  const double e = ex(-s);
+  if (M52) {
+    if (WITH_G) g = (5.0 / 3.0) * (1.0 + s) * e;
+    return __builtin_fma(5.0 / 3.0, r2, 1.0 + s) * e;
+  }
+  if (WITH_G) g = 3.0 * e;
+  return (1.0 + s) * e;
+}
+// the same with the kernel as a (wave-uniform) run-time argument: the register-level covariance of the sliding windows
+template <bool WITH_G>
+__device__ __forceinline__ double matern_radial_rt(int kid, double r2, double &g) {
+  auto ex = [](double x) { return exp(x); };
+  return kid == K_MATERN52_ARD ? matern_radial<true, WITH_G>(r2, g, ex) : matern_radial<false, WITH_G>(r2, g, ex);
+}
 
 // One 16x16 diagonal block in the registers of a wavefront: lane holds row (lane & 15) of the block
 // in a[] (replicated over the four 16-lane groups).  On return a[] holds the row of the Cholesky
@@ -714,7 +744,7 @@ __global__ __launch_bounds__(256) void k_finalize(FitArgs p, int do_logml) {
   const size_t rb = (size_t)p.NT * TS;  // first extra row
   const double *th = p.theta + (size_t)b * MAX_THETA;
   const int kid = p.kernel_id;
-  const int nth = (kid == K_SE_ISO) ? 3 : (kid == K_SE_ARD ? p.d + 2 : 4);
+  const int nth = k_ntheta(kid, p.d);
   // RB test rows per block, 256 / RB column groups (RB = 16 for the latency schedule: 4x the blocks)
   constexpr int NG = 256 / RB;
   const int nmb = (M + RB - 1) / RB;

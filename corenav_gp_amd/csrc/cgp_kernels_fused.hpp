@@ -1011,7 +1011,10 @@ static_assert(2 * GK * TS + 3 * TS <= BX_FLOATS, "Gram inputs fit the second pla
 // amplifies it: tests/fuzz/fuzz_parity.py found 1 window in 2 000 (d = 1, N = 255 ... 1000) at 1.05-1.3 of the 1e-3 bar where
 // single-precision LAPACK on the exact Gram matrix is at 5e-5.  For d >= 2 the expansion stays (d subtractions and FMAs per
 // entry on the VALU would cost more than the Gram phase has; no window of the sweeps needs it).
-template <typename T, bool BROWN, bool FAST, bool TRI = false, int NR = 2, bool DIFF1 = false>
+// MAT (fp64): 0 = the kernel is the exponential of the MFMA result; 1 / 2 = Matern 3/2 / 5/2: the log-amplitude addend of the augmented
+// points is 0 (k_prep), so the MFMA result is -r^2 / 2, and the VALU evaluates the radial function of r^2 = max(-2 e, 0) (one sqrt,
+// the same exp_nonpos, four more FMAs) and multiplies by the amplitude.  The auto-covariance diagonal is r^2 = 0 exactly.
+template <typename T, bool BROWN, bool FAST, bool TRI = false, int NR = 2, bool DIFF1 = false, int MAT = 0>
 __device__ __forceinline__ void gram_apply_tile(const FitArgs &p, typename Prec<T>::acc_t (&acc)[NCB][NR],
                                                 const T *__restrict__ xrT, const T *__restrict__ xcT,
                                                 const T *__restrict__ xraw, const T *__restrict__ craw,
@@ -1034,6 +1037,7 @@ __device__ __forceinline__ void gram_apply_tile(const FitArgs &p, typename Prec<
 #pragma unroll
     for (int s = 0; s < GK / 4; ++s) fb[j][s] = xrT[(4 * s + lq) * TS + rl[j]];
   static_assert(!DIFF1 || (!BROWN && sizeof(T) == 4), "the difference form is for the fp32 SE kernels");
+  static_assert(MAT == 0 || (!BROWN && !DIFF1 && sizeof(T) == 8), "the Matern kernels are fp64 cases of the inner-product form");
   T xrw[2] = {T(0), T(0)};
   if (BROWN || DIFF1) {
     xrw[0] = xraw[rl[0]];
@@ -1062,6 +1066,10 @@ __device__ __forceinline__ void gram_apply_tile(const FitArgs &p, typename Prec<
         if constexpr (DIFF1) {
           const T df = (xrw[j] - craw[cl]) * inv_ell;
           g = amp * exp_gen(T(-0.5) * df * df, ec);
+        } else if constexpr (MAT != 0) {
+          const bool same = !FAST && !extra && grow == gcol;
+          double unused;
+          g = amp * T(matern_radial<MAT == 2, false>(same ? 0.0 : -2.0 * (double)e[r], unused, [&](double x) { return exp_nonpos(x, ec); }));
         } else if (!BROWN) {
           g = CGP_DBG_ON(p, 128) ? e[r] : exp_gen(e[r], ec);
         } else {
@@ -1112,14 +1120,14 @@ __global__ void k_prep(FitArgs p, int batch, double *prep, int zero_info, int *w
   const int kid = p.kernel_id, d = p.d;
   for (int q = 0; q < MAXD; ++q) {
     double s = 0.0;
-    if (q < d) s = (kid == K_SE_ARD) ? 1.0 / th[1 + q] : 1.0 / th[1];
+    if (q < d) s = k_is_ard(kid) ? 1.0 / th[1 + q] : 1.0 / th[1];
     o[q] = s;
   }
   const bool brown = kid == K_RBF_BROWNIAN;
-  o[8] = brown ? 0.0 : log(th[0]);
+  o[8] = (brown || k_is_matern(kid)) ? 0.0 : log(th[0]);   // Matern: the MFMA result stays -r^2 / 2, the amplitude multiplies the radial function
   o[9] = th[0];
   o[10] = brown ? th[2] : 0.0;
-  const int nth = (kid == K_SE_ISO) ? 3 : (kid == K_SE_ARD ? d + 2 : 4);
+  const int nth = k_ntheta(kid, d);
   o[11] = th[nth - 1] + 1e-8 + (p.jitter ? p.jitter[b] : 0.0);
   for (int q = 12; q < PREP_N; ++q) o[q] = 0.0;
 }
@@ -1155,8 +1163,9 @@ __device__ __forceinline__ void gram_prefetch(const FitArgs &p, int b, int k, in
 }
 
 // Stages the augmented points of tile (rt, k) in LDS ([GK][128], component-major) and applies
-// acc <- G - acc.
-template <typename T, bool TRI = false, int NR = 2>
+// acc <- G - acc.  MAT: the launch is a Matern fit (fp64; 3/2 or 5/2 by kernel_id) -- a template case of every kernel that builds
+// Gram tiles, so that the squared-exponential / Brownian instantiations (MAT = false) are the code objects they were.
+template <typename T, bool TRI = false, int NR = 2, bool MAT = false>
 __device__ __forceinline__ void gram_apply(const FitArgs &p, typename Prec<T>::acc_t (&acc)[NCB][NR], T *__restrict__ smem,
                                            int b, int k, int rt, int tid, const GramPre<T> &g, PhaseClock *pc = nullptr,
                                            int slot = 0, int row0 = -1, bool live = true) {
@@ -1207,6 +1216,21 @@ __device__ __forceinline__ void gram_apply(const FitArgs &p, typename Prec<T>::a
       else gram_apply_tile<T, false, false, false, NR, true>(p, acc, xrT, xcT, xraw, craw, yc, extra, rowbase, colbase, amp, amp_b, diag_add, lane, wave, T(pr[0]));
       return;
     }
+  }
+  static_assert(!MAT || sizeof(T) == 8, "the Matern kernels are fp64 only");
+  if constexpr (MAT) {   // 3/2 or 5/2: uniform over the launch
+#define CGP_MATERN_TILE(FAST_, TRI_)                                                                                                  \
+  do {                                                                                                                                \
+    if (kid == K_MATERN52_ARD)                                                                                                        \
+      gram_apply_tile<T, false, FAST_, TRI_, NR, false, 2>(p, acc, xrT, xcT, xraw, craw, yc, extra, rowbase, colbase, amp, amp_b, diag_add, lane, wave); \
+    else                                                                                                                              \
+      gram_apply_tile<T, false, FAST_, TRI_, NR, false, 1>(p, acc, xrT, xcT, xraw, craw, yc, extra, rowbase, colbase, amp, amp_b, diag_add, lane, wave); \
+  } while (0)
+    if constexpr (TRI) CGP_MATERN_TILE(false, true);
+    else if (fast) CGP_MATERN_TILE(true, false);
+    else CGP_MATERN_TILE(false, false);
+#undef CGP_MATERN_TILE
+    return;
   }
   if constexpr (TRI) {  // diagonal tile: never "fast" (it carries the noise diagonal)
     if (brown) gram_apply_tile<T, true, false, true>(p, acc, xrT, xcT, xraw, craw, yc, extra, rowbase, colbase, amp, amp_b, diag_add, lane, wave, T(pr[0]));
@@ -1415,7 +1439,7 @@ __device__ __forceinline__ void acc_image(typename Prec<T>::acc_t (&acc)[NCB][2]
 // the trailing updates and the inverse on waves 1-3; in-kernel clocks, fp32, lone workgroup: 67 k ticks against the packed
 // form's 89 k, 76 k against 124 k with 64 fits on the chip) -- the packed form exists to fit TWO diagonal workgroups on a CU.
 template <typename T> constexpr int potf2_lds_elems() { return TS * LDP + 8 * DB * DB + 4 * DB * DB + 8; }
-template <typename T, int MODE, bool TRI, bool DEEP = sizeof(T) == 8, bool FAT = false>
+template <typename T, int MODE, bool TRI, bool DEEP = sizeof(T) == 8, bool FAT = false, bool MAT = false>
 __device__ __forceinline__ void diag_next(const FitArgs &p, typename Prec<T>::acc_t (&acc)[NCB][2], T *__restrict__ smem,
                                           T *__restrict__ Lw, int b, int kn, int tid, PhaseClock *pc = nullptr, bool img_ready = false) {
   using P = Prec<T>;
@@ -1457,7 +1481,7 @@ __device__ __forceinline__ void diag_next(const FitArgs &p, typename Prec<T>::ac
     else if (nchunk > 0) stage_first_chunk<T>(gR, (size_t)ld, gR, (size_t)ld, smem, tid);
     if (from_image) {
       if (!img_ready) acc_image<T, TRI, false>(acc, img, tid);   // (img_ready: the caller requested it before the fence, see panel_tile_body)
-    } else gram_apply<T, TRI>(p, acc, smem + (BXT ? BXT_FLOATS : CH2), b, kn, kn, tid, gp);   // BXT: behind plane buffer 0, over buffer 1
+    } else gram_apply<T, TRI, 2, MAT>(p, acc, smem + (BXT ? BXT_FLOATS : CH2), b, kn, kn, tid, gp);   // BXT: behind plane buffer 0, over buffer 1
   }
   if (pc) pc->lap(p, 344);  // finisher: fence + image / Gram tile (measurement build; slots 344.. = all steps summed)
   if constexpr (BXT) bx6_syrk_tri_loop(acc, bxt, nchunk, smem, tid);
@@ -1536,14 +1560,14 @@ __device__ __forceinline__ void diag_next(const FitArgs &p, typename Prec<T>::ac
 
 // k_diag_lean: the diagonal tile in the LDS budget of a panel workgroup (two per CU), so that with
 // two or more fits per CU one workgroup's factorisation latency runs under the other's MFMA loop.
-template <typename T, bool FAT = false>
+template <typename T, bool FAT = false, bool MAT = false>
 __global__ __launch_bounds__(256, 2) void k_diag_lean(FitArgs p, int k) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T *smem = reinterpret_cast<T *>(smem_raw);
   const int b = blockIdx.x;
   T *Lw = reinterpret_cast<T *>(p.Lw) + (size_t)b * p.lw_stride;
   typename Prec<T>::acc_t acc[NCB][2];
-  diag_next<T, DIAG_FULL, kTriDiag, sizeof(T) == 8 || FAT, FAT>(p, acc, smem, Lw, b, k, threadIdx.x);
+  diag_next<T, DIAG_FULL, kTriDiag, sizeof(T) == 8 || FAT, FAT, MAT>(p, acc, smem, Lw, b, k, threadIdx.x);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1746,7 +1770,7 @@ __device__ __forceinline__ void load_tile(typename Prec<T>::acc_t (&acc)[NCB][2]
 // Kind C of k_panel<T, true, DEEP, MID> in launch k: tile (k + 2, k + 1) -- the NEXT launch's kind-A tile -- with the
 // block columns < k (final since the previous launch): acc = -G + sum_{j<k} L(k+2, j) L(k+1, j)^T, left as a raw
 // register image in p.pimg[(k + 1) & 1].  Same arithmetic, in the same order, as the one-workgroup form.
-template <typename T, bool DEEP>
+template <typename T, bool DEEP, bool MAT = false>
 __device__ __forceinline__ void panel_partial(const FitArgs &p, typename Prec<T>::acc_t (&acc)[NCB][2], T *__restrict__ smem, int b,
                                               int k, int tid) {
   constexpr int CH2 = 2 * KT * LDST;
@@ -1763,11 +1787,11 @@ __device__ __forceinline__ void panel_partial(const FitArgs &p, typename Prec<T>
     T ms[4] = {T(0), T(0), T(0), T(0)};
     rdirect_prologue<T, R>(rf, gR, (size_t)ld, gC, (size_t)ld, nchunk, smem, tid);
     // the Gram inputs are staged in the ring slots the prologue leaves free (first written after iteration 0's barrier)
-    gram_apply<T>(p, acc, smem + (R - 2) * KT * LDST, b, kc, rt, tid, gp);
+    gram_apply<T, false, 2, MAT>(p, acc, smem + (R - 2) * KT * LDST, b, kc, rt, tid, gp);
     mfma_rowpanel_loop_rdirect<T, R>(acc, rf, gR, (size_t)ld, gC, (size_t)ld, nchunk, smem, tid, zs, ms);
   } else {
     if (nchunk > 0) stage_first_chunk<T>(gR, (size_t)ld, gC, (size_t)ld, smem, tid);
-    gram_apply<T>(p, acc, smem + CH2, b, kc, rt, tid, gp);
+    gram_apply<T, false, 2, MAT>(p, acc, smem + CH2, b, kc, rt, tid, gp);
     mfma_rowpanel_loop<T, true>(acc, gR, (size_t)ld, gC, (size_t)ld, nchunk, smem, tid);
   }
   acc_image<T, false, true>(acc, reinterpret_cast<T *>(p.pimg) + ((size_t)b * img_slots(p) + kc % img_slots(p)) * DPART, tid);
@@ -1780,7 +1804,7 @@ template <typename T, bool MID> constexpr bool mid_fat() { return MID && sizeof(
 // One tile of block step k: L(rt, k) = (G(rt,k) - sum_{c_first*16 <= col < 128 k} L(rt,:) L(k,:)^T [+ image]) W_k^T, stored; then, kind A
 // (finish_next), the next diagonal tile.  The body of k_panel after its role decode -- also what a tile task of the
 // one-launch schedule (k_sched) runs.
-template <typename T, bool DIAGNEXT, bool DEEP, bool MID>
+template <typename T, bool DIAGNEXT, bool DEEP, bool MID, bool MAT = false>
 __device__ __forceinline__ void panel_tile_body(const FitArgs &p, int k, int b, int rt, int c_first, bool finish_next, bool from_image,
                                                 T *smem, int tid) {
   using P = Prec<T>;
@@ -1827,7 +1851,7 @@ __device__ __forceinline__ void panel_tile_body(const FitArgs &p, int k, int b, 
       if (!(MID && from_image)) gram_prefetch<T>(p, b, k, rt, tid, gp);
       rdirect_prologue<T, R>(rf, gR, (size_t)ld, gC, (size_t)ld, nchunk, smem, tid);
       if (MID && from_image) acc_image<T, false, false>(acc, const_cast<T *>(pimg), tid);
-      else gram_apply<T>(p, acc, smem + (R - 2) * KT * LDST, b, k, rt, tid, gp, &pc, ps + 6);   // ring slots the prologue leaves free
+      else gram_apply<T, false, 2, MAT>(p, acc, smem + (R - 2) * KT * LDST, b, k, rt, tid, gp, &pc, ps + 6);   // ring slots the prologue leaves free
     }
     pc.lap(p, ps + 0);
     mfma_rowpanel_loop_rdirect<T, R>(acc, rf, gR, (size_t)ld, gC, (size_t)ld, nchunk, smem, tid, zs, ms);
@@ -1856,7 +1880,7 @@ __device__ __forceinline__ void panel_tile_body(const FitArgs &p, int k, int b, 
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[cb][j][r] = gp.v[0];
       } else if (MID && from_image) acc_image<T, false, false>(acc, const_cast<T *>(pimg), tid);
-      else gram_apply<T>(p, acc, smem + GRAM_OFF, b, k, rt, tid, gp, &pc, ps + 6, -1, live);
+      else gram_apply<T, false, 2, MAT>(p, acc, smem + GRAM_OFF, b, k, rt, tid, gp, &pc, ps + 6, -1, live);
     }
     pc.lap(p, ps + 0);
     if constexpr (PL) bx6p_loop(acc, bps, nchunk, smem, tid, accm ? zs : nullptr, ms, live, gR, (size_t)ld);
@@ -1918,7 +1942,7 @@ __device__ __forceinline__ void panel_tile_body(const FitArgs &p, int k, int b, 
           img_ready = true;
         }
       }
-      diag_next<T, DIAG_FINISH, kTriDiag, DEEP, mid_fat<T, MID>()>(p, acc, smem, Lw, b, k + 1, tid, &pc, img_ready);
+      diag_next<T, DIAG_FINISH, kTriDiag, DEEP, mid_fat<T, MID>(), MAT>(p, acc, smem, Lw, b, k + 1, tid, &pc, img_ready);
     }
   }
 }
@@ -1947,7 +1971,7 @@ __device__ __forceinline__ void panel_tile_body(const FitArgs &p, int k, int b, 
                              // spill) the bf16-plane build measured 5 % slower (121.8 k against 127.9 k fits/s)
 #endif
 constexpr int F32_FULL_OCC = CGP_F32_FULL_OCC;
-template <typename T, bool DIAGNEXT = false, bool DEEP = sizeof(T) == 8, bool MID = false>
+template <typename T, bool DIAGNEXT = false, bool DEEP = sizeof(T) == 8, bool MID = false, bool MAT = false>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? (DEEP ? ((MID && (CGP_MID_RING > 4 || CGP_F32_BF16X6)) ? 2 : 3) : F32_FULL_OCC) : 2) void k_panel(FitArgs p, int k) {
   using P = Prec<T>;
   using acc_t = typename P::acc_t;
@@ -1994,11 +2018,11 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (DEEP ? ((MID && (CGP_MID_RIN
     } else if (io < nB) {
       b = io;
       T *LwB = reinterpret_cast<T *>(p.Lw) + (size_t)b * p.lw_stride;
-      diag_next<T, DIAG_PARTIAL, kTriDiag, DEEP>(p, acc, smem, LwB, b, k + 2, tid);
+      diag_next<T, DIAG_PARTIAL, kTriDiag, DEEP, false, MAT>(p, acc, smem, LwB, b, k + 2, tid);
       sc.leave(p, k, tid);
       return;
     } else if (MID && io < nB + nC) {
-      panel_partial<T, DEEP>(p, acc, smem, io - nB, k, tid);  // kind C (a path of its own, as kind B: the main path keeps its registers)
+      panel_partial<T, DEEP, MAT>(p, acc, smem, io - nB, k, tid);  // kind C (a path of its own, as kind B: the main path keeps its registers)
       sc.leave(p, k, tid);
       return;
     } else {
@@ -2019,7 +2043,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (DEEP ? ((MID && (CGP_MID_RIN
     tile_fit_of_block(bt, b);
     rt = row_tile_of(bt + p.tile_off, k + 1, p.NT, p.rows_from_extra);
   }
-  panel_tile_body<T, DIAGNEXT, DEEP, MID>(p, k, b, rt, c_first, finish_next, from_image, smem, tid);
+  panel_tile_body<T, DIAGNEXT, DEEP, MID, MAT>(p, k, b, rt, c_first, finish_next, from_image, smem, tid);
   sc.leave(p, k, tid);
 }
 
@@ -2078,7 +2102,7 @@ __device__ __forceinline__ void r16_step(typename Prec<T>::acc_t (&acc)[NCB][1],
   }
 }
 
-template <typename T>
+template <typename T, bool MAT = false>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : 2) void k_rows64(FitArgs p, int k) {
   using P = Prec<T>;
   using acc_t = typename P::acc_t;
@@ -2111,7 +2135,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 4 : 2) void k_rows64(FitArgs 
       cpanel_stage<T>(gC, (size_t)ld, 1, smem + CH, lane, wave);
       r16_load<T, 1>(rf, gRl, (size_t)ld, 1, lq);
     }
-    gram_apply<T, false, 1>(p, acc, smem + 2 * CH, b, k, p.NT, tid, gp, nullptr, 0, row0);
+    gram_apply<T, false, 1, MAT>(p, acc, smem + 2 * CH, b, k, p.NT, tid, gp, nullptr, 0, row0);
   }
   if (nchunk > 0) {
     int c = 0;
@@ -2315,7 +2339,7 @@ __global__ __launch_bounds__(256, 2) void k_sched(FitArgs p, SchedArgs q) {
 // --------------------------------------------------------------------------------------------------
 // k_diag: the diagonal tile of block step k, updated, factored and inverted by one workgroup.
 // --------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool MAT = false>
 __global__ __launch_bounds__(256) void k_diag(FitArgs p, int k) {
   using P = Prec<T>;
   using acc_t = typename P::acc_t;
@@ -2344,7 +2368,7 @@ __global__ __launch_bounds__(256) void k_diag(FitArgs p, int k) {
       if (nchunk > 0) stage_chunk_tri<T>(gR, (size_t)ld, 0, smem + tri_buf(0), tid);
       if (nchunk > 1) stage_chunk_tri<T>(gR, (size_t)ld, 1, smem + tri_buf(1), tid);
     } else if (nchunk > 0) stage_first_chunk<T>(gR, (size_t)ld, gR, (size_t)ld, smem, tid);
-    gram_apply<T, TRI>(p, acc, smem + CH2, b, k, k, tid, gp);
+    gram_apply<T, TRI, 2, MAT>(p, acc, smem + CH2, b, k, k, tid, gp);
   }
   if constexpr (TRI) mfma_syrk_tri_loop<T>(acc, gR, (size_t)ld, nchunk, smem, tid);
   else mfma_rowpanel_loop<T, true>(acc, gR, (size_t)ld, gR, (size_t)ld, nchunk, smem, tid);
@@ -2422,7 +2446,7 @@ __host__ __device__ __forceinline__ constexpr int lat_images(int kn) {  // image
   return kn >= 2 ? ((kn - 1) * (TS / KT) + LAT_IMG_CHUNKS - 1) / LAT_IMG_CHUNKS : 0;
 }
 
-template <typename T>
+template <typename T, bool MAT = false>
 __global__ __launch_bounds__(256) void k_tile_sk(FitArgs p, SplitArgs q, int k) {
   using P = Prec<T>;
   using acc_t = typename P::acc_t;
@@ -2462,7 +2486,7 @@ __global__ __launch_bounds__(256) void k_tile_sk(FitArgs p, SplitArgs q, int k) 
       if (s == 0) gram_prefetch<T>(p, b, kn, kn, tid, gp);
       stage_chunk_tri<T>(gR, (size_t)ld, 0, smem + tri_buf(0), tid);
       if (sizeof(T) == 8 && nchunk > 1) stage_chunk_tri<T>(gR, (size_t)ld, 1, smem + tri_buf(1), tid);
-      if (s == 0) gram_apply<T, true>(p, acc, smem + CH2, b, kn, kn, tid, gp);
+      if (s == 0) gram_apply<T, true, 2, MAT>(p, acc, smem + CH2, b, kn, kn, tid, gp);
       else {
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) acc[cb][0] = acc[cb][1] = acc_t{0, 0, 0, 0};
@@ -2514,7 +2538,7 @@ __global__ __launch_bounds__(256) void k_tile_sk(FitArgs p, SplitArgs q, int k) 
       if (nimg == 0) gram_prefetch<T>(p, b, k, k, tid, gp);
       if (nchunk > 0) stage_chunk_tri<T>(gR, (size_t)ld, 0, smem + tri_buf(0), tid);
       if (sizeof(T) == 8 && nchunk > 1) stage_chunk_tri<T>(gR, (size_t)ld, 1, smem + tri_buf(1), tid);
-      if (nimg == 0) gram_apply<T, true>(p, acc, smem + CH2, b, k, k, tid, gp);
+      if (nimg == 0) gram_apply<T, true, 2, MAT>(p, acc, smem + CH2, b, k, k, tid, gp);
       else {
         acc_image<T, true, false>(acc, imgs + (size_t)(k & 1) * LAT_IMG_MAX * DPART, tid);  // already the fixed-order sum
       }
@@ -2554,7 +2578,7 @@ __global__ __launch_bounds__(256) void k_tile_sk(FitArgs p, SplitArgs q, int k) 
   if (sp == 0) {
     GramPre<T> gp;
     gram_prefetch<T>(p, b, k, rt, tid, gp);
-    gram_apply<T>(p, acc, smem + CH2, b, k, rt, tid, gp);
+    gram_apply<T, false, 2, MAT>(p, acc, smem + CH2, b, k, rt, tid, gp);
     __syncthreads();
   } else {
 #pragma unroll
@@ -2724,9 +2748,12 @@ __global__ __launch_bounds__(64 * TRMM_WAVES) void k_trmm_sk(FitArgs p, int k) {
 //     S_amp  = sum w_ij K_ij        S_ell[q] = sum w_ij K_ij d_q^2        S_noise = sum_i w_ii
 // with w = alpha_i alpha_j - Ky^-1_ij, d_q the length-scaled coordinate difference; off-diagonal
 // tiles count twice.  Wt[e][c] = 0 for c < e, so the inner dimension starts at column block ti.
+// MAT = 1 / 2 (fp64): Matern 3/2 / 5/2, a kernel of its own so that the squared-exponential one is the code it was.  S_ell[q] then
+// carries -2 dk/dr^2 in K_ij's place (matern_radial), and the host's SE_ARD formulas turn the sums into the gradient unchanged.
 // --------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, int MAT = 0>
 __global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
+  static_assert(MAT == 0 || sizeof(T) == 8, "the Matern kernels are fp64 only");
   using P = Prec<T>;
   using acc_t = typename P::acc_t;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -2790,6 +2817,7 @@ __global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
         if (grow < N && gcol < N) {
           const T w = ar[rl] * ac[cl] - kinv;
           T kv, dq2[MAXD];
+          T kg = T(0);   // what multiplies dq2 in the length-scale sums: k itself, Matern: -2 dk/dr^2
           if (!brown) {
             T d2 = 0;
 #pragma unroll
@@ -2798,7 +2826,14 @@ __global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
               dq2[q] = df * df;
               d2 += dq2[q];
             }
-            kv = amp * P::exp_(T(-0.5) * d2);
+            if constexpr (MAT != 0) {
+              double gm;
+              kv = amp * matern_radial<MAT == 2, true>((double)d2, gm, [](double x) { return exp(x); });
+              kg = amp * gm;
+            } else {
+              kv = amp * P::exp_(T(-0.5) * d2);
+              kg = kv;
+            }
           } else {
             const T x = xr[rl], xp = xc[cl];
             T r2 = (grow == gcol) ? T(0) : (T(-2) * x * xp + (x * x + xp * xp));
@@ -2811,11 +2846,13 @@ __global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
 #pragma unroll
             for (int q = 0; q < MAXD; ++q) dq2[q] = T(0);
             dq2[0] = rr * rr;
+            kg = kv;
           }
           const double wk = (double)w * (double)kv;
           s_amp += wk;
+          const double wg = MAT != 0 ? (double)w * (double)kg : wk;
 #pragma unroll
-          for (int q = 0; q < MAXD; ++q) s_ell[q] += wk * (double)dq2[q];
+          for (int q = 0; q < MAXD; ++q) s_ell[q] += wg * (double)dq2[q];
           if (grow == gcol) s_noise += (double)w;
         }
       }

@@ -57,7 +57,10 @@ struct WindowArgs {
   int *info_out;    // [nwin] or nullptr: a copy of state[2] (first failing tick) where the host can read it without a copy command
 };
 
-// Covariance of two points (raw coordinates), direct formulas.
+// Covariance of two points (raw coordinates), direct formulas.  MAT = false: the caller is an instantiation that never sees a
+// Matern window (k_window_pairs, whose register allocation a run-time case would move; the single-tick and multi-tick kernels keep
+// their figures with the run-time case and use the default).
+template <bool MAT = true>
 __device__ __forceinline__ double win_cov(int kid, int d, const double *pr, const double *a, int as, const double *b,
                                           int bs, bool same) {
   if (kid != K_RBF_BROWNIAN) {
@@ -65,6 +68,10 @@ __device__ __forceinline__ double win_cov(int kid, int d, const double *pr, cons
     for (int q = 0; q < d; ++q) {
       const double df = (a[q * as] - b[q * bs]) * pr[q];
       d2 += df * df;
+    }
+    if (MAT && k_is_matern(kid)) {   // (uniform over the launch) the radial function of the same scaled squared distance
+      double unused;
+      return pr[9] * matern_radial_rt<false>(kid, d2, unused);
     }
     return pr[9] * exp(-0.5 * d2);
   }
@@ -124,7 +131,7 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? WIN_OCC : 1) void k_window_ticks(
   int *st = p.state + w * 4;
   const double *pr = p.prep + (size_t)w * PREP_N;
   const double *th = p.theta + (size_t)w * MAX_THETA;
-  const int nth = (kid == K_SE_ISO) ? 3 : (kid == K_SE_ARD ? d + 2 : 4);
+  const int nth = k_ntheta(kid, d);
   const double noise = th[nth - 1];
   int o = st[0], n = st[1], bad = st[2];
 
@@ -483,7 +490,7 @@ __global__ __launch_bounds__(NTH, NTH == 256 ? WIN_OCC : 1) void k_window_ticks(
 // the workgroup; DPP row_newbcast is row-local, nothing in the chain crosses rows), so one pass of the chains advances WPW
 // windows, and waves 1-3 sweep the rows of all of them.  Windows of a context advance in lock-step: origin, size and panel
 // count are workgroup-uniform.
-template <int WPW>
+template <int WPW, bool MAT = false>   // MAT: the windows hold a Matern kernel (a case of its own: see win_cov)
 __global__ __launch_bounds__(256, WIN_OCC) void k_window_pairs(WindowArgs p) {
   static_assert(WPW == 1 || WPW == 2 || WPW == 4, "rows of wave 0 per window: 4, 2 or 1");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -502,7 +509,7 @@ __global__ __launch_bounds__(256, WIN_OCC) void k_window_pairs(WindowArgs p) {
   const int w0 = blockIdx.x * WPW;
   const size_t LWs = (size_t)CAP * CAP;
   double *Lg = p.L + (size_t)w0 * LWs;
-  const int nth = (kid == K_SE_ISO) ? 3 : (kid == K_SE_ARD ? d + 2 : 4);
+  const int nth = k_ntheta(kid, d);
   // wave 0: this lane's window
   double *vv1 = blk(wl0), *kk1 = vv1 + NS, *ll1 = kk1 + NS, *vv2 = ll1 + NS, *kk2 = vv2 + NS, *ll2 = kk2 + NS;
   double *cs1 = ll2 + NS, *cs2 = cs1 + 8 * WPB, *xn = cs2 + 8 * WPB, *red = xn + 2 * MAXD;
@@ -550,10 +557,10 @@ __global__ __launch_bounds__(256, WIN_OCC) void k_window_pairs(WindowArgs p) {
       const double *xww = p.xw + (size_t)(w0 + wl) * d * CAP;
       if (rr < m) {
         b[rr] = Lg[wl * LWs + (size_t)o * CAP + o1 + rr];                                      // vv1
-        b[NS + rr] = win_cov(kid, d, prw, xww + o1 + rr, CAP, xnw, 1, false);                  // kk1
-        b[4 * NS + rr] = win_cov(kid, d, prw, xww + o1 + rr, CAP, xnw + MAXD, 1, false);       // kk2
+        b[NS + rr] = win_cov<MAT>(kid, d, prw, xww + o1 + rr, CAP, xnw, 1, false);                  // kk1
+        b[4 * NS + rr] = win_cov<MAT>(kid, d, prw, xww + o1 + rr, CAP, xnw + MAXD, 1, false);       // kk2
       } else {
-        b[4 * NS + m] = win_cov(kid, d, prw, xnw, 1, xnw + MAXD, 1, false);   // kk2[m]: the two incoming points
+        b[4 * NS + m] = win_cov<MAT>(kid, d, prw, xnw, 1, xnw + MAXD, 1, false);   // kk2[m]: the two incoming points
         b[m] = 0.0;            // vv1[m]
         b[NS + m] = 0.0;       // kk1[m]
         b[2 * NS + m] = 0.0;   // ll1[m]
@@ -979,7 +986,7 @@ __global__ __launch_bounds__(256, WIN_OCC) void k_window_multi(WindowArgs p) {
   double *Lg = p.L + (size_t)w * CAP * CAP;
   double *z = p.z + (size_t)w * CAP, *xw = p.xw + (size_t)w * d * CAP, *yw = p.yw + (size_t)w * CAP;
   const double *pr = p.prep + (size_t)w * PREP_N;
-  const int nth = (kid == K_SE_ISO) ? 3 : (kid == K_SE_ARD ? d + 2 : 4);
+  const int nth = k_ntheta(kid, d);
   const double noise = p.theta[(size_t)w * MAX_THETA + nth - 1];
   int o = p.state[w * 4], bad = p.state[w * 4 + 2];
   // only correct for full windows with room for TK more rows (the host cuts a push from its mirror; see k_window_pairs)

@@ -68,8 +68,10 @@ struct WaCov {
   double pr[MAXD], amp, ampb;
   int kid, d;
   __device__ __forceinline__ double kss(double x0) const { return kid == K_RBF_BROWNIAN ? amp * ampb * fabs(x0) : amp; }
-  // k(a, b) for a != b; dq2[q] = the squared length-scaled differences (Brownian: dq2[0] = r^2 / ell^2) for the gradient
-  template <bool WITH_DQ> __device__ __forceinline__ double eval(const double (&xa)[MAXD], const double (&xb)[MAXD], double (&dq2)[MAXD]) const {
+  // k(a, b) for a != b; dq2[q] = the squared length-scaled differences (Brownian: dq2[0] = r^2 / ell^2) for the gradient.
+  // Matern: dq2 comes back times (-2 dk/dr^2) / k = 3 / (1 + s) resp. (5/3) (1 + s) / (1 + s + s^2 / 3) -- a quotient whose
+  // denominator is >= 1 -- so that the caller's sums of w k dq2 are the length-scale sums of that kernel as they stand.
+  template <bool WITH_DQ, bool MAT = true> __device__ __forceinline__ double eval(const double (&xa)[MAXD], const double (&xb)[MAXD], double (&dq2)[MAXD]) const {
     if (kid != K_RBF_BROWNIAN) {
       double d2 = 0;
 #pragma unroll
@@ -81,6 +83,17 @@ struct WaCov {
         } else if (WITH_DQ) {
           dq2[q] = 0.0;
         }
+      }
+      if (MAT && k_is_matern(kid)) {   // MAT = false: an instantiation that never sees a Matern window (k_window_refactor)
+        double unused;
+        const double k1 = matern_radial_rt<false>(kid, d2, unused);
+        if (WITH_DQ) {
+          const double s = sqrt((kid == K_MATERN52_ARD ? 5.0 : 3.0) * d2);
+          const double ratio = kid == K_MATERN52_ARD ? (5.0 / 3.0) * (1.0 + s) / __builtin_fma(5.0 / 3.0, d2, 1.0 + s) : 3.0 / (1.0 + s);
+#pragma unroll
+          for (int q = 0; q < MAXD; ++q) dq2[q] *= ratio;
+        }
+        return amp * k1;
       }
       return amp * exp(-0.5 * d2);
     }
@@ -99,10 +112,10 @@ struct WaCov {
   }
 };
 
-__device__ __forceinline__ int wa_ntheta(int kid, int d) { return (kid == K_SE_ISO) ? 3 : (kid == K_SE_ARD ? d + 2 : 4); }
+__device__ __forceinline__ int wa_ntheta(int kid, int d) { return k_ntheta(kid, d); }
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <int TPW>
+template <int TPW, bool MAT = false>   // MAT: the windows hold a Matern kernel (an instantiation of its own)
 __global__ __launch_bounds__(WA_THREADS) void k_window_refactor(AdaptArgs p) {
   typedef double d4 __attribute__((ext_vector_type(4)));
   __shared__ double tile[WPB * WPB];   // the diagonal tile, [c * 16 + r]
@@ -123,13 +136,13 @@ __global__ __launch_bounds__(WA_THREADS) void k_window_refactor(AdaptArgs p) {
   cv.kid = kid;
   cv.d = d;
 #pragma unroll
-  for (int q = 0; q < MAXD; ++q) cv.pr[q] = q < d ? 1.0 / ((kid == K_SE_ARD) ? tn[1 + q] : tn[1]) : 0.0;
+  for (int q = 0; q < MAXD; ++q) cv.pr[q] = q < d ? 1.0 / (k_is_ard(kid) ? tn[1 + q] : tn[1]) : 0.0;
   cv.amp = tn[0];
   cv.ampb = (kid == K_RBF_BROWNIAN) ? tn[2] : 0.0;
   const double noise = tn[nth - 1];
   if (tid < PREP_N) {
     double v = 0.0;
-    if (tid < d) v = 1.0 / ((kid == K_SE_ARD) ? tn[1 + tid] : tn[1]);
+    if (tid < d) v = 1.0 / (k_is_ard(kid) ? tn[1 + tid] : tn[1]);
     if (tid == 9) v = tn[0];
     if (tid == 10) v = (kid == K_RBF_BROWNIAN) ? tn[2] : 0.0;
     p.prep[(size_t)w * PREP_N + tid] = v;
@@ -178,7 +191,7 @@ __global__ __launch_bounds__(WA_THREADS) void k_window_refactor(AdaptArgs p) {
           for (int r = 0; r < 4; ++r) {
             const int gj = J0 + lq + 4 * r;
             double dq[MAXD], v;
-            if (gi < n && gj < n) v = (gi == gj) ? cv.kss(xi[0]) + noise + 1e-8 : cv.eval<false>(xj[r], xi, dq);
+            if (gi < n && gj < n) v = (gi == gj) ? cv.kss(xi[0]) + noise + 1e-8 : cv.template eval<false, MAT>(xj[r], xi, dq);
             else v = (gi == gj) ? 1.0 : 0.0;   // rows past the window: identity
             acc[t][r] = v;
           }
@@ -551,7 +564,7 @@ __global__ __launch_bounds__(64) void k_window_grad_finish(AdaptArgs p) {
     for (int q = 0; q < d; ++q) se += s[1 + q];
     g[1] = -0.5 * se / th[1];
     g[2] = -0.5 * s[9];
-  } else if (kid == K_SE_ARD) {
+  } else if (k_is_ard(kid)) {
     for (int q = 0; q < d; ++q) g[1 + q] = -0.5 * s[1 + q] / th[1 + q];
     g[d + 1] = -0.5 * s[9];
   } else {

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64) void k_window_diag_inv(ForecastArgs p) {
 // NCT column tiles per workgroup (the waves of a tile split the sum over J WF_WAVES / NCT ways); VW = columns of a tile in use
 // KEEP: every finished V(I) block is also stored for the joint forecast (cgp_window_joint.hpp); the forms cgp_window_predict
 // launches are the KEEP = false ones
-template <int NCT, int VW, bool KEEP = false>
+template <int NCT, int VW, bool KEEP = false, bool MAT = false>   // MAT: the windows hold a Matern kernel (an instantiation of its own)
 __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs p) {
   static_assert((NCT == 1 || NCT == 2) && (VW == 16 || VW == 8), "forms of the forecast kernel");
   constexpr int SPLIT = WF_WAVES / NCT, MC = NCT * VW;
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
   const int o = p.state[w * 4], n = p.state[w * 4 + 1], bad = p.state[w * 4 + 2];
   const double *pr = p.prep + (size_t)w * PREP_N;
   const double *th = p.theta + (size_t)w * MAX_THETA;
-  const int nth = (kid == K_SE_ISO) ? 3 : (kid == K_SE_ARD ? d + 2 : 4);
+  const int nth = k_ntheta(kid, d);
   const double noise = p.include_noise ? th[nth - 1] : 0.0;
   // this lane's test point (solver waves: column l15 of tile ct)
   const int col = ch * MC + ct * VW + l15;
@@ -177,6 +177,10 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
           const double df = (xa[q] - xq[q]) * prr[q];
           d2 += df * df;
         }
+      if constexpr (MAT) {
+        double unused;
+        return amp * matern_radial_rt<false>(kid, d2, unused);
+      }
       return amp * exp(-0.5 * d2);
     }
     const double x = xa[0], xp = xq[0];

@@ -9,11 +9,20 @@ import os
 import numpy as np
 
 KERNEL_SE_ISO, KERNEL_SE_ARD, KERNEL_RBF_BROWNIAN = 0, 1, 2
+KERNEL_MATERN32_ARD, KERNEL_MATERN52_ARD = 3, 4   # theta layout of SE_ARD; fp64 contexts only (include/corenav_gp.h)
 F64, F32 = 0, 1
 MAX_D = 8
 MAX_THETA = MAX_D + 2
 PROF_KERNELS = 5
 PROF_NAMES = ("update", "potf2", "trmm", "finalize", "alpha")
+
+
+def ntheta(kernel_id, d):
+    """Entries of theta for `kernel_id` at d input dimensions (the layouts of include/corenav_gp.h)."""
+    if kernel_id == KERNEL_SE_ISO:
+        return 3
+    return 4 if kernel_id == KERNEL_RBF_BROWNIAN else d + 2
+
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CGP_LIB selects another build of the same ABI for measurements (the -DCGP_AB -DCGP_ABLATION library
@@ -323,7 +332,7 @@ class Context:
         if theta.ndim == 1:
             theta = np.tile(theta, (nwin, 1))
         self._win = (nwin, d)
-        self._win_nth = 3 if kernel_id == KERNEL_SE_ISO else (d + 2 if kernel_id == KERNEL_SE_ARD else 4)
+        self._win_nth = ntheta(kernel_id, d)
         self._chk(self.lib.cgp_window_init(self.h, nwin, N, d, kernel_id, _p(theta), theta.shape[1]))
 
     def window_push(self, xs, ys, include_noise=True):

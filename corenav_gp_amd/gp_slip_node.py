@@ -4,6 +4,8 @@ data flow -- the GPy calls are replaced by the HIP engine through the C ABI.
   reference                                      here
   ---------------------------------------------  ------------------------------------------------
   GPy.kern.RBF(1) * GPy.kern.Brownian(1)   :31   KERNEL_RBF_BROWNIAN + theta
+  GPy.kern.Matern32(1) / Matern52(1)    :32-34   GpSlipNode(kernel_id=engine.KERNEL_MATERN32_ARD | KERNEL_MATERN52_ARD):
+                                                 theta = [variance, lengthscale, noise variance]
   GPy.models.GPRegression(...)             :35   engine.Context.fit (cgp_fit)
   m.optimize()                             :36   engine.Context.optimize (cgp_optimize): L-BFGS on the
                                                  Logexp-transformed parameters, device gradients
@@ -45,8 +47,13 @@ class GP_Output:                                         # core_navigation/msg/G
 
 
 class GpSlipNode:
-    def __init__(self, theta=None, device=0, publisher=None, optimize=True):
+    def __init__(self, theta=None, device=0, publisher=None, optimize=True, kernel_id=engine.KERNEL_RBF_BROWNIAN):
         self.optimize = optimize
+        self.kernel_id = kernel_id          # the one-line kernel choice of gp_slip_node.py:31
+        if theta is None and kernel_id != engine.KERNEL_RBF_BROWNIAN:
+            if not optimize:
+                raise ValueError("a fixed theta is needed for this kernel (DEFAULT_THETA is the RBF x Brownian one)")
+            theta = (1.0,) * engine.ntheta(kernel_id, 1)    # GPy's start values
         if theta is None:
             theta = GPY_START_THETA if optimize else DEFAULT_THETA
         self.theta = np.asarray(theta, dtype=np.float64)
@@ -58,9 +65,10 @@ class GpSlipNode:
         """gp_slip_node.py:16-63.  Returns the GP_Output it publishes."""
         if self.optimize:   # gp_slip_node.py:36: a fresh model per window, optimised from the start values
             mean, sigma, self.last_theta = self.ctx.slip_node_callback_opt(data.time_array, data.slip_array,
-                                                                           self.theta, max_evals=MAX_EVALS)
+                                                                           self.theta, kernel_id=self.kernel_id,
+                                                                           max_evals=MAX_EVALS)
         else:
-            mean, sigma = self.ctx.slip_node_callback(data.time_array, data.slip_array, self.theta)
+            mean, sigma = self.ctx.slip_node_callback(data.time_array, data.slip_array, self.theta, kernel_id=self.kernel_id)
         msg_out = GP_Output()
         msg_out.mean = mean
         msg_out.sigma = sigma

@@ -28,8 +28,22 @@ typedef struct cgp_ctx cgp_ctx;
  *   SE_ISO        [sigma_f^2, ell, sigma_n^2]
  *   SE_ARD        [sigma_f^2, ell_1 .. ell_d, sigma_n^2]
  *   RBF_BROWNIAN  [sigma_rbf^2, ell, sigma_brownian^2, sigma_n^2]   d == 1
- * RBF_BROWNIAN is `GPy.kern.RBF(1) * GPy.kern.Brownian(1)` of gp_slip_node.py:31. */
-enum { CGP_KERNEL_SE_ISO = 0, CGP_KERNEL_SE_ARD = 1, CGP_KERNEL_RBF_BROWNIAN = 2 };
+ *   MATERN32_ARD, MATERN52_ARD   the layout of SE_ARD: [sigma_f^2, ell_1 .. ell_d, sigma_n^2]
+ * RBF_BROWNIAN is `GPy.kern.RBF(1) * GPy.kern.Brownian(1)` of gp_slip_node.py:31.  The Matern pair (ids appended: no existing value
+ * moved, the ABI revision stays 3; a library built before them answers CGP_EINVAL) is what that one line becomes with the
+ * alternatives listed under it, `GPy.kern.Matern32(1)` / `GPy.kern.Matern52(1)` (gp_slip_node.py:32-34) at d = 1, with one
+ * length-scale per input dimension beyond:
+ *   r^2 = sum_q ((x_q - x'_q) / ell_q)^2
+ *   MATERN32: k = sigma_f^2 (1 + sqrt(3) r) exp(-sqrt(3) r)
+ *   MATERN52: k = sigma_f^2 (1 + sqrt(5) r + 5/3 r^2) exp(-sqrt(5) r)            k(x, x) = sigma_f^2 for both
+ * They are CGP_F64 kernels: every entry point of a CGP_F32 context returns CGP_EINVAL for them before anything is enqueued (the
+ * context stays usable).  In fp64 contexts every entry point takes them, the sliding windows included.  The one-launch
+ * short-window kernels (below) hold the squared-exponential and Brownian forms only: a Matern call of ANY length runs the tiled
+ * schedules, and its optimisation the host L-BFGS over device gradients -- the route windows of more than 160 samples take. */
+enum {
+  CGP_KERNEL_SE_ISO = 0, CGP_KERNEL_SE_ARD = 1, CGP_KERNEL_RBF_BROWNIAN = 2, CGP_KERNEL_MATERN32_ARD = 3,
+  CGP_KERNEL_MATERN52_ARD = 4
+};
 enum { CGP_F64 = 0, CGP_F32 = 1 };
 enum {
   CGP_OK = 0, CGP_EINVAL = -1, CGP_ENOMEM = -2, CGP_EHIP = -3, CGP_ESTATE = -4, CGP_ENODEVICE = -5,
@@ -60,6 +74,7 @@ enum {
  *     fp64 path, as in the reference: in CGP_F32 its mean is refined like any d = 1 window, its variance is held to
  *     max(3e-3, 30 x that LAPACK error) only (its banded factor meets the bf16 matrix cores' truncating sums: a bias of
  *     +1.6e-3 +- 5e-4 at a thousand samples, one sweep window at 3.29e-3).  Use CGP_F64 for that kernel.
+ *   - the Matern kernels are not part of the fp32 contract at all: CGP_EINVAL from every entry point (see the kernel ids above).
  * Returns NULL on failure (device index out of range, device is not gfx950 -- the architecture name
  * is checked: the code object holds gfx950 kernels only -- or out of memory): no CPU fallback. */
 cgp_ctx *cgp_create(int device, int max_n, int max_m, int max_d, int max_batch, int dtype);
@@ -81,7 +96,9 @@ const char *cgp_last_error(const cgp_ctx *ctx);
  * for cgp_window_set_theta, cgp_window_set_theta_device, cgp_window_nll_grad, cgp_window_nll_grad_device and
  * cgp_window_optimize (hyper-parameters of the resident windows replaced / re-estimated in place): revision 3, symbols added only;
  * and for cgp_window_joint_reserve, cgp_window_predict_cov, cgp_window_predict_cov_device, cgp_window_sample and
- * cgp_window_sample_device (the joint forecast: full posterior covariance and sample paths). */
+ * cgp_window_sample_device (the joint forecast: full posterior covariance and sample paths).  Revision 3 libraries built after the
+ * Matern kernels were added accept CGP_KERNEL_MATERN32_ARD and CGP_KERNEL_MATERN52_ARD in fp64 contexts (values added only: an
+ * earlier library answers CGP_EINVAL for them; probe with cgp_fit on a two-sample window). */
 #define CGP_ABI_VERSION 3
 int cgp_abi_version(void);
 /* How the library was built: 0 for the shipped library.  CGP_BUILD_ABLATION (-DCGP_ABLATION): env
@@ -127,7 +144,8 @@ int cgp_nll_grad(cgp_ctx *ctx, const double *X, const double *y, int N, int d, i
  * 1000).  Writes the optimum to theta_inout, its log marginal likelihood to *logml, the number of
  * evaluations to *n_evals, and leaves the context fitted at the optimum (cgp_predict may follow).
  * *n_evals: windows of at most 160 samples (one-launch device optimiser) report the optimiser's own evaluations (what
- * scipy reports as nfev for the same run); longer windows (host optimiser over device gradients) report those + 1,
+ * scipy reports as nfev for the same run); longer windows, and Matern windows of any length (host optimiser over device
+ * gradients: which form runs is a function of (kernel, N, d, M) only), report those + 1,
  * the refit at the optimum that leaves the factor panel resident.  The optimiser is scipy's L-BFGS-B without bounds
  * (csrc/lbfgs_core.hpp): same line search, same stopping tests, same trajectory to rounding. */
 int cgp_optimize(cgp_ctx *ctx, const double *X, const double *y, int N, int d, int kernel_id,
