@@ -17,6 +17,13 @@ and call at --gpus 8).  CGP_BENCH_FORCE_DIST=1 runs the RCCL rendezvous / barrie
 with a world of ONE rank (the collective path on a one-GPU box).
 
 Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs).
+
+A plain run does what the headline needs and no more: set-up, the warm-up steps, the timed steps, the dump when asked for, the
+line (metric / value / unit / ms_per_step, the workload and its rates under `config`).  `--full` adds, after the timed region and the
+dump, every secondary measurement and check: the lone fit's latency, `roofline` and `kernel_ms_per_step` (extra profiled steps and
+two rocprofv3 --pmc child passes), `cpu_baseline` and the oracle checks of the timed outputs, `config.extra` (configs[2] / [3],
+look-ahead, node callback, replay, the C-ABI sweep, the fp32 refinement) and, on a multi-rank job, `cfg3_strong`; `--no-cpu`,
+`--no-extra` and `--no-pmc` take parts of that away again.
 """
 import argparse
 import json
@@ -52,11 +59,14 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=512, help="independent fits per GPU per step (2 per CU)")
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3])
     ap.add_argument("--n", type=int, default=None, help="override window length N")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="fits timed on the host for cpu_baseline (0 = by time budget)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip config.extra (cfg3 / window / look-ahead / end-to-end lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and the dump), also run every secondary measurement and check: single-fit latency, "
+                         "roofline / kernel_ms_per_step, cpu_baseline, config.extra, the live PMC passes (minutes instead of seconds)")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: fits timed on the host for cpu_baseline (0 = by time budget)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without cpu_baseline and the other host-side (oracle) legs")
+    ap.add_argument("--no-extra", action="store_true", help="--full without config.extra (cfg3 / window / look-ahead / end-to-end lines)")
     ap.add_argument("--streams", type=int, default=0, help="cgp_set_streams: 0 = the engine decides (default), 1 = one group, n = n groups")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child passes behind roofline.traffic")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the two rocprofv3 --pmc child passes behind roofline.traffic")
     ap.add_argument("--pipeline", type=int, default=0,
                     help="contexts (slab sets) the steps are dealt over, one HIP stream each, so that successive calls too small "
                          "to fill the chip overlap on the GPU (cross-sweep overlap: a throughput-of-repeated-sweeps figure, not the "
@@ -264,7 +274,8 @@ def run_rank(args):
             torch.cuda.synchronize()
         if args.dump_outputs and rank == 0:   # nothing has touched the output buffers since the last timed step
             dump_outputs(args.dump_outputs, W if depth == 1 else lanes[(turn[0] - 1) % depth])
-        single_ms = W.single_fit_latency_ms()
+        if args.full:
+            single_ms = W.single_fit_latency_ms()
         # per-fit summaries gathered over RCCL (the only collective on the path: SURVEY.md 8e)
         summ = torch.stack([W.dlogml, 2.0 * W.dvar.to(torch.float64).max(1).values.sqrt(), W.dinfo.to(torch.float64)], 1)
     else:
@@ -273,11 +284,11 @@ def run_rank(args):
     ens = sharding.ensemble_stats(table)
     assert table.shape[0] == B_total
 
-    # A plain `bench.py --gpus N` (weak scaling of the headline) also carries BASELINE configs[2] AS WRITTEN -- 512 x N=1024
+    # `bench.py --full --gpus N` (weak scaling of the headline) also carries BASELINE configs[2] AS WRITTEN -- 512 x N=1024
     # fp32 fits cut into contiguous per-rank shards, ONE context per GPU -- so that a driver-run scaling sweep shows the
     # strong-scaling curve of the sharded batch next to the weak-scaling headline (config.extra.cfg3_strong).
     cfg3_strong = None
-    if world > 1 and not strong and not args.no_extra and args.config == 2:
+    if args.full and world > 1 and not strong and not args.no_extra and args.config == 2:
         cfg3_strong = cfg3_strong_line(args, dry, world, rank, local, dev, cdev, use_dist, sync)
 
     if rank == 0:
@@ -287,13 +298,11 @@ def run_rank(args):
         out = {
             "metric": "GP-fits/s", "value": value, "unit": "fits/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": dts, "data": "synthetic",
+            "scaling": args.scaling, "vs_baseline": None, "dtype": dts, "data": "synthetic", "full": args.full,
             "config": {"workload": f"BASELINE configs[{args.config - 1}]: batch of independent fixed-theta GP fits, "
                                    f"N={N} d={d} M={M_TEST} kernel={'SE-ARD' if kid == 1 else 'SE-iso'} {dts}",
                        "fits_per_gpu_per_step": B if not strong else B_total / world, "fits_per_step_all_ranks": B_total,
                        "streams": args.streams, "pipeline_depth": depth, "N": N, "d": d, "M": M_TEST,
-                       "single_fit_latency_ms": single_ms,
-                       "single_fit_cholesky_roofline_frac": (f_chol / 1e12 / (single_ms * 1e-3) / peak) if single_ms else None,
                        "fit_tflops": value * f_fit / 1e12, "cholesky_roofline_frac": value * f_chol / 1e12 / world / peak,
                        "inputs": "resident in HBM", "ensemble": ens,
                        "ranks": world, "collective_backend": ("rccl" if backend == "nccl" else backend) if use_dist else None,
@@ -306,7 +315,9 @@ def run_rank(args):
                 out["config"].setdefault("extra", {})["cfg3_strong"] = cfg3_strong
         if ablation:
             out["ablation_build"] = True   # CGP_DBG in a -DCGP_ABLATION library: NOT a measurement of the product
-        if not dry:
+        if args.full and not dry:   # everything below is a run of its own behind the timed region: never part of a plain run
+            out["config"]["single_fit_latency_ms"] = single_ms
+            out["config"]["single_fit_cholesky_roofline_frac"] = f_chol / 1e12 / (single_ms * 1e-3) / peak
             out["roofline"], out["kernel_ms_per_step"] = W.roofline(peak)
             if world == 1 and not args.no_extra and not strong:
                 out["config"]["extra"] = extras(engine, torch, dev, local, W)
@@ -549,7 +560,8 @@ def under_profiler():
 
 def pmc_traffic_live(args):
     """HBM bytes per k_panel launch of THIS command, measured during this run: two child processes
-    `rocprofv3 --kernel-trace --pmc <counter> -- python3 bench.py --steps 1 ...` (FETCH_SIZE and WRITE_SIZE in separate
+    `rocprofv3 --kernel-trace --pmc <counter> -- python3 bench.py --steps 1 --full --no-cpu --no-extra --no-pmc ...` (--full:
+    the launches counted include those of the roofline's profiled steps, which `avg_launch_ms` is taken over; FETCH_SIZE and WRITE_SIZE in separate
     passes, no other tracing, as MI355X_MICROARCH.md's HBM section prescribes; FETCH doubled for the gfx950
     half-count, units KB).  Children, not exec: this process keeps its GPU context.  None if rocprofv3 is missing
     or a pass fails or overruns -- the committed builder-run figure then stays in the line."""
@@ -557,7 +569,7 @@ def pmc_traffic_live(args):
     if shutil.which("rocprofv3") is None or os.environ.get("CGP_BENCH_CHILD") or under_profiler():
         return None
     tmp = tempfile.mkdtemp(prefix="cgp_pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-cpu", "--no-extra", "--no-pmc",
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--full", "--no-cpu", "--no-extra", "--no-pmc",
              "--batch", str(args.batch), "--config", str(args.config)] + (["--n", str(args.n)] if args.n else [])
     # the children get a clean environment: nothing of a profiler that may be wrapping a parent survives
     env = {k: v for k, v in os.environ.items() if k != "LD_PRELOAD" and not k.startswith(PROFILER_ENV_PREFIXES)}

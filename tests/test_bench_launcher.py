@@ -20,7 +20,7 @@ def run_bench(*argv, **env):
 
 
 def test_gpus2_spawns_two_ranks():
-    r = run_bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8")
+    r = run_bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -32,7 +32,7 @@ def test_gpus2_spawns_two_ranks():
     assert j["steps"] == 3 and j["warmup"] == 1 and j["scaling"] == "weak"
     # whole-job value = fits of all ranks / max-over-ranks time
     assert j["value"] <= sum(j["config"]["per_rank_fits_per_s"]) * 1.001
-    # a plain multi-rank run also carries BASELINE configs[2] as written (strong scaling, one context per GPU)
+    # a multi-rank --full run also carries BASELINE configs[2] as written (strong scaling, one context per GPU)
     c3 = j["config"]["extra"]["cfg3_strong"]
     assert c3["n_gpus"] == 2 and c3["scaling"] == "strong" and c3["pipeline_depth"] == 1 and c3["fits_per_step_all_ranks"] == 512
     assert c3["fits_per_gpu_per_call"] == 256 and c3["fits_per_s"] > 0
@@ -48,6 +48,15 @@ def test_single_rank_dry_line():
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert j["n_gpus"] == 1 and j["config"]["ranks"] == 1 and j["config"]["collective_backend"] is None
+    assert j["full"] is False and "extra" not in j["config"]
+
+
+def test_plain_multi_rank_line_has_no_secondary_measurements():
+    """Without --full the ranks time the headline and nothing else: no configs[2] leg behind it."""
+    r = run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8")
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert j["full"] is False and j["n_gpus"] == 2 and j["config"]["ensemble"]["n"] == 16 and "extra" not in j["config"]
 
 
 def test_strong_scaling_shards_the_total():

@@ -1,4 +1,4 @@
-"""bench.py prints ONE JSON line with the driver's contract fields (plus roofline and cpu_baseline)."""
+"""bench.py prints ONE JSON line with the driver's contract fields; with --full also roofline, cpu_baseline and config.extra."""
 import json
 import os
 import subprocess
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "8", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "8", "--steps", "2", "--warmup", "1",
                         "--cpu-sample", "1", "--no-extra", "--no-pmc"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -33,7 +33,35 @@ def test_bench_line_contract():
     rows = cb["single_thread_rows"]      # the baseline is the FASTER of the two single-thread runs of the oracle
     assert cb["value"] == max(r["value"] for r in rows.values() if "value" in r)
     assert "ablation_build" not in j and "dry_run" not in j
-    assert j["value"] > 0 and j["config"]["single_fit_latency_ms"] > 0
+    assert j["value"] > 0 and j["config"]["single_fit_latency_ms"] > 0 and j["full"] is True
+
+
+def test_bench_plain_line_is_lean(tmp_path):
+    """Without --full the run is set-up, warm-up, the timed steps, the dump and the line: the headline fields are there and say
+    what the --full line says, nothing that takes a run of its own behind the timed region is (lone-fit latency, roofline,
+    per-kernel times, CPU baseline, config.extra), --no-cpu / --no-extra / --no-pmc change nothing, and the dumped arrays are
+    bit for bit those of a --full run of the same command."""
+    import numpy as np
+    lines, dumps = {}, {}
+    for tag, extra in (("plain", []), ("flags", ["--no-cpu", "--no-extra", "--no-pmc"]), ("full", ["--full", "--no-cpu", "--no-extra", "--no-pmc"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", "8", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / tag)] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines[tag] = json.loads(out[0])
+        dumps[tag] = {n: np.load(tmp_path / tag / (n + ".npy")) for n in ("mean", "var", "logml")}
+    for tag in ("plain", "flags"):
+        j = lines[tag]
+        assert j["full"] is False and j["metric"] == "GP-fits/s" and j["unit"] == "fits/s" and j["higher_is_better"] is True
+        assert j["dtype"] == "f64" and j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["scaling"] == "weak"
+        assert j["value"] > 0 and abs(j["value"] * j["ms_per_step"] * 1e-3 - 8) < 1e-6
+        assert not {"roofline", "kernel_ms_per_step", "cpu_baseline"} & set(j)
+        assert not {"extra", "single_fit_latency_ms", "single_fit_cholesky_roofline_frac", "single_fit_vs_cpu_1thread"} & set(j["config"])
+        assert j["config"]["ensemble"]["n"] == 8 and j["config"]["ensemble"]["n_failed"] == 0
+        assert j["config"]["workload"] == lines["full"]["config"]["workload"]
+        assert all(np.array_equal(dumps[tag][n], dumps["full"][n]) for n in ("mean", "var", "logml"))
+    assert lines["full"]["full"] is True and lines["full"]["roofline"]["frac"] > 0
 
 
 def test_bench_dump_outputs(tmp_path):
@@ -66,9 +94,9 @@ def test_bench_dump_outputs(tmp_path):
 
 
 def test_bench_extra_lines():
-    """config.extra of the same driver command: the PCIe-inclusive rate, BASELINE configs[2] (512 x N=1024
+    """config.extra of the same driver command with --full: the PCIe-inclusive rate, BASELINE configs[2] (512 x N=1024
     fp32) on its own schedule, configs[3] (sliding window) and the batched look-ahead."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "8", "--steps", "1", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "8", "--steps", "1", "--warmup", "1",
                         "--cpu-sample", "1", "--no-pmc"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -99,12 +127,12 @@ def test_bench_extra_lines():
 
 
 def test_bench_live_pmc_traffic():
-    """roofline.traffic is measured by the run itself: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) of
+    """roofline.traffic is measured by the --full run itself: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) of
     the same command.  32 fits per call take the throughput schedule, so k_panel launches exist."""
     import shutil
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 not on PATH")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "32", "--steps", "1", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "32", "--steps", "1", "--warmup", "1",
                         "--no-cpu", "--no-extra"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -121,7 +149,7 @@ def test_bench_gpus2_on_one_gpu():
     env = dict(os.environ, CGP_BENCH_SAME_DEVICE="1", CGP_BENCH_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "16", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "16", "--steps", "2",
                         "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -160,7 +188,7 @@ def test_bench_rccl_collectives_with_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "CGP_BENCH_BACKEND"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "3", "--batch", "64", "--steps", "3",
-                        "--warmup", "1", "--no-cpu", "--no-extra", "--no-pmc"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--warmup", "1", "--full", "--no-cpu", "--no-extra", "--no-pmc"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert j["config"]["collective_backend"] == "rccl" and j["config"]["collective_world"] == 1

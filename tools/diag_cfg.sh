@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 python3 $R/bench.py --no-pmc --no-cpu --no-extra "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err
-CGP_PROF_DUMP=1 python3 $R/bench.py --no-pmc --no-cpu --no-extra --steps 2 --warmup 1 "$@" > $O/${tag}_dump.json 2> $O/${tag}_dump.err
+CGP_PROF_DUMP=1 python3 $R/bench.py --full --no-pmc --no-cpu --no-extra --steps 2 --warmup 1 "$@" > $O/${tag}_dump.json 2> $O/${tag}_dump.err
 AB=$R/corenav_gp_amd/libcorenav_gp_ab.so
 for dbg in 64 128 192; do
   CGP_LIB=$AB CGP_DBG=$dbg python3 $R/bench.py --no-pmc --no-cpu --no-extra "$@" > $O/${tag}_dbg$dbg.json 2> $O/${tag}_dbg$dbg.err

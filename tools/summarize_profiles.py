@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Condenses rocprofv3 output (gpurun_out/<tag>_stats, <tag>_pmc1..4) into profiles/<round>_*.
+"""Condenses rocprofv3 output (<tag>_stats, <tag>_pmc1..4 where tools/profile_round.sh wrote them: env CGP_OUT, default <repo>/out)
+into profiles/<round>_*.
 PMC passes are separate runs (one counter group each), as the MI355X guide prescribes; FETCH_SIZE is
 doubled for the gfx950 half-count of wide coalesced reads (MI355X_MICROARCH.md, HBM section); units KB."""
 import collections
@@ -15,7 +16,7 @@ N = int(sys.argv[4]) if len(sys.argv) > 4 else 2048
 dtype = sys.argv[5] if len(sys.argv) > 5 else "f64"
 suffix = "" if dtype == "f64" else "_" + dtype
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src, dst = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles")
+src, dst = os.environ.get("CGP_OUT") or os.path.join(root, "out"), os.path.join(root, "profiles")
 os.makedirs(dst, exist_ok=True)
 shutil.copy(os.path.join(src, f"{tag}_stats", f"{tag}_kernel_stats.csv"), os.path.join(dst, f"{rnd}_kernel_stats{suffix}.csv"))
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
