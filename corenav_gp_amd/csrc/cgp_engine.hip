@@ -178,6 +178,7 @@ int node_callback_small(cgp_ctx *c, const double *time_array, const double *slip
                         double *mean, double *sigma, int cap, int *m_out);
 bool grow_pinned(void *&p, size_t &cap, size_t bytes);
 bool grow_device(void *&p, size_t &cap, size_t bytes);
+void window_free(cgp_ctx *c, bool joint_only);   // cgp_window_host.hpp
 
 inline int ntheta(int kid, int d) { return k_ntheta(kid, d); }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -254,21 +255,6 @@ constexpr bool kNoExtraSplit = CGP_NO_EXTRA_SPLIT != 0;
 #define CGP_LAT_MIN_NT 1   // block steps from which a handful of fits takes the latency schedule (3 until the end of round 3: `make variant` A/B)
 #endif
 constexpr size_t kOptPinIn = CGP_MAX_THETA + 8;   // doubles at the head of the gradient-mode pinned block: theta, jitter
-#ifndef CGP_WIN_PAIRS
-#define CGP_WIN_PAIRS 1   // sliding window: steady-state ticks two per pass over the factor (`make variant`: 0 = every tick on its own)
-#endif
-constexpr bool kWinPairs = CGP_WIN_PAIRS != 0;
-constexpr size_t kWinZeroCopyBytes = 16 * 1024;   // cgp_window_push blocks up to this size are read / written in pinned host memory by the kernels
-constexpr int kWinPackLds = 72 * 1024;       // pack windows into a workgroup only while two workgroups still fit a CU's LDS ...
-#ifndef CGP_WIN_MULTI
-#define CGP_WIN_MULTI 4   // steady-state ticks per pass over the factor where the window is long enough (k_window_multi); 0 = pairs only
-#endif
-constexpr int kWinMulti = CGP_WIN_MULTI > 2 ? CGP_WIN_MULTI : 4;
-constexpr bool kWinUseMulti = CGP_WIN_MULTI > 2;
-constexpr int kWinMultiMinWindows = 512;
-constexpr size_t kWinPairStage = 3 * WPB * 64 * sizeof(double);   // k_window_pairs: the three sweep waves' staged trips (24 KB)
-constexpr int kWinPackMinGroups = 512;
-constexpr int kWinWideMax = 256;            // single-tick kernel: up to this many windows 512 threads per window       // ... and the chip still gets two workgroups per CU
 // fp64 mid-size calls put their extra rows on a second stream when there is enough of them: fits x block steps >= this
 // (tools/r3_xs_n.sh, same box, with / without, ms per call: N = 2048 28 fits 3.77 / 3.70, 36 fits 4.25 / 4.45, 48 fits 5.01 / 5.70;
 // N = 1536 36 fits 2.37 / 2.38, 48 fits 2.71 / 3.01; N = 1024 36 fits 1.27 / 1.17, 48 fits 1.29 / 1.31; N = 512 28 fits 0.52 / 0.42)
@@ -1376,10 +1362,7 @@ void cgp_destroy(cgp_ctx *c) {
   }
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
-  for (void *wb : c->winbuf)
-    if (wb) (void)hipFree(wb);
-  for (void *jb : c->jointbuf)
-    if (jb) (void)hipFree(jb);
+  window_free(c, false);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -2438,732 +2421,8 @@ extern "C" int cgp_slip_node_callback_opt(cgp_ctx *c, const double *time_array, 
   return cgp_slip_node_callback(c, time_array, slip_array, n, kid, theta, mean, sigma, cap, m_out);
 }
 
-extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, const double *theta, int theta_stride) {
-  if (!c || nwin < 1 || N < 2 || N > 2048 || d < 1 || d > CGP_MAX_D || !theta || kid < 0 || kid > CGP_KERNEL_MATERN52_ARD) return CGP_EINVAL;
-  if (kid == CGP_KERNEL_RBF_BROWNIAN && d != 1) return CGP_EINVAL;
-  if (k_is_matern(kid) && c->dtype != CGP_F64) return CGP_EINVAL;
-  const int nth = ntheta(kid, d);
-  if (theta_stride < nth) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // the two-ticks-per-pass kernel keeps six window-length vectors in LDS: 98 KB at N = 2048
-  if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_pairs<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_pairs<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_pairs<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_multi<kWinMulti>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-      // the forecast keeps a chunk's V = L^-1 K* in LDS: 128 KB + the waves' partial tiles in every form (cgp_window_forecast.hpp)
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<2, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-      // the same solve with V kept for the joint forecast (cgp_window_joint.hpp)
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<2, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&k_window_forecast<1, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return CGP_EHIP;
-  if (k_is_matern(kid)) {   // the same limits for the Matern instantiations of those kernels
-    const void *fn150[] = {reinterpret_cast<const void *>(&k_window_pairs<1, true>), reinterpret_cast<const void *>(&k_window_pairs<2, true>),
-                           reinterpret_cast<const void *>(&k_window_pairs<4, true>)};
-    const void *fn160[] = {reinterpret_cast<const void *>(&k_window_forecast<2, 16, false, true>), reinterpret_cast<const void *>(&k_window_forecast<1, 16, false, true>),
-                           reinterpret_cast<const void *>(&k_window_forecast<1, 8, false, true>), reinterpret_cast<const void *>(&k_window_forecast<2, 16, true, true>),
-                           reinterpret_cast<const void *>(&k_window_forecast<1, 16, true, true>), reinterpret_cast<const void *>(&k_window_forecast<1, 8, true, true>)};
-    for (const void *fn : fn150)
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return CGP_EHIP;
-    for (const void *fn : fn160)
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CGP_EHIP;
-  }
-  // the old windows are gone from here on: a failure below must leave the context without windows,
-  // not with stale pointers (cgp_window_push checks nwin)
-  c->nwin = 0;
-  c->win = WindowArgs{};
-  auto drop = [c]() {
-    for (void *&wb : c->winbuf) {
-      if (wb) (void)hipFree(wb);
-      wb = nullptr;
-    }
-    for (void *&jb : c->jointbuf) {   // the joint forecast's scratch goes with the windows it was sized for
-      if (jb) (void)hipFree(jb);
-      jb = nullptr;
-    }
-    c->joint_max_m = 0;
-  };
-  drop();
-#ifndef CGP_WIN_CAP_PAD
-#define CGP_WIN_CAP_PAD 0
-#endif
-  const int CAP = 2 * N + CGP_WIN_CAP_PAD;   // ring capacity = leading dimension of the windows' slabs
-  const size_t W = nwin;
-  // [6]: cgp_window_predict's inverses of the factors' 16 x 16 diagonal blocks (allocated here: no allocation between launches of a call)
-  // [7]: cgp_window_nll_grad's alpha, per-chunk partial sums and values (cgp_window_adapt.hpp): 28 N / 16 + 1 doubles per window
-  size_t sizes[8] = {W * CAP * CAP * 8, W * CAP * 8, W * d * CAP * 8, W * CAP * 8, W * 4 * sizeof(int),
-                     W * (PREP_N + MAX_THETA) * 8, W * cdiv(N, WPB) * WPB * WPB * 8, W * ((size_t)cdiv(N, WPB) * (WPB + GRAD_N) + 1) * 8};
-  for (int i = 0; i < 8; ++i)
-    if (hipMalloc(&c->winbuf[i], sizes[i]) != hipSuccess) {
-      c->winbuf[i] = nullptr;
-      drop();
-      return CGP_ENOMEM;
-    }
-  WindowArgs wa{};
-  wa.L = (double *)c->winbuf[0];
-  wa.z = (double *)c->winbuf[1];
-  wa.xw = (double *)c->winbuf[2];
-  wa.yw = (double *)c->winbuf[3];
-  wa.state = (int *)c->winbuf[4];
-  double *pt = (double *)c->winbuf[5];
-  wa.prep = pt;
-  wa.theta = pt + W * PREP_N;
-  wa.N = N;
-  wa.CAP = CAP;
-  wa.d = d;
-  wa.kernel_id = kid;
-  std::vector<double> h(W * (PREP_N + MAX_THETA), 0.0);
-  for (size_t w = 0; w < W; ++w) {
-    const double *th = theta + w * theta_stride;
-    double *o = h.data() + w * PREP_N;
-    for (int q = 0; q < d; ++q) o[q] = k_is_ard(kid) ? 1.0 / th[1 + q] : 1.0 / th[1];
-    o[9] = th[0];
-    o[10] = (kid == CGP_KERNEL_RBF_BROWNIAN) ? th[2] : 0.0;
-    for (int q = 0; q < nth; ++q) h[W * PREP_N + w * MAX_THETA + q] = th[q];
-  }
-  // hipMemset of device memory is ASYNCHRONOUS to the host and ordered on the legacy default stream only -- the pushes run on the
-  // context's non-blocking stream (or the caller's), which does not wait for it: without the synchronisation below the first
-  // push could read the windows' state words before they were zeroed (found by round 6's sweep under load: fourteen processes
-  // sharing the GPU -- a memory access fault, or garbage for one window; never seen on an idle GPU, where the fill is over
-  // before the first launch is issued).
-  if (!hip_ok(c, hipMemcpy(pt, h.data(), h.size() * 8, hipMemcpyHostToDevice), "window theta H2D") ||
-      !hip_ok(c, hipMemset(wa.state, 0, W * 4 * sizeof(int)), "window state memset") ||
-      !hip_ok(c, hipDeviceSynchronize(), "window init synchronise")) {
-    drop();
-    return CGP_EHIP;
-  }
-  c->win = wa;  // published only when every allocation and copy has succeeded
-  c->nwin = nwin;
-  c->win_o = c->win_n = 0;
-  return CGP_OK;
-}
-
-namespace {
-int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, int include_noise, double *dpm, double *dpv, double *dl,
-                     int *info_out, hipStream_t ws);
-}
-extern "C" int cgp_window_push_device(cgp_ctx *c, int T, const double *dxs, const double *dys, int include_noise,
-                                      double *dpm, double *dpv, double *dl, void *hip_stream) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  if (T < 1 || !dxs || !dys || !dpm || !dpv || !dl) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  return window_push_impl(c, T, dxs, dys, include_noise, dpm, dpv, dl, nullptr, pick_stream(c, hip_stream));
-}
-namespace {
-// info_out: [nwin] ints the kernels mirror every window's status word into (pinned host memory for the per-tick entry), or null
-int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, int include_noise, double *dpm, double *dpv, double *dl,
-                     int *info_out, hipStream_t ws) {
-  WindowArgs a = c->win;
-  a.info_out = info_out;
-  a.xs = dxs;
-  a.ys = dys;
-  a.pred_mean = dpm;
-  a.pred_var = dpv;
-  a.logml = dl;
-  a.T = T;
-  a.include_noise = include_noise;
-  // The T ticks are cut into launches: runs of steady-state ticks (full windows, no ring compaction inside) go two per
-  // pass over the factor (k_window_pairs), everything else -- filling, the tick that compacts the ring, an odd one out --
-  // through the single-tick kernel.  Origin and size of the windows are deterministic and identical for every window of
-  // the context, so the host mirrors them instead of reading them back.
-  const size_t lds1 = (size_t)(3 * a.N + 8 * WPB + MAXD + 8 + 2 * WIN_STG) * sizeof(double);
-  const size_t lds2 = (size_t)(6 * ((a.N + 3) & ~1) + 16 * WPB + 2 * MAXD + 16) * sizeof(double);   // per window
-  // windows per workgroup of the paired kernel (rows of wave 0 per window: 4 / wpw)
-  // measured (tools/r3_winpack.sh, N = 512): 1024 windows 2.20 / 2.65 / 2.03 M ticks/s at 1 / 2 / 4 per workgroup, 512 windows
-  // 2.18 / 1.81 / 1.20 -- two per workgroup once that still leaves two workgroups per CU, four never
-  int wpw = 1;
-  if (c->nwin % 2 == 0 && 2 * lds2 + kWinPairStage <= (size_t)kWinPackLds + 8 * 1024 && c->nwin / 2 >= kWinPackMinGroups) wpw = 2;
-  if constexpr (kAbBuild) {
-    const char *e = getenv("CGP_WIN_WPW");
-    const int v = e ? atoi(e) : 0;
-    if ((v == 1 || v == 2 || v == 4) && c->nwin % v == 0 && v * lds2 + kWinPairStage <= 150 * 1024) wpw = v;
-  }
-  const int N = a.N, CAP = a.CAP;
-  if (c->win_o < 0) {   // the mirror was invalidated by a failed push: read the windows' state back (they advance in lock-step)
-    int st[4];
-    HIP_TRY(c, hipStreamSynchronize(ws));
-    HIP_TRY(c, hipMemcpy(st, c->win.state, sizeof(st), hipMemcpyDeviceToHost));
-    c->win_o = st[0];
-    c->win_n = st[1];
-  }
-  int o = c->win_o, n = c->win_n;
-  auto one_tick = [&](int &oo, int &nn) {   // k_window_ticks, one tick
-    if (oo + nn >= CAP) oo = 0;
-    const bool drop = nn >= N;
-    oo = drop ? oo + 1 : oo;
-    nn = (drop ? nn - 1 : nn) + 1;
-  };
-  auto pair_ok = [&](int oo, int nn, int left) { return kWinPairs && N >= 2 * WPB && nn == N && left >= 2 && oo + N + 1 < CAP; };
-  const int NSm = (N + kWinMulti + 3) & ~1;
-  const size_t ldsm = (size_t)(3 * kWinMulti * NSm + kWinMulti * (8 * WPB + MAXD + 8)) * sizeof(double) + kWinPairStage;
-  auto multi_ok = [&](int oo, int nn, int left) {
-    // (measured, N = 512: 512 windows 3.99 M ticks/s against 3.54 M two per pass, 1 024 windows 3.97 against 3.41; 256 windows 2.92 against 3.38 --
-    // one window per workgroup leaves half of a small call's lanes idle: from kWinMultiMinWindows windows)
-    return kWinUseMulti && kWinPairs && c->nwin >= kWinMultiMinWindows && N >= 4 * WPB && ldsm <= 80 * 1024 && nn == N && left >= kWinMulti &&
-           oo + N + kWinMulti - 1 < CAP;
-  };
-  for (int t = 0; t < T;) {
-    a.t0 = t;
-    int nm = 0;
-    for (int oo = o; multi_ok(oo, n, T - t - kWinMulti * nm); oo += kWinMulti) ++nm;
-    if (nm > 0) {
-      a.nt = kWinMulti * nm;
-      hipLaunchKernelGGL(k_window_multi<kWinMulti>, dim3(c->nwin), dim3(256), ldsm, ws, a);
-      o += kWinMulti * nm;
-      t += kWinMulti * nm;
-      continue;
-    }
-    int np = 0;
-    for (int oo = o; pair_ok(oo, n, T - t - 2 * np); oo += 2) ++np;
-    if (np > 0) {
-      a.nt = 2 * np;
-      if (k_is_matern(a.kernel_id)) {
-        if (wpw == 4) hipLaunchKernelGGL((k_window_pairs<4, true>), dim3(c->nwin / 4), dim3(256), 4 * lds2 + kWinPairStage, ws, a);
-        else if (wpw == 2) hipLaunchKernelGGL((k_window_pairs<2, true>), dim3(c->nwin / 2), dim3(256), 2 * lds2 + kWinPairStage, ws, a);
-        else hipLaunchKernelGGL((k_window_pairs<1, true>), dim3(c->nwin), dim3(256), lds2 + kWinPairStage, ws, a);
-      } else if (wpw == 4) hipLaunchKernelGGL(k_window_pairs<4>, dim3(c->nwin / 4), dim3(256), 4 * lds2 + kWinPairStage, ws, a);
-      else if (wpw == 2) hipLaunchKernelGGL(k_window_pairs<2>, dim3(c->nwin / 2), dim3(256), 2 * lds2 + kWinPairStage, ws, a);
-      else hipLaunchKernelGGL(k_window_pairs<1>, dim3(c->nwin), dim3(256), lds2 + kWinPairStage, ws, a);
-      o += 2 * np;
-      t += 2 * np;
-      continue;
-    }
-    int ns = 0;
-    do {
-      one_tick(o, n);
-      ++ns;
-    } while (t + ns < T && !pair_ok(o, n, T - t - ns));
-    a.nt = ns;
-    // threads per window: with no more windows than CUs a workgroup sweeps with seven waves instead of three (1024 threads: 128 VGPRs
-    // per lane, the serial wave spills -- 251 us per host tick against 117)
-    int wth = c->nwin <= kWinWideMax ? 512 : 256;
-    if constexpr (kAbBuild) {
-      const char *e = getenv("CGP_WIN_THREADS");
-      const int v = e ? atoi(e) : 0;
-      if (v == 256 || v == 512) wth = v;
-    }
-    if (wth == 512) hipLaunchKernelGGL(k_window_ticks<512>, dim3(c->nwin), dim3(512), lds1, ws, a);
-    else hipLaunchKernelGGL(k_window_ticks<256>, dim3(c->nwin), dim3(256), lds1, ws, a);
-    t += ns;
-  }
-  if (!hip_ok(c, hipGetLastError(), "window launches")) {
-    c->win_o = c->win_n = -1;   // what reached the device is unknown: the next push re-reads the state
-    return CGP_EHIP;
-  }
-  c->win_o = o;   // committed only once every launch of the push was accepted
-  c->win_n = n;
-  return CGP_OK;
-}
-}  // namespace
-
-extern "C" int cgp_window_push(cgp_ctx *c, int T, const double *xs, const double *ys, int include_noise, double *pm,
-                               double *pv, double *logml) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  if (T < 1 || !xs || !ys || !pm || !pv || !logml) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // The per-tick host entry (configs[3] is "streamed per IMU tick": T = 1 is the common call): no allocation and no
-  // pageable copy on the path.  One pinned block [xs | ys | pm pv logml | state] and its device twin live in the
-  // context; per call: stage in, ONE H2D, the launch, TWO D2H (outputs, window states), one synchronisation.
-  const size_t W = c->nwin, nx = W * T * c->win.d, ny = W * T;
-  const size_t ndbl = nx + 4 * ny, bytes = ndbl * 8 + W * 4 * sizeof(int);
-  // (the pinned block is never smaller than the largest push the kernels access in place: a block that was freed and allocated again
-  // between two small pushes -- the first pushes of a stream grow -- is what round 6's sweep caught under load, fourteen processes on
-  // the GPU: about one push in a hundred came back with its outputs untouched, the kernel's stores having gone to the pages of the
-  // block just freed.  One allocation for the context's lifetime takes the window out of that path.)
-  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(bytes, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
-  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
-  int *hst = reinterpret_cast<int *>(h + ndbl);
-  memcpy(h, xs, nx * 8);
-  memcpy(h + nx, ys, ny * 8);
-  hipStream_t s = c->stream;
-  if (bytes <= kWinZeroCopyBytes) {
-    // A tick or a handful of them (configs[3] is "streamed per IMU tick"): no copy command at all.  The kernels read the
-    // samples where they were staged (pinned host memory is device-visible at its host address) and write the tick's
-    // outputs and every window's status word back there; one synchronisation.  (Round 4: one H2D, two D2H, 176 us per tick of
-    // one N = 512 window, ~30 us of it the three copy commands; the tick itself is 147 us of one workgroup's serial chains.)
-    // T = 1 is ONE launch of the single-tick kernel, whose last store is the window's status word (after a system-scope fence): the host
-    // polls those words in the pinned block instead of synchronising the stream (a few microseconds of the runtime's wake-up), and
-    // falls back to the synchronisation if they do not arrive (which is also where a faulting kernel's error surfaces)
-    constexpr int kPending = INT_MIN;
-    const bool poll = T == 1;
-    for (size_t w = 0; w < W; ++w) hst[w] = poll ? kPending : 0;
-    int rc0 = window_push_impl(c, T, h, h + nx, include_noise, h + nx + ny, h + nx + 2 * ny, h + nx + 3 * ny, hst, s);
-    if (rc0 != CGP_OK) return rc0;
-    bool done = false;
-    if (poll) {
-      volatile int *v = hst;
-      const auto t0 = std::chrono::steady_clock::now();
-      for (int spin = 0;; ++spin) {
-        size_t w = 0;
-        while (w < W && v[w] != kPending) ++w;
-        if (w == W) { done = true; break; }
-        if ((spin & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    if (!done) HIP_TRY(c, hipStreamSynchronize(s));
-    memcpy(pm, h + nx + ny, ny * 8);
-    memcpy(pv, h + nx + 2 * ny, ny * 8);
-    memcpy(logml, h + nx + 3 * ny, ny * 8);
-    for (size_t w = 0; w < W; ++w)
-      if (hst[w] != 0) return hst[w];
-    return CGP_OK;
-  }
-  HIP_TRY(c, hipMemcpyAsync(d, h, (nx + ny) * 8, hipMemcpyHostToDevice, s));
-  int rc = cgp_window_push_device(c, T, d, d + nx, include_noise, d + nx + ny, d + nx + 2 * ny, d + nx + 3 * ny, s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + nx + ny, d + nx + ny, 3 * ny * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(hst, c->win.state, W * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  memcpy(pm, h + nx + ny, ny * 8);
-  memcpy(pv, h + nx + 2 * ny, ny * 8);
-  memcpy(logml, h + nx + 3 * ny, ny * 8);
-  for (size_t w = 0; w < W; ++w)
-    if (hst[w * 4 + 2] != 0) return hst[w * 4 + 2];
-  return CGP_OK;
-}
-
-// ---- forecast from the windows as they stand (cgp_window_forecast.hpp) ----------------------------------------------
-extern "C" int cgp_window_predict_device(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dvar,
-                                         void *hip_stream) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  if (M < 1 || !dxs || !dmean || !dvar) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t ws = pick_stream(c, hip_stream);
-  const WindowArgs &wa = c->win;
-  ForecastArgs a{};
-  a.L = wa.L; a.z = wa.z; a.xw = wa.xw; a.state = wa.state; a.prep = wa.prep; a.theta = wa.theta;
-  a.xs = dxs; a.mean = dmean; a.var = dvar;
-  a.dinv = static_cast<double *>(c->winbuf[6]);
-  a.N = wa.N; a.CAP = wa.CAP; a.d = wa.d; a.kernel_id = wa.kernel_id;
-  a.M = M; a.include_noise = include_noise; a.nwin = c->nwin;
-  a.NB = cdiv(wa.N, WPB);
-  // Origin and size are read from the windows' state words on the device (the kernels run after every earlier push of the
-  // stream), so the launches are sized by the capacity N and need no host mirror.  The form depends on N alone.
-  const int mc = wa.N <= 512 ? 32 : (wa.N <= 1024 ? 16 : 8);
-  a.nchunk = cdiv(M, mc);
-  const size_t lds = ((size_t)a.NB * WPB * mc + WF_WAVES * 256) * sizeof(double);   // the chunk's V + the waves' partial tiles
-  const long long total = (long long)c->nwin * a.nchunk;
-  if (total > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
-  if (k_is_matern(a.kernel_id)) {
-    if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16, false, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-    else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16, false, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-    else hipLaunchKernelGGL((k_window_forecast<1, 8, false, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-  } else if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-  else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-  else hipLaunchKernelGGL((k_window_forecast<1, 8>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-  if (!hip_ok(c, hipGetLastError(), "window forecast launches")) return CGP_EHIP;
-  return CGP_OK;
-}
-
-extern "C" int cgp_window_predict(cgp_ctx *c, int M, const double *xs, int include_noise, double *mean, double *var) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  if (M < 1 || !xs || !mean || !var) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // staged like a push: one pinned block [xs | mean var | state] and its device twin; a small call is read and written in
-  // place by the kernels (no copy command), a large one is one H2D and two D2H
-  const size_t W = c->nwin, nx = W * M * c->win.d, ny = W * M;
-  const size_t ndbl = nx + 2 * ny, bytes = ndbl * 8 + W * 4 * sizeof(int);
-  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(bytes, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
-  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
-  int *hst = reinterpret_cast<int *>(h + ndbl);
-  memcpy(h, xs, nx * 8);
-  hipStream_t s = c->stream;
-  const bool inplace = bytes <= kWinZeroCopyBytes;
-  if (!inplace) HIP_TRY(c, hipMemcpyAsync(d, h, nx * 8, hipMemcpyHostToDevice, s));
-  double *io = inplace ? h : d;
-  int rc = cgp_window_predict_device(c, M, io, include_noise, io + nx, io + nx + ny, s);
-  if (rc != CGP_OK) return rc;
-  if (!inplace) HIP_TRY(c, hipMemcpyAsync(h + nx, d + nx, 2 * ny * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(hst, c->win.state, W * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  memcpy(mean, h + nx, ny * 8);
-  memcpy(var, h + nx + ny, ny * 8);
-  for (size_t w = 0; w < W; ++w)
-    if (hst[w * 4 + 2] != 0) return hst[w * 4 + 2];
-  return CGP_OK;
-}
-
-// ---- joint forecast: full posterior covariance and sample paths (cgp_window_joint.hpp) -------------------------------
-extern "C" int cgp_window_joint_reserve(cgp_ctx *c, int max_m) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  if (max_m < 1 || max_m > 1024) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipDeviceSynchronize());   // an earlier joint forecast may still read the buffers that go
-  for (void *&jb : c->jointbuf) {
-    if (jb) (void)hipFree(jb);
-    jb = nullptr;
-  }
-  c->joint_max_m = 0;
-  const size_t W = c->nwin, mpad = (size_t)cdiv(max_m, WPB) * WPB, nrow = (size_t)cdiv(c->win.N, WPB) * WPB;
-  const size_t sizes[4] = {W * nrow * mpad * 8, W * mpad * mpad * 8, 2 * W * (size_t)max_m * 8, W * sizeof(int)};
-  for (int i = 0; i < 4; ++i)
-    if (hipMalloc(&c->jointbuf[i], sizes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      c->jointbuf[i] = nullptr;
-      for (void *&jb : c->jointbuf) {
-        if (jb) (void)hipFree(jb);
-        jb = nullptr;
-      }
-      return CGP_ENOMEM;
-    }
-  c->joint_max_m = max_m;
-  return CGP_OK;
-}
-
-namespace {
-// the launches both entry points share: diagonal inverses, the solve with V kept (mean to dmean, variance to the scratch), and
-// the contraction -- into the caller's dcov, or (dcov == nullptr) into the scratch matrix for the factorisation
-int window_joint_launch(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dcov, JointArgs &j, hipStream_t ws) {
-  const WindowArgs &wa = c->win;
-  ForecastArgs a{};
-  a.L = wa.L; a.z = wa.z; a.xw = wa.xw; a.state = wa.state; a.prep = wa.prep; a.theta = wa.theta;
-  a.xs = dxs; a.mean = dmean;
-  a.var = static_cast<double *>(c->jointbuf[2]) + (size_t)c->nwin * c->joint_max_m;
-  a.dinv = static_cast<double *>(c->winbuf[6]);
-  a.N = wa.N; a.CAP = wa.CAP; a.d = wa.d; a.kernel_id = wa.kernel_id;
-  a.M = M; a.include_noise = include_noise; a.nwin = c->nwin;
-  a.NB = cdiv(wa.N, WPB);
-  a.vkeep = static_cast<double *>(c->jointbuf[0]);
-  a.mt = cdiv(M, WPB);
-  const int mc = wa.N <= 512 ? 32 : (wa.N <= 1024 ? 16 : 8);   // the forecast's forms, by N alone
-  a.nchunk = cdiv(M, mc);
-  const size_t lds = ((size_t)a.NB * WPB * mc + WF_WAVES * 256) * sizeof(double);
-  j = JointArgs{};
-  j.state = wa.state; j.prep = wa.prep; j.theta = wa.theta; j.xs = dxs;
-  j.V = a.vkeep; j.mean = dmean; j.var = a.var; j.cov = dcov;
-  j.C = static_cast<double *>(c->jointbuf[1]);
-  j.jinfo = static_cast<int *>(c->jointbuf[3]);
-  j.d = wa.d; j.kernel_id = wa.kernel_id; j.M = M; j.nwin = c->nwin;
-  j.mt = a.mt; j.nrow = a.NB * WPB;
-  j.nsup = cdiv(j.mt, WJ_ST);
-  j.npair = j.nsup * (j.nsup + 1) / 2;
-  j.per_win = cdiv(j.npair, WJ_WAVES);
-  const long long total = (long long)c->nwin * a.nchunk, jtotal = (long long)c->nwin * j.per_win;
-  if (total > (1ll << 30) || jtotal > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS), jgrid = (unsigned)(cdiv((int)jtotal, WF_XCDS) * WF_XCDS);
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
-  if (k_is_matern(a.kernel_id)) {
-    if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16, true, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-    else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16, true, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-    else hipLaunchKernelGGL((k_window_forecast<1, 8, true, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-  } else if (wa.N <= 512) hipLaunchKernelGGL((k_window_forecast<2, 16, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-  else if (wa.N <= 1024) hipLaunchKernelGGL((k_window_forecast<1, 16, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-  else hipLaunchKernelGGL((k_window_forecast<1, 8, true>), dim3(grid), dim3(WF_THREADS), lds, ws, a);
-  if (dcov) hipLaunchKernelGGL(k_window_joint_cov<false>, dim3(jgrid), dim3(WJ_THREADS), 0, ws, j);
-  else hipLaunchKernelGGL(k_window_joint_cov<true>, dim3(jgrid), dim3(WJ_THREADS), 0, ws, j);
-  return CGP_OK;
-}
-}  // namespace
-
-extern "C" int cgp_window_predict_cov_device(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dcov,
-                                             void *hip_stream) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
-  if (M < 1 || !dxs || !dmean || !dcov) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
-  HIP_TRY(c, hipSetDevice(c->device));
-  JointArgs j;
-  int rc = window_joint_launch(c, M, dxs, include_noise, dmean, dcov, j, pick_stream(c, hip_stream));
-  if (rc != CGP_OK) return rc;
-  if (!hip_ok(c, hipGetLastError(), "window joint covariance launches")) return CGP_EHIP;
-  return CGP_OK;
-}
-
-extern "C" int cgp_window_sample_device(cgp_ctx *c, int M, const double *dxs, int S, const double *dxi, int include_noise,
-                                        double jitter_rel, double *dout, int *dinfo, void *hip_stream) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
-  if (M < 1 || S < 1 || !dxs || !dxi || !dout || !(jitter_rel >= 0.0)) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t ws = pick_stream(c, hip_stream);
-  JointArgs j;
-  int rc = window_joint_launch(c, M, dxs, include_noise, static_cast<double *>(c->jointbuf[2]), nullptr, j, ws);
-  if (rc != CGP_OK) return rc;
-  j.xi = dxi; j.out = dout; j.S = S; j.info = dinfo; j.jitter_rel = jitter_rel;
-  if (j.mt <= 4 * WA_WAVES) hipLaunchKernelGGL(k_window_joint_chol<4>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, j);
-  else hipLaunchKernelGGL(k_window_joint_chol<8>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, j);
-  const long long per_win = ((long long)j.mt * cdiv(S, WPB) + WJ_WAVES - 1) / WJ_WAVES;   // one wave per 16 x 16 tile of the paths
-  if (per_win * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  j.per_win = (int)per_win;
-  hipLaunchKernelGGL(k_window_joint_paths, dim3((unsigned)(j.per_win * c->nwin)), dim3(WJ_THREADS), 0, ws, j);
-  if (!hip_ok(c, hipGetLastError(), "window sample launches")) return CGP_EHIP;
-  return CGP_OK;
-}
-
-extern "C" int cgp_window_predict_cov(cgp_ctx *c, int M, const double *xs, int include_noise, double *mean, double *cov) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
-  if (M < 1 || !xs || !mean || !cov) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // device block [xs | mean | cov]; the copies are ordered on the context's stream with the launches
-  const size_t W = c->nwin, nx = W * M * c->win.d, ny = W * M, nc = W * M * M;
-  if (!grow_device(c->win_dev, c->win_dev_cap, (nx + ny + nc) * 8) || !grow_pinned(c->win_pin, c->win_pin_cap, std::max(W * 4 * sizeof(int), kWinZeroCopyBytes)))
-    return CGP_ENOMEM;
-  double *d = static_cast<double *>(c->win_dev);
-  int *hst = static_cast<int *>(c->win_pin);
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(d, xs, nx * 8, hipMemcpyHostToDevice, s));
-  int rc = cgp_window_predict_cov_device(c, M, d, include_noise, d + nx, d + nx + ny, s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(mean, d + nx, ny * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(cov, d + nx + ny, nc * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(hst, c->win.state, W * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  for (size_t w = 0; w < W; ++w)
-    if (hst[w * 4 + 2] != 0) return hst[w * 4 + 2];
-  return CGP_OK;
-}
-
-extern "C" int cgp_window_sample(cgp_ctx *c, int M, const double *xs, int S, const double *xi, int include_noise, double jitter_rel,
-                                 double *out, int *info) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
-  if (M < 1 || S < 1 || !xs || !xi || !out || !(jitter_rel >= 0.0)) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // device block [xs | xi | out | info]
-  const size_t W = c->nwin, nx = W * M * c->win.d, np = W * (size_t)S * M, ni = (W + 1) / 2;
-  if (!grow_device(c->win_dev, c->win_dev_cap, (nx + 2 * np + ni) * 8) || !grow_pinned(c->win_pin, c->win_pin_cap, std::max(W * sizeof(int), kWinZeroCopyBytes)))
-    return CGP_ENOMEM;
-  double *d = static_cast<double *>(c->win_dev);
-  int *hi = static_cast<int *>(c->win_pin);
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(d, xs, nx * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(d + nx, xi, np * 8, hipMemcpyHostToDevice, s));
-  int rc = cgp_window_sample_device(c, M, d, S, d + nx, include_noise, jitter_rel, d + nx + np, reinterpret_cast<int *>(d + nx + 2 * np), s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(out, d + nx + np, np * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(hi, d + nx + 2 * np, W * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  if (info) memcpy(info, hi, W * sizeof(int));
-  for (size_t w = 0; w < W; ++w)
-    if (hi[w] != 0) return (int)w + 1;
-  return CGP_OK;
-}
-
-extern "C" int cgp_window_state(cgp_ctx *c, int w, int *n, int *info) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  if (w < 0 || w >= c->nwin) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipDeviceSynchronize());
-  int st[4];
-  HIP_TRY(c, hipMemcpy(st, c->win.state + w * 4, sizeof(st), hipMemcpyDeviceToHost));
-  if (n) *n = st[1];
-  if (info) *info = st[2];
-  return CGP_OK;
-}
-
-// ---- hyper-parameters of the resident windows replaced / re-estimated in place (cgp_window_adapt.hpp) -----------------
-namespace {
-AdaptArgs adapt_args(cgp_ctx *c) {
-  const WindowArgs &wa = c->win;
-  AdaptArgs a{};
-  a.L = wa.L; a.z = wa.z; a.xw = wa.xw; a.yw = wa.yw; a.state = wa.state;
-  a.prep = const_cast<double *>(wa.prep);
-  a.theta = const_cast<double *>(wa.theta);
-  a.N = wa.N; a.CAP = wa.CAP; a.d = wa.d; a.kernel_id = wa.kernel_id; a.nwin = c->nwin;
-  a.NB = cdiv(wa.N, WPB);
-  a.dinv = static_cast<double *>(c->winbuf[6]);
-  double *sc = static_cast<double *>(c->winbuf[7]);
-  a.alpha = sc;
-  a.gpart = sc + (size_t)c->nwin * a.NB * WPB;
-  a.nllv = a.gpart + (size_t)c->nwin * a.NB * GRAD_N;
-  return a;
-}
-}  // namespace
-
-extern "C" int cgp_window_set_theta_device(cgp_ctx *c, const double *dtheta, int theta_stride, const unsigned char *dselect,
-                                           double *dlogml, int *dinfo, void *hip_stream) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  if (!dtheta || theta_stride < ntheta(c->win.kernel_id, c->win.d)) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t ws = pick_stream(c, hip_stream);
-  AdaptArgs a = adapt_args(c);
-  a.new_theta = dtheta; a.theta_stride = theta_stride; a.select = dselect; a.logml = dlogml; a.info = dinfo;
-  // origin and size come from the windows' state words; the form (accumulators per wave) depends on N alone
-  if (k_is_matern(a.kernel_id)) {
-    if (a.N <= 512) hipLaunchKernelGGL((k_window_refactor<4, true>), dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
-    else if (a.N <= 1024) hipLaunchKernelGGL((k_window_refactor<8, true>), dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
-    else hipLaunchKernelGGL((k_window_refactor<16, true>), dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
-  } else if (a.N <= 512) hipLaunchKernelGGL(k_window_refactor<4>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
-  else if (a.N <= 1024) hipLaunchKernelGGL(k_window_refactor<8>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
-  else hipLaunchKernelGGL(k_window_refactor<16>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, a);
-  if (!hip_ok(c, hipGetLastError(), "window refactor launch")) return CGP_EHIP;
-  return CGP_OK;
-}
-
-extern "C" int cgp_window_set_theta(cgp_ctx *c, const double *theta, int theta_stride, const unsigned char *select, double *logml,
-                                    int *info) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  const int nth = ntheta(c->win.kernel_id, c->win.d);
-  if (!theta || theta_stride < nth) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // one pinned block [theta | logml | info | select] and its device twin: one H2D, the launch, one D2H, one synchronisation
-  const size_t W = c->nwin, nt = W * nth, ni = (W + 1) / 2, ns = (W + 7) / 8, ndbl = nt + W + ni + ns;
-  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(ndbl * 8, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
-  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
-  for (size_t w = 0; w < W; ++w) memcpy(h + w * nth, theta + w * theta_stride, nth * sizeof(double));
-  unsigned char *hs = reinterpret_cast<unsigned char *>(h + nt + W + ni);
-  for (size_t w = 0; w < W; ++w) hs[w] = select ? (select[w] ? 1 : 0) : 1;
-  int *hi = reinterpret_cast<int *>(h + nt + W);
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemsetAsync(d + nt, 0, (W + ni) * 8, s));   // unselected windows report logML 0, info 0
-  HIP_TRY(c, hipMemcpyAsync(d, h, nt * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(d + nt + W + ni, hs, ns * 8, hipMemcpyHostToDevice, s));
-  int rc = cgp_window_set_theta_device(c, d, nth, reinterpret_cast<unsigned char *>(d + nt + W + ni), d + nt, reinterpret_cast<int *>(d + nt + W), s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + nt, d + nt, (W + ni) * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  if (logml) memcpy(logml, h + nt, W * sizeof(double));
-  if (info) memcpy(info, hi, W * sizeof(int));
-  for (size_t w = 0; w < W; ++w)
-    if (hi[w] != 0) return (int)w + 1;
-  return CGP_OK;
-}
-
-extern "C" int cgp_window_nll_grad_device(cgp_ctx *c, double *dnll, double *dgrad, int grad_stride, void *hip_stream) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  if (!dnll || !dgrad || grad_stride < ntheta(c->win.kernel_id, c->win.d)) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t ws = pick_stream(c, hip_stream);
-  AdaptArgs a = adapt_args(c);
-  a.nll = dnll; a.grad = dgrad; a.grad_stride = grad_stride;
-  const WindowArgs &wa = c->win;
-  ForecastArgs f{};   // k_window_diag_inv reads the windows and writes the inverses only
-  f.L = wa.L; f.state = wa.state; f.dinv = static_cast<double *>(c->winbuf[6]);
-  f.N = wa.N; f.CAP = wa.CAP; f.d = wa.d; f.kernel_id = wa.kernel_id; f.nwin = c->nwin; f.NB = a.NB;
-  const long long chunks = (long long)c->nwin * a.NB;
-  if (chunks > (1ll << 30)) return CGP_EINVAL;
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, f);
-  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, a);
-  hipLaunchKernelGGL(k_window_kinv_grad, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a);
-  hipLaunchKernelGGL(k_window_grad_finish, dim3((unsigned)cdiv(c->nwin, 64)), dim3(64), 0, ws, a);
-  if (!hip_ok(c, hipGetLastError(), "window gradient launches")) return CGP_EHIP;
-  return CGP_OK;
-}
-
-extern "C" int cgp_window_nll_grad(cgp_ctx *c, double *nll, double *grad, int grad_stride) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  const int nth = ntheta(c->win.kernel_id, c->win.d);
-  if (!nll || !grad || grad_stride < nth) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t W = c->nwin, ndbl = W * (1 + nth);
-  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(ndbl * 8, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
-  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
-  hipStream_t s = c->stream;
-  int rc = cgp_window_nll_grad_device(c, d, d + W, nth, s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h, d, ndbl * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  memcpy(nll, h, W * sizeof(double));
-  for (size_t w = 0; w < W; ++w) memcpy(grad + w * grad_stride, h + W + w * nth, nth * sizeof(double));
-  return CGP_OK;
-}
-
-// m.optimize() on the resident windows: cgp_optimize_batch's host loop (one batched evaluation per round, every window its own
-// LbfgsStepper and line search) with set_theta + nll_grad on the windows themselves as the evaluation.
-extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
-                                   double *logml_out, int *n_evals) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  const int nth = ntheta(c->win.kernel_id, c->win.d);
-  if (theta_out && theta_stride < nth) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const size_t W = c->nwin;
-  const int cap = max_evals > 0 ? max_evals : 1000;
-  std::vector<double> cur(W * MAX_THETA);
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipMemcpy(cur.data(), c->win.theta, cur.size() * sizeof(double), hipMemcpyDeviceToHost));
-  auto sel = [&](size_t w) { return !select || select[w] != 0; };
-  for (size_t w = 0; w < W; ++w)
-    for (int i = 0; i < nth; ++i)
-      if (sel(w) && !(cur[w * MAX_THETA + i] > 0.0)) return CGP_EINVAL;
-  auto to_theta = [](double x) { return x > 35.0 ? x : std::log1p(std::exp(x)); };
-  auto to_x = [](double th) { return th > 35.0 ? th : std::log(std::expm1(th)); };
-  std::vector<corenav::LbfgsStepper> st;
-  st.reserve(W);
-  for (size_t w = 0; w < W; ++w) {
-    std::vector<double> x0(nth);
-    for (int i = 0; i < nth; ++i) x0[i] = sel(w) ? to_x(cur[w * MAX_THETA + i]) : 0.0;
-    st.emplace_back(x0, cap, 1e-5, 1e7);
-  }
-  // staging: [theta | nll | grad | logml | info | select], pinned and on the device
-  const size_t nt = W * nth, ni = (W + 1) / 2, ns = (W + 7) / 8, ndbl = 2 * nt + 2 * W + ni + ns;
-  if (!grow_pinned(c->win_pin, c->win_pin_cap, std::max(ndbl * 8, kWinZeroCopyBytes)) || !grow_device(c->win_dev, c->win_dev_cap, ndbl * 8)) return CGP_ENOMEM;
-  double *h = static_cast<double *>(c->win_pin), *d = static_cast<double *>(c->win_dev);
-  double *hth = h, *hnll = h + nt, *hgrad = hnll + W, *hlm = hgrad + nt;
-  int *hinfo = reinterpret_cast<int *>(hlm + W);
-  unsigned char *hsel = reinterpret_cast<unsigned char *>(hlm + W + ni);
-  const size_t o_nll = nt, o_grad = nt + W, o_lm = 2 * nt + W, o_info = o_lm + W, o_sel = o_info + ni;
-  std::vector<double> gx(nth);
-  std::vector<char> at_best(W, 1);   // the window holds the factor of its stepper's best point
-  auto set_theta = [&]() -> int {    // the windows marked in hsel take hth
-    HIP_TRY(c, hipMemcpyAsync(d, hth, nt * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d + o_sel, hsel, ns * 8, hipMemcpyHostToDevice, s));
-    return cgp_window_set_theta_device(c, d, nth, reinterpret_cast<unsigned char *>(d + o_sel), d + o_lm, reinterpret_cast<int *>(d + o_info), s);
-  };
-  for (int round = 0; round < cap + 40; ++round) {
-    bool any = false;
-    for (size_t w = 0; w < W; ++w) {
-      const bool act = sel(w) && !st[w].done();
-      hsel[w] = act ? 1 : 0;
-      any = any || act;
-      const std::vector<double> &xx = st[w].trial();
-      for (int i = 0; i < nth; ++i) hth[w * nth + i] = act ? std::max(to_theta(xx[i]), 1e-300) : cur[w * MAX_THETA + i];
-    }
-    if (!any) break;
-    int rc = set_theta();
-    if (rc != CGP_OK) return rc;
-    rc = cgp_window_nll_grad_device(c, d + o_nll, d + o_grad, nth, s);
-    if (rc != CGP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(hnll, d + o_nll, (2 * W + nt + ni) * 8, hipMemcpyDeviceToHost, s));   // nll | grad | logml | info
-    HIP_TRY(c, hipStreamSynchronize(s));
-    for (size_t w = 0; w < W; ++w) {
-      if (!hsel[w]) continue;
-      const double *tb = hth + w * nth;
-      for (int i = 0; i < nth; ++i) cur[w * MAX_THETA + i] = tb[i];
-      double f = INFINITY;
-      if (hinfo[w] == 0 && std::isfinite(hnll[w])) {   // a trial point that is not positive definite is infeasible (no jitter ladder)
-        const std::vector<double> &xx = st[w].trial();
-        for (int i = 0; i < nth; ++i) gx[i] = hgrad[w * nth + i] * (xx[i] > 35.0 ? 1.0 : -std::expm1(-tb[i]));
-        f = hnll[w];
-      } else {
-        std::fill(gx.begin(), gx.end(), 0.0);
-      }
-      const std::vector<double> xt = st[w].trial();
-      st[w].tell(f, gx);
-      at_best[w] = st[w].best() == xt;
-    }
-  }
-  // a window whose last trial was not its best point gets the best theta's factor back
-  bool again = false;
-  for (size_t w = 0; w < W; ++w) {
-    hsel[w] = 0;
-    if (!sel(w)) continue;
-    const std::vector<double> &xb = st[w].best();
-    for (int i = 0; i < nth; ++i) hth[w * nth + i] = std::max(to_theta(xb[i]), 1e-300);
-    if (!at_best[w]) {
-      hsel[w] = 1;
-      again = true;
-    }
-  }
-  if (again) {
-    int rc = set_theta();
-    if (rc != CGP_OK) return rc;
-    HIP_TRY(c, hipStreamSynchronize(s));
-  }
-  for (size_t w = 0; w < W; ++w) {
-    if (!sel(w)) continue;
-    const corenav::LbfgsResult r = st[w].result();
-    if (theta_out) memcpy(theta_out + w * theta_stride, hth + w * nth, nth * sizeof(double));
-    if (logml_out) logml_out[w] = -r.f;
-    if (n_evals) n_evals[w] = r.evals;
-  }
-  return CGP_OK;
-}
+// the sliding windows' host layer: cgp_window_init ... cgp_window_optimize
+#include "cgp_window_host.hpp"
 
 struct cgp_recorder {
   corenav::SlipWindowRecorder r;
