@@ -39,6 +39,77 @@ template <bool MAT> auto pairs_kernel_of(int wpw) {
 }
 inline auto pairs_kernel(int wpw, bool matern) { return matern ? pairs_kernel_of<true>(wpw) : pairs_kernel_of<false>(wpw); }
 
+// LDS of a k_window_multi workgroup: three vectors per tick of the pass, the ticks' column blocks and the sweep waves' staged trips
+inline size_t multi_lds(int N) {
+  const int NSm = (N + kWinMulti + 3) & ~1;
+  return (size_t)(3 * kWinMulti * NSm + kWinMulti * (8 * WPB + MAXD + 8)) * sizeof(double) + kWinPairStage;
+}
+
+// The T ticks of a push are cut into launches: runs of steady-state ticks (full windows, no ring compaction inside) go two per
+// pass over the factor (k_window_pairs) or four (k_window_multi), everything else -- filling, the tick that compacts the ring, an
+// odd one out -- through the single-tick kernel.  Origin o and size n of the windows are deterministic and identical for every
+// window of the context, so the host mirrors them instead of reading them back: they come in as they stand before the push and
+// leave as they stand after it.  emit(kind, arg, t0, nt) is called once per launch, in order: kind CGP_PLAN_*, arg the windows per
+// workgroup (pairs), the ticks per pass (multi) or the threads per window (ticks), [t0, t0 + nt) the ticks.  cgp_window_push
+// launches from it and cgp_debug_window_plan records it: the choices below are made here and nowhere else.
+template <class Emit> void window_cut(int nwin, int N, int CAP, int T, int &o, int &n, Emit &&emit) {
+  // windows per workgroup of the paired kernel (rows of wave 0 per window: 4 / wpw)
+  // measured (tools/r3_winpack.sh, N = 512): 1024 windows 2.20 / 2.65 / 2.03 M ticks/s at 1 / 2 / 4 per workgroup, 512 windows
+  // 2.18 / 1.81 / 1.20 -- two per workgroup once that still leaves two workgroups per CU, four never
+  int wpw = 1;
+  if (nwin % 2 == 0 && pairs_lds(N, 2) <= (size_t)kWinPackLds + 8 * 1024 && nwin / 2 >= kWinPackMinGroups) wpw = 2;
+  // threads per window of the single-tick kernel: with no more windows than CUs a workgroup sweeps with seven waves instead of
+  // three (1024 threads: 128 VGPRs per lane, the serial wave spills -- 251 us per host tick against 117)
+  int wth = nwin <= kWinWideMax ? 512 : 256;
+  if constexpr (kAbBuild) {
+    const char *e = getenv("CGP_WIN_WPW");
+    int v = e ? atoi(e) : 0;
+    if ((v == 1 || v == 2 || v == 4) && nwin % v == 0 && pairs_lds(N, v) <= (size_t)kWinPushLdsMax) wpw = v;
+    e = getenv("CGP_WIN_THREADS");
+    v = e ? atoi(e) : 0;
+    if (v == 256 || v == 512) wth = v;
+  }
+  auto one_tick = [&](int &oo, int &nn) {   // k_window_ticks, one tick
+    if (oo + nn >= CAP) oo = 0;
+    const bool drop = nn >= N;
+    oo = drop ? oo + 1 : oo;
+    nn = (drop ? nn - 1 : nn) + 1;
+  };
+  auto pair_ok = [&](int oo, int nn, int left) { return kWinPairs && N >= 2 * WPB && nn == N && left >= 2 && oo + N + 1 < CAP; };
+  const size_t ldsm = multi_lds(N);
+  auto multi_ok = [&](int oo, int nn, int left) {
+    // (measured, N = 512: 512 windows 3.99 M ticks/s against 3.54 M two per pass, 1 024 windows 3.97 against 3.41; 256 windows 2.92 against 3.38 --
+    // one window per workgroup leaves half of a small call's lanes idle: from kWinMultiMinWindows windows)
+    return kWinUseMulti && kWinPairs && nwin >= kWinMultiMinWindows && N >= 4 * WPB && ldsm <= 80 * 1024 && nn == N && left >= kWinMulti &&
+           oo + N + kWinMulti - 1 < CAP;
+  };
+  for (int t = 0; t < T;) {
+    int nm = 0;
+    for (int oo = o; multi_ok(oo, n, T - t - kWinMulti * nm); oo += kWinMulti) ++nm;
+    if (nm > 0) {
+      emit(CGP_PLAN_MULTI, kWinMulti, t, kWinMulti * nm);
+      o += kWinMulti * nm;
+      t += kWinMulti * nm;
+      continue;
+    }
+    int np = 0;
+    for (int oo = o; pair_ok(oo, n, T - t - 2 * np); oo += 2) ++np;
+    if (np > 0) {
+      emit(CGP_PLAN_PAIRS, wpw, t, 2 * np);
+      o += 2 * np;
+      t += 2 * np;
+      continue;
+    }
+    int ns = 0;
+    do {
+      one_tick(o, n);
+      ++ns;
+    } while (t + ns < T && !pair_ok(o, n, T - t - ns));
+    emit(CGP_PLAN_TICKS, wth, t, ns);
+    t += ns;
+  }
+}
+
 template <bool MAT> auto refactor_kernel_of(int N) {   // accumulators per wave: 4 / 8 / 16
   return N <= kWinClassMaxN[0] ? k_window_refactor<4, MAT> : N <= kWinClassMaxN[1] ? k_window_refactor<8, MAT> : k_window_refactor<16, MAT>;
 }
@@ -247,22 +318,7 @@ int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, in
   a.logml = dl;
   a.T = T;
   a.include_noise = include_noise;
-  // The T ticks are cut into launches: runs of steady-state ticks (full windows, no ring compaction inside) go two per
-  // pass over the factor (k_window_pairs), everything else -- filling, the tick that compacts the ring, an odd one out --
-  // through the single-tick kernel.  Origin and size of the windows are deterministic and identical for every window of
-  // the context, so the host mirrors them instead of reading them back.
   const size_t lds1 = (size_t)(3 * a.N + 8 * WPB + MAXD + 8 + 2 * WIN_STG) * sizeof(double);
-  // windows per workgroup of the paired kernel (rows of wave 0 per window: 4 / wpw)
-  // measured (tools/r3_winpack.sh, N = 512): 1024 windows 2.20 / 2.65 / 2.03 M ticks/s at 1 / 2 / 4 per workgroup, 512 windows
-  // 2.18 / 1.81 / 1.20 -- two per workgroup once that still leaves two workgroups per CU, four never
-  int wpw = 1;
-  if (c->nwin % 2 == 0 && pairs_lds(a.N, 2) <= (size_t)kWinPackLds + 8 * 1024 && c->nwin / 2 >= kWinPackMinGroups) wpw = 2;
-  if constexpr (kAbBuild) {
-    const char *e = getenv("CGP_WIN_WPW");
-    const int v = e ? atoi(e) : 0;
-    if ((v == 1 || v == 2 || v == 4) && c->nwin % v == 0 && pairs_lds(a.N, v) <= (size_t)kWinPushLdsMax) wpw = v;
-  }
-  const int N = a.N, CAP = a.CAP;
   if (c->win_o < 0) {   // the mirror was invalidated by a failed push: read the windows' state back (they advance in lock-step)
     int st[4];
     HIP_TRY(c, hipStreamSynchronize(ws));
@@ -271,59 +327,15 @@ int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, in
     c->win_n = st[1];
   }
   int o = c->win_o, n = c->win_n;
-  auto one_tick = [&](int &oo, int &nn) {   // k_window_ticks, one tick
-    if (oo + nn >= CAP) oo = 0;
-    const bool drop = nn >= N;
-    oo = drop ? oo + 1 : oo;
-    nn = (drop ? nn - 1 : nn) + 1;
-  };
-  auto pair_ok = [&](int oo, int nn, int left) { return kWinPairs && N >= 2 * WPB && nn == N && left >= 2 && oo + N + 1 < CAP; };
-  const int NSm = (N + kWinMulti + 3) & ~1;
-  const size_t ldsm = (size_t)(3 * kWinMulti * NSm + kWinMulti * (8 * WPB + MAXD + 8)) * sizeof(double) + kWinPairStage;
-  auto multi_ok = [&](int oo, int nn, int left) {
-    // (measured, N = 512: 512 windows 3.99 M ticks/s against 3.54 M two per pass, 1 024 windows 3.97 against 3.41; 256 windows 2.92 against 3.38 --
-    // one window per workgroup leaves half of a small call's lanes idle: from kWinMultiMinWindows windows)
-    return kWinUseMulti && kWinPairs && c->nwin >= kWinMultiMinWindows && N >= 4 * WPB && ldsm <= 80 * 1024 && nn == N && left >= kWinMulti &&
-           oo + N + kWinMulti - 1 < CAP;
-  };
-  for (int t = 0; t < T;) {
-    a.t0 = t;
-    int nm = 0;
-    for (int oo = o; multi_ok(oo, n, T - t - kWinMulti * nm); oo += kWinMulti) ++nm;
-    if (nm > 0) {
-      a.nt = kWinMulti * nm;
-      hipLaunchKernelGGL(k_window_multi<kWinMulti>, dim3(c->nwin), dim3(256), ldsm, ws, a);
-      o += kWinMulti * nm;
-      t += kWinMulti * nm;
-      continue;
-    }
-    int np = 0;
-    for (int oo = o; pair_ok(oo, n, T - t - 2 * np); oo += 2) ++np;
-    if (np > 0) {
-      a.nt = 2 * np;
-      hipLaunchKernelGGL(pairs_kernel(wpw, k_is_matern(a.kernel_id)), dim3(c->nwin / wpw), dim3(256), pairs_lds(N, wpw), ws, a);
-      o += 2 * np;
-      t += 2 * np;
-      continue;
-    }
-    int ns = 0;
-    do {
-      one_tick(o, n);
-      ++ns;
-    } while (t + ns < T && !pair_ok(o, n, T - t - ns));
-    a.nt = ns;
-    // threads per window: with no more windows than CUs a workgroup sweeps with seven waves instead of three (1024 threads: 128 VGPRs
-    // per lane, the serial wave spills -- 251 us per host tick against 117)
-    int wth = c->nwin <= kWinWideMax ? 512 : 256;
-    if constexpr (kAbBuild) {
-      const char *e = getenv("CGP_WIN_THREADS");
-      const int v = e ? atoi(e) : 0;
-      if (v == 256 || v == 512) wth = v;
-    }
-    if (wth == 512) hipLaunchKernelGGL(k_window_ticks<512>, dim3(c->nwin), dim3(512), lds1, ws, a);
+  const bool matern = k_is_matern(a.kernel_id);
+  window_cut(c->nwin, a.N, a.CAP, T, o, n, [&](int kind, int arg, int t0, int nt) {
+    a.t0 = t0;
+    a.nt = nt;
+    if (kind == CGP_PLAN_MULTI) hipLaunchKernelGGL(k_window_multi<kWinMulti>, dim3(c->nwin), dim3(256), multi_lds(a.N), ws, a);
+    else if (kind == CGP_PLAN_PAIRS) hipLaunchKernelGGL(pairs_kernel(arg, matern), dim3(c->nwin / arg), dim3(256), pairs_lds(a.N, arg), ws, a);
+    else if (arg == 512) hipLaunchKernelGGL(k_window_ticks<512>, dim3(c->nwin), dim3(512), lds1, ws, a);
     else hipLaunchKernelGGL(k_window_ticks<256>, dim3(c->nwin), dim3(256), lds1, ws, a);
-    t += ns;
-  }
+  });
   if (!hip_ok(c, hipGetLastError(), "window launches")) {
     c->win_o = c->win_n = -1;   // what reached the device is unknown: the next push re-reads the state
     return CGP_EHIP;
@@ -575,6 +587,20 @@ extern "C" int cgp_window_state(cgp_ctx *c, int w, int *n, int *info) {
   if (n) *n = st[1];
   if (info) *info = st[2];
   return CGP_OK;
+}
+
+extern "C" int cgp_debug_window_plan(cgp_ctx *c, int T, int *out, int cap) {
+  if (!c || c->nwin < 1 || c->win_o < 0) return CGP_ESTATE;   // (an invalidated mirror is re-read by the next push, not here)
+  if (T < 1 || cap < 0 || (cap > 0 && !out)) return CGP_EINVAL;
+  int o = c->win_o, n = c->win_n, count = 0;
+  window_cut(c->nwin, c->win.N, c->win.CAP, T, o, n, [&](int kind, int arg, int t0, int nt) {
+    if (count < cap) {
+      const int rec[4] = {kind, arg, t0, nt};
+      memcpy(out + 4 * count, rec, sizeof(rec));
+    }
+    ++count;
+  });
+  return count;
 }
 
 // ---- hyper-parameters of the resident windows replaced / re-estimated in place (cgp_window_adapt.hpp) -----------------

@@ -32,6 +32,7 @@ DEBUG_SLOTS = 512
 ABI_VERSION = 3   # include/corenav_gp.h CGP_ABI_VERSION: load() refuses a library of another revision
 BUILD_ABLATION, BUILD_AB, BUILD_F32_NATIVE = 1, 2, 4
 STREAM_CTX = ctypes.c_void_p(-1).value   # CGP_STREAM_CTX: the context's private stream
+PLAN_TICKS, PLAN_PAIRS, PLAN_MULTI = 0, 1, 2   # CGP_PLAN_*: the kinds of launch cgp_debug_window_plan reports
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -93,6 +94,7 @@ _SIGS = {
     "cgp_debug_read": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "cgp_debug_buffers": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_ulonglong)]),
     "cgp_debug_small": (ctypes.c_int, [_vp, _dp]),
+    "cgp_debug_window_plan": (ctypes.c_int, [_vp, ctypes.c_int, _ip, ctypes.c_int]),
     "cgp_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_profile_read": (ctypes.c_int, [_vp, _dp, _dp, ctypes.POINTER(ctypes.c_longlong)]),
     "cgp_llh_to_enu": (ctypes.c_int, [ctypes.c_double] * 3 + [_dp, _dp, _dp]),
@@ -335,13 +337,17 @@ class Context:
         self._win_nth = ntheta(kernel_id, d)
         self._chk(self.lib.cgp_window_init(self.h, nwin, N, d, kernel_id, _p(theta), theta.shape[1]))
 
-    def window_push(self, xs, ys, include_noise=True):
-        """xs (nwin, T, d), ys (nwin, T) -> one-step-ahead mean, variance and logML per tick, each (nwin, T)."""
+    def window_push(self, xs, ys, include_noise=True, check=True):
+        """xs (nwin, T, d), ys (nwin, T) -> one-step-ahead mean, variance and logML per tick, each (nwin, T).  A window that
+        lost positive definiteness, in this push or an earlier one, raises CgpError with the 1-based tick of the push it failed
+        in (check=False: returns (mean, var, logml, code); the other windows' outputs are valid)."""
         nwin, d = self._win
         xs, ys = _d(xs).reshape(nwin, -1, d), _d(ys).reshape(nwin, -1)
         T = ys.shape[1]
         pm, pv, lm = np.empty((nwin, T)), np.empty((nwin, T)), np.empty((nwin, T))
         rc = self._chk(self.lib.cgp_window_push(self.h, T, _p(xs), _p(ys), int(include_noise), _p(pm), _p(pv), _p(lm)))
+        if not check:
+            return pm, pv, lm, rc
         if rc > 0:
             raise CgpError(rc)
         return pm, pv, lm
@@ -502,6 +508,15 @@ class Context:
         out = np.zeros(48)
         self._chk(self.lib.cgp_debug_small(self.h, _p(out)))
         return out
+
+    def window_plan(self, T, cap=64):
+        """[(kind, arg, t0, nt)] of the launches a window_push of T ticks would make now (include/corenav_gp.h:
+        cgp_debug_window_plan; kind is PLAN_TICKS / PLAN_PAIRS / PLAN_MULTI)."""
+        out = np.zeros(4 * cap, dtype=np.int32)
+        n = self._chk(self.lib.cgp_debug_window_plan(self.h, int(T), out.ctypes.data_as(_ip), cap))
+        if n > cap:
+            return self.window_plan(T, n)
+        return [tuple(int(v) for v in out[4 * i:4 * i + 4]) for i in range(n)]
 
     def set_streams(self, n):
         self._chk(self.lib.cgp_set_streams(self.h, int(n)))

@@ -298,6 +298,17 @@ int cgp_debug_small(cgp_ctx *ctx, double out[CGP_SMALL_OUT]);
  * (tools/ctx_placement.py prints them next to the timings of a context). */
 #define CGP_DEBUG_BUFFERS 8
 int cgp_debug_buffers(cgp_ctx *ctx, unsigned long long out[2 * CGP_DEBUG_BUFFERS]);
+/* Development aid: the launches a cgp_window_push / cgp_window_push_device of T ticks would make from the windows' present
+ * state, from the routine the push itself cuts its ticks with; nothing is launched and the context is unchanged.  Per launch
+ * out[4 i ..] = {kind, arg, t0, nt}: ticks [t0, t0 + nt) of the push go to k_window_ticks with `arg` threads per window
+ * (CGP_PLAN_TICKS), to k_window_pairs with `arg` windows per workgroup (CGP_PLAN_PAIRS) or to k_window_multi with `arg` ticks per
+ * pass (CGP_PLAN_MULTI).  At most `cap` records are written; returns the number of launches (call again with a larger array if
+ * it exceeds cap), CGP_ESTATE without windows or after a push whose launches failed.  The tests assert with it which kernel a
+ * case runs; the crossovers between the kernels are measured constants that move. */
+#define CGP_PLAN_TICKS 0
+#define CGP_PLAN_PAIRS 1
+#define CGP_PLAN_MULTI 2
+int cgp_debug_window_plan(cgp_ctx *ctx, int T, int *out, int cap);
 
 /* ---- online sliding-window GP (BASELINE configs[3]; not reference behaviour) -------------------
  * `nwin` independent windows of at most N samples each live on the device.  cgp_window_push feeds
@@ -306,7 +317,9 @@ int cgp_debug_buffers(cgp_ctx *ctx, unsigned long long out[2 * CGP_DEBUG_BUFFERS
  * one-step-ahead predictive mean / variance of the incoming y BEFORE it is added, and the log
  * marginal likelihood of the window after it.  theta (nwin, theta_stride) is fixed per window.
  * xs (nwin, T, d), ys (nwin, T); outputs (nwin, T).  Returns 0, or the 1-based tick at which a window
- * lost positive definiteness.  cgp_window_push blocks until the outputs are in the caller's arrays (a small push is read and
+ * lost positive definiteness: of the first such window in index order, counted within the push in which it failed.  The window
+ * keeps that code (cgp_window_state) and every later push returns it again, whatever its own length, until cgp_window_set_theta
+ * or cgp_window_init replaces the window; the other windows go on unaffected.  cgp_window_push blocks until the outputs are in the caller's arrays (a small push is read and
  * written by the kernels in pinned host memory; a one-tick push waits on the windows' status words there rather than on the
  * stream: 74 us per tick of one N = 512 window from a C caller).  Steady-state ticks of a longer push go two per pass over the
  * factors, four from 512 windows: the outputs are those of the tick-by-tick stream to rounding. */

@@ -32,9 +32,9 @@ def test_fuzz_single_window_api_prefix():
 
 
 def test_fuzz_sliding_window_prefix():
-    """tests/fuzz/fuzz_window.py: random window lengths around the 16-column panel boundaries, kernels, dimensions, stream
-    lengths with several ring compactions, 1-3 windows, random block cuts, against the refit-per-tick oracle (the
-    builder ran 90 s of this seed: 2 283 cases clean)."""
+    """tests/fuzz/fuzz_window.py: random window lengths around the 16-column panel boundaries and long ones around the kernels'
+    LDS limits, the five kernels, d <= 8, stream lengths with several ring compactions, 1-3 or 256 ... 1 024 windows, random block
+    cuts, against the refit oracle (150 s of seed 0: 1 094 cases clean, profiles/window_paths_fuzz_extended.txt)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz", "fuzz_window.py"), "10", "1"], capture_output=True,
                        text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-2000:])
