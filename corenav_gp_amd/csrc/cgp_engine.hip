@@ -8,6 +8,7 @@
 #include "cgp_window_forecast.hpp"
 #include "cgp_window_adapt.hpp"
 #include "cgp_window_joint.hpp"
+#include "cgp_joint.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
 #include "cgp_refine.hpp"
@@ -125,6 +126,12 @@ struct cgp_ctx {
   // mean | variance [2][nwin][max_m], failure words [nwin]
   void *jointbuf[4] = {nullptr};
   int joint_max_m = 0;
+  // joint forecast after batch / single fits (cgp_joint_reserve): the posterior covariance or its factor [max_batch][(mt * 16)^2],
+  // the factorisations' failure words [max_batch]; staging of the host sampling calls [xi | out], grown on demand and kept
+  void *fjbuf[2] = {nullptr};
+  int fj_max_batch = 0, fj_max_m = 0;
+  void *fj_dev = nullptr;
+  size_t fj_dev_cap = 0;
   // cgp_window_push staging, grown on demand and kept: one pinned host block and one device block per direction
   void *win_pin = nullptr, *win_dev = nullptr;
   size_t win_pin_cap = 0, win_dev_cap = 0;
@@ -137,6 +144,7 @@ struct cgp_ctx {
   int *dsmdone = nullptr;              // k_small_predict's count of finished workgroups (the node callback polls a pinned word the last one writes)
   int small_seq = 0;
   size_t smdeal_off[SM_MAX_NB + 1] = {0};
+  std::vector<char> xs_stage;     // cgp_predict's test points in the device layout: the source of an asynchronous copy, kept until the next call
   std::vector<double> lazy_win;   // [X (N, d) | y] of the window a short-window kernel evaluated in place (ensure_fitted uploads it)
   int pending_tab = 0;               // tick-grid table size cgp_fit_predict_batch found for the batch it is about to submit (0: none)
   bool last_small_dev = false;       // ... or window 0's record of the last batched fit + predict launch, still in dsmall
@@ -179,6 +187,13 @@ int node_callback_small(cgp_ctx *c, const double *time_array, const double *slip
 bool grow_pinned(void *&p, size_t &cap, size_t bytes);
 bool grow_device(void *&p, size_t &cap, size_t bytes);
 void window_free(cgp_ctx *c, bool joint_only);   // cgp_window_host.hpp
+// cgp_joint_host.hpp.  What a joint call adds to a batch of fits: the contraction of the fits' V rows into their covariance slots.
+struct JointHook {
+  double *dcov;   // output form (batch, M, M) on the device; null: the scratch form for the factorisation
+};
+void joint_free(cgp_ctx *c);
+int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, const double *dXs,
+                     const double *dtheta, const double *dvar, const int *dinfo, hipStream_t s);
 
 inline int ntheta(int kid, int d) { return k_ntheta(kid, d); }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -1363,6 +1378,7 @@ void cgp_destroy(cgp_ctx *c) {
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
   window_free(c, false);
+  joint_free(c);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -1480,10 +1496,12 @@ int cgp_profile_read(cgp_ctx *c, double ms[CGP_PROF_KERNELS], double flops[CGP_P
   return CGP_OK;
 }
 
-int cgp_fit_predict_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int kid, const void *dX,
-                                 const void *dy, const void *dXs, const double *dtheta, const double *djitter,
-                                 int include_noise, void *dmean, void *dvar, double *dlogml, int *dinfo,
-                                 void *hip_stream) {
+// tiled_only: the joint entry points (cgp_joint_host.hpp) keep every shape on the tiled schedules -- the contraction reads V^T from
+// the factor panel, which the one-launch short-window kernel never writes.  Among the tiled
+// schedules the call takes the one the marginal call of its size takes: mean and variance are bitwise that call's
+static int fit_predict_device(cgp_ctx *c, int batch, int N, int d, int M, int kid, const void *dX, const void *dy, const void *dXs,
+                              const double *dtheta, const double *djitter, int include_noise, void *dmean, void *dvar, double *dlogml,
+                              int *dinfo, void *hip_stream, bool tiled_only) {
   int rc = check_shape(c, batch, N, d, M, kid);
   if (rc != CGP_OK) return rc;
   if (!dX || !dy || !dtheta || !dlogml || !dinfo || (M > 0 && (!dXs || !dmean || !dvar))) return CGP_EINVAL;
@@ -1500,7 +1518,7 @@ int cgp_fit_predict_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int
   a.info = dinfo;
   c->have_fit = false;
   c->lazy_fit = false;
-  if (!k_is_matern(kid) && small_batch_predict_ok(c, batch, N, d, M)) {   // short windows: fit + predictions of the whole batch in ONE launch, factors in LDS
+  if (!tiled_only && !k_is_matern(kid) && small_batch_predict_ok(c, batch, N, d, M)) {   // short windows: fit + predictions of the whole batch in ONE launch, factors in LDS
     const SmallDev dev{static_cast<const double *>(dX), static_cast<const double *>(dy), static_cast<const double *>(dXs), dtheta, djitter, dlogml, dinfo};
     const int tab = c->pending_tab;   // only the host-buffer entry point knows whether the inputs are tick counts
     c->pending_tab = 0;
@@ -1510,12 +1528,23 @@ int cgp_fit_predict_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int
   return run(c, a, batch, true, false, pick_stream(c, hip_stream));
 }
 
-int cgp_fit_predict_batch(cgp_ctx *c, int batch, int N, int d, int M, int kid, const double *X, const double *y,
-                          const double *Xs, const double *theta, int theta_stride, int include_noise,
-                          double *mean, double *var, double *logml, int *info) {
+int cgp_fit_predict_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int kid, const void *dX,
+                                 const void *dy, const void *dXs, const double *dtheta, const double *djitter,
+                                 int include_noise, void *dmean, void *dvar, double *dlogml, int *dinfo,
+                                 void *hip_stream) {
+  return fit_predict_device(c, batch, N, d, M, kid, dX, dy, dXs, dtheta, djitter, include_noise, dmean, dvar, dlogml, dinfo, hip_stream,
+                            false);
+}
+
+// jh: a joint call (cgp_joint_host.hpp, fp64).  Tiled schedules for every shape, and every fit's V rows are contracted into its
+// covariance slot while they are still in the panel: the whole batch before the ladder's first retry, a retried fit -- which runs
+// as a call of one fit, in slab 0 -- right after its retry.  mean / var may be NULL then (the device copies stay in the context).
+static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, int kid, const double *X, const double *y,
+                                  const double *Xs, const double *theta, int theta_stride, int include_noise,
+                                  double *mean, double *var, double *logml, int *info, const JointHook *jh) {
   int rc = check_shape(c, batch, N, d, M, kid);
   if (rc != CGP_OK) return rc;
-  if (!X || !y || !theta || (M > 0 && (!Xs || !mean || !var))) return CGP_EINVAL;
+  if (!X || !y || !theta || (M > 0 && (!Xs || (!jh && (!mean || !var))))) return CGP_EINVAL;
   const int nth = ntheta(kid, d);
   if (theta_stride < nth) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1603,13 +1632,16 @@ int cgp_fit_predict_batch(cgp_ctx *c, int batch, int N, int d, int M, int kid, c
   }
   // (the scan that establishes "tick counts" is 1.5 ns per input on the host: 0.3 ms for 256 windows with their 599 test points,
   // more than the launch it would shorten by a tenth -- ensembles beyond 20 k inputs take the direct evaluation)
-  const int tick_tab = small_batch_predict_ok(c, batch, N, d, M) && (size_t)batch * (N + M) <= 20000
+  const int tick_tab = !jh && small_batch_predict_ok(c, batch, N, d, M) && (size_t)batch * (N + M) <= 20000
                            ? tick_table_entries_batch(kid, d, batch, X, N, Xs, M) : 0;
   c->pending_tab = tick_tab;
-  rc = cgp_fit_predict_batch_device(c, batch, N, d, M, kid, c->dX, c->dy, c->dXs, c->dtheta, c->djitter,
-                                    include_noise, c->dmean, c->dvar, c->dlogml, c->dinfo, CGP_STREAM_CTX);
+  rc = fit_predict_device(c, batch, N, d, M, kid, c->dX, c->dy, c->dXs, c->dtheta, c->djitter,
+                          include_noise, c->dmean, c->dvar, c->dlogml, c->dinfo, CGP_STREAM_CTX, jh != nullptr);
   c->pending_tab = 0;
   if (rc != CGP_OK) return rc;
+  if (jh && (rc = joint_cov_launch(c, *jh, N, d, M, kid, 0, 0, batch, static_cast<const double *>(c->dXs), c->dtheta,
+                                   static_cast<const double *>(c->dvar), c->dinfo, s)) != CGP_OK)
+    return rc;
   char *hout = static_cast<char *>(c->pin_out);
   double *hl = reinterpret_cast<double *>(hout + out_elems * esz);
   int *hinfo = reinterpret_cast<int *>(hl + B);
@@ -1639,12 +1671,15 @@ int cgp_fit_predict_batch(cgp_ctx *c, int batch, int N, int d, int M, int kid, c
     for (int attempt = 0; attempt < 5 && hinfo[b] != 0; ++attempt, jit *= 10.0) {
       HIP_TRY(c, hipMemcpyAsync(c->djitter + b, &jit, sizeof(double), hipMemcpyHostToDevice, s));
       c->pending_tab = tick_tab;
-      rc = cgp_fit_predict_batch_device(
+      rc = fit_predict_device(
           c, 1, N, d, M, kid, (char *)c->dX + (size_t)b * d * N * esz, (char *)c->dy + (size_t)b * N * esz,
           (char *)c->dXs + (size_t)b * d * M * esz, c->dtheta + (size_t)b * CGP_MAX_THETA, c->djitter + b,
           include_noise, (char *)c->dmean + (size_t)b * M * esz, (char *)c->dvar + (size_t)b * M * esz,
-          c->dlogml + b, c->dinfo + b, CGP_STREAM_CTX);
+          c->dlogml + b, c->dinfo + b, CGP_STREAM_CTX, jh != nullptr);
       if (rc != CGP_OK) return rc;
+      if (jh && (rc = joint_cov_launch(c, *jh, N, d, M, kid, 0, b, 1, static_cast<const double *>(c->dXs), c->dtheta,
+                                       static_cast<const double *>(c->dvar), c->dinfo, s)) != CGP_OK)
+        return rc;
       HIP_TRY(c, hipMemcpyAsync(&hinfo[b], c->dinfo + b, sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_TRY(c, hipStreamSynchronize(s));
       hjit[b] = jit;
@@ -1658,8 +1693,8 @@ int cgp_fit_predict_batch(cgp_ctx *c, int batch, int N, int d, int M, int kid, c
   lap("D2H");
   if (M > 0) {
     if (c->dtype == CGP_F64) {
-      memcpy(mean, hout, B * M * sizeof(double));
-      memcpy(var, hout + B * M * esz, B * M * sizeof(double));
+      if (mean) memcpy(mean, hout, B * M * sizeof(double));
+      if (var) memcpy(var, hout + B * M * esz, B * M * sizeof(double));
     } else {
       const float *fm = reinterpret_cast<const float *>(hout), *fv = fm + B * M;
       for (size_t i = 0; i < B * M; ++i) {
@@ -1676,6 +1711,12 @@ int cgp_fit_predict_batch(cgp_ctx *c, int batch, int N, int d, int M, int kid, c
   }
   lap("copy out");
   return first;
+}
+
+int cgp_fit_predict_batch(cgp_ctx *c, int batch, int N, int d, int M, int kid, const double *X, const double *y,
+                          const double *Xs, const double *theta, int theta_stride, int include_noise,
+                          double *mean, double *var, double *logml, int *info) {
+  return fit_predict_batch_host(c, batch, N, d, M, kid, X, y, Xs, theta, theta_stride, include_noise, mean, var, logml, info, nullptr);
 }
 
 int cgp_fit(cgp_ctx *c, const double *X, const double *y, int N, int d, int kid, const double *theta, double *logml) {
@@ -1696,15 +1737,18 @@ int cgp_fit(cgp_ctx *c, const double *X, const double *y, int N, int d, int kid,
   return info;
 }
 
-int cgp_predict(cgp_ctx *c, const double *Xs, int M, int include_noise, double *mean, double *var) {
-  if (!c || !Xs || !mean || !var || M < 1) return CGP_EINVAL;
+// the extra rows of M test points against the resident factor of the last single fit, on the context's stream: V^T into slab 0,
+// mean / variance into dmean / dvar (cgp_predict; the single-fit joint calls of cgp_joint_host.hpp contract V^T after it)
+static int predict_enqueue(cgp_ctx *c, const double *Xs, int M, int include_noise) {
   if (!c->have_fit) return CGP_ESTATE;
   if (M > c->max_m) return CGP_ECAPACITY;
   HIP_TRY(c, hipSetDevice(c->device));
   if (int fr = ensure_fitted(c)) return fr;
   hipStream_t s = c->stream;
   const size_t esz = c->esz;
-  std::vector<char> hxs((size_t)c->fd * M * esz);
+  HIP_TRY(c, hipStreamSynchronize(s));   // (an earlier call's copy has read the staging vector)
+  std::vector<char> &hxs = c->xs_stage;
+  hxs.resize((size_t)c->fd * M * esz);
   pack_soa(Xs, M, c->fd, c->dtype, hxs, 0);
   HIP_TRY(c, hipMemcpyAsync(c->dXs, hxs.data(), hxs.size(), hipMemcpyHostToDevice, s));
   FitArgs a = base_args(c, c->fN, c->fd, M, c->fkernel, include_noise);
@@ -1717,8 +1761,15 @@ int cgp_predict(cgp_ctx *c, const double *Xs, int M, int include_noise, double *
   a.var = c->dvar;
   a.logml = c->dlogml;
   a.info = c->dinfo;
-  int rc = run(c, a, 1, false, false, s);
+  return run(c, a, 1, false, false, s);
+}
+
+int cgp_predict(cgp_ctx *c, const double *Xs, int M, int include_noise, double *mean, double *var) {
+  if (!c || !Xs || !mean || !var || M < 1) return CGP_EINVAL;
+  int rc = predict_enqueue(c, Xs, M, include_noise);
   if (rc != CGP_OK) return rc;
+  hipStream_t s = c->stream;
+  const size_t esz = c->esz;
   std::vector<char> hm((size_t)M * esz), hv((size_t)M * esz);
   HIP_TRY(c, hipMemcpyAsync(hm.data(), c->dmean, hm.size(), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(hv.data(), c->dvar, hv.size(), hipMemcpyDeviceToHost, s));
@@ -2423,6 +2474,8 @@ extern "C" int cgp_slip_node_callback_opt(cgp_ctx *c, const double *time_array, 
 
 // the sliding windows' host layer: cgp_window_init ... cgp_window_optimize
 #include "cgp_window_host.hpp"
+// joint forecast after batch / single fits: cgp_joint_reserve ... cgp_sample
+#include "cgp_joint_host.hpp"
 
 struct cgp_recorder {
   corenav::SlipWindowRecorder r;

@@ -72,6 +72,18 @@ _SIGS = {
                                                                           ctypes.c_int, _dp, _dp, _dp, _ip]),
     "cgp_fit_predict_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp, _vp,
                                                                                  ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "cgp_joint_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "cgp_fit_predict_cov_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp, _dp, _dp, _dp, ctypes.c_int,
+                                                                              ctypes.c_int, _dp, _dp, _dp, _ip]),
+    "cgp_fit_predict_cov_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp, _vp,
+                                                                                     ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "cgp_fit_sample_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int,
+                                                                         ctypes.c_int, _dp, ctypes.c_double, _dp, _dp, _ip, _ip]),
+    "cgp_fit_sample_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                                                                ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp,
+                                                                                _vp, _vp]),
+    "cgp_predict_cov": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    "cgp_sample": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_double, _dp, _ip]),
     "cgp_window_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int]),
     "cgp_window_push": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
     "cgp_window_push_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
@@ -327,6 +339,79 @@ class Context:
 
     def synchronize(self):
         self._chk(self.lib.cgp_synchronize(self.h))
+
+    # -- joint forecast after batch / single fits (fp64 contexts) ---------------------------------------
+    def joint_reserve(self, max_batch, max_m):
+        """Scratch for the joint calls below (posterior covariance / its factor of up to max_batch fits at up to max_m test
+        points: max_batch x max_m^2 doubles, max_m rounded up to 16)."""
+        return self._chk(self.lib.cgp_joint_reserve(self.h, int(max_batch), int(max_m)))
+
+    def fit_predict_cov_batch(self, X, y, Xs, theta, kernel_id, include_noise=True):
+        """fit_predict_batch with the full posterior covariance (B, M, M) in place of the variance; include_noise adds the
+        noise variance to the diagonal only.  A fit whose info stays non-zero after the jitter ladder has NaN in its covariance."""
+        X, y, Xs, theta = _d(X), _d(y), _d(Xs), _d(theta)
+        B, N, d = X.shape
+        M = Xs.shape[1]
+        mean, cov = np.empty((B, M)), np.empty((B, M, M))
+        logml, info = np.empty(B), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_fit_predict_cov_batch(self.h, B, N, d, M, kernel_id, _p(X), _p(y), _p(Xs), _p(theta),
+                                                          theta.shape[1], int(include_noise), _p(mean), _p(cov),
+                                                          _p(logml), info.ctypes.data_as(_ip)))
+        return rc, mean, cov, logml, info
+
+    def fit_predict_cov_batch_device(self, B, N, d, M, kernel_id, dX, dy, dXs, dtheta, djitter, include_noise, dmean,
+                                     dcov, dlogml, dinfo, stream=0):
+        """Device pointers as fit_predict_batch_device, dcov (B, M, M) in place of dvar."""
+        return self._chk(self.lib.cgp_fit_predict_cov_batch_device(self.h, B, N, d, M, kernel_id, dX, dy, dXs, dtheta,
+                                                                   djitter or None, int(include_noise), dmean, dcov,
+                                                                   dlogml, dinfo, ctypes.c_void_p(stream)))
+
+    def fit_sample_batch(self, X, y, Xs, theta, kernel_id, xi, include_noise=False, jitter_rel=1e-6):
+        """Fits and sample paths of their joint posterior: xi (B, S, M) standard normals drawn by the caller -> (code, paths
+        (B, S, M) = mean + C xi, logml, info, sinfo); C the Cholesky factor of the posterior covariance (+ noise) + jitter_rel x
+        its mean diagonal.  A fit whose matrix is not positive definite gets NaN paths and its 1-based pivot in sinfo; code is
+        the 1-based index of the first such fit."""
+        X, y, Xs, theta = _d(X), _d(y), _d(Xs), _d(theta)
+        B, N, d = X.shape
+        M = Xs.shape[1]
+        xi = _d(xi).reshape(B, -1, M)
+        S = xi.shape[1]
+        out, logml = np.empty((B, S, M)), np.empty(B)
+        info, sinfo = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_fit_sample_batch(self.h, B, N, d, M, kernel_id, _p(X), _p(y), _p(Xs), _p(theta),
+                                                     theta.shape[1], int(include_noise), S, _p(xi), float(jitter_rel), _p(out),
+                                                     _p(logml), info.ctypes.data_as(_ip), sinfo.ctypes.data_as(_ip)))
+        return rc, out, logml, info, sinfo
+
+    def fit_sample_batch_device(self, B, N, d, M, kernel_id, dX, dy, dXs, dtheta, djitter, include_noise, S, dxi, jitter_rel,
+                                dout, dlogml, dinfo, dsinfo, stream=0):
+        return self._chk(self.lib.cgp_fit_sample_batch_device(self.h, B, N, d, M, kernel_id, dX, dy, dXs, dtheta,
+                                                              djitter or None, int(include_noise), S, dxi, float(jitter_rel),
+                                                              dout, dlogml, dinfo, dsinfo or None, ctypes.c_void_p(stream)))
+
+    def predict_cov(self, Xs, include_noise=True):
+        """After fit / optimize: mean (M,) and the full posterior covariance (M, M), m.predict(Xs, full_cov=True)."""
+        Xs = _d(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs[:, None]
+        M = Xs.shape[0]
+        mean, cov = np.empty(M), np.empty((M, M))
+        self._chk(self.lib.cgp_predict_cov(self.h, _p(Xs), M, int(include_noise), _p(mean), _p(cov)))
+        return mean, cov
+
+    def sample(self, Xs, xi, include_noise=False, jitter_rel=1e-6):
+        """After fit / optimize: sample paths (S, M) = mean + C xi, m.posterior_samples_f with the caller's normals xi (S, M);
+        returns (paths, pivot): pivot != 0 (and NaN paths) when the matrix is not positive definite."""
+        Xs = _d(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs[:, None]
+        M = Xs.shape[0]
+        xi = _d(xi).reshape(-1, M)
+        S = xi.shape[0]
+        out, info = np.empty((S, M)), np.zeros(1, dtype=np.int32)
+        self._chk(self.lib.cgp_sample(self.h, _p(Xs), M, S, _p(xi), int(include_noise), float(jitter_rel), _p(out),
+                                      info.ctypes.data_as(_ip)))
+        return out, int(info[0])
 
     # -- sliding windows (BASELINE configs[3]) ----------------------------------------------------
     def window_init(self, nwin, N, d, kernel_id, theta):

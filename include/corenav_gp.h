@@ -216,6 +216,69 @@ int cgp_fit_predict_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, i
                                  const double *djitter, int include_noise, void *dmean, void *dvar,
                                  double *dlogml, int *dinfo, void *hip_stream);
 
+/* ---- joint forecast after batch / single fits: full posterior covariance and sample paths ----------
+ * The calls above answer with the marginals.  The reference's model also offers the JOINT posterior at its test points --
+ * m.predict(Xnew, full_cov=True) and m.posterior_samples_f(Xnew, size) -- which a Monte-Carlo trajectory ensemble needs: one
+ * realisation of the whole slip curve per member, correlated from tick to tick.  After a tiled fit the factor panel holds
+ * V^T = (L^-1 K*)^T beside L, so the covariance is one more pass over resident rows, no second solve:
+ *   cov = K(Xs, Xs) - V^T V        N M^2 flops per fit (lower triangle) on the fp64 matrix cores
+ * CGP_F64 contexts only: every entry point of this section returns CGP_EINVAL in a CGP_F32 context before anything is enqueued
+ * (a covariance formed by cancellation in single precision is not something to promise).  All five kernel ids.  Every shape
+ * takes the tiled schedules here (the one-launch short-window kernel leaves no V^T behind), so for N <= 144 / 160 mean and
+ * diag(cov) agree with cgp_fit_predict_batch to rounding; beyond, they are bitwise its mean / var: among the tiled schedules a
+ * joint call takes the one the marginal call of its size takes, and adds launches after it.  A fit's covariance and paths are a
+ * function of its own data and of that schedule only: never of its slot or its neighbours, and of the size of the call exactly as
+ * far as mean / var are -- bitwise the same among the mid-size and fused schedules (a lone fit of N > 2560 up to 511 fits), to
+ * rounding (1e-9) against a call small enough for the latency schedule, which sums a tile's inner dimension in ranges.
+ *
+ * cgp_joint_reserve: scratch for the posterior covariance / its factor of up to max_batch fits at up to max_m test points:
+ * max_batch x mpad^2 doubles, mpad = max_m rounded up to 16 (512 x 599: 1.5 GB -- the caller decides).  1 <= max_batch <= the
+ * context's, 1 <= max_m <= min(the context's max_m, 1024), else CGP_EINVAL; CGP_ENOMEM leaves no reservation; calling it again
+ * replaces the reservation.  Blocks (it synchronises the device).  Without a reservation the calls below return CGP_ESTATE, for
+ * a batch or an M beyond it CGP_ECAPACITY; M < 1 and NULL pointers are CGP_EINVAL. */
+int cgp_joint_reserve(cgp_ctx *ctx, int max_batch, int max_m);
+/* cgp_fit_predict_cov_batch: arguments, status words, jitter ladder and return value as cgp_fit_predict_batch, with
+ * cov (batch, M, M) row-major in place of var.  Both triangles are written and exactly equal.  mean and diag(cov) are the fit's
+ * own mean / var: the diagonal is clipped at 1e-15 and include_noise != 0 adds sigma_n^2 to the DIAGONAL only (GPy's
+ * predict(full_cov=True, include_likelihood=True)).  A fit whose info stays non-zero has NaN in all of its covariance; the
+ * other fits of the call are unaffected.  Blocks. */
+int cgp_fit_predict_cov_batch(cgp_ctx *ctx, int batch, int N, int d, int M, int kernel_id,
+                              const double *X, const double *y, const double *Xs, const double *theta,
+                              int theta_stride, int include_noise, double *mean, double *cov,
+                              double *logml, int *info);
+/* Device-resident variant: pointers as cgp_fit_predict_batch_device (fp64), dcov (batch, M, M) in place of dvar (the variance
+ * stays in the context).  The fit schedule plus one launch, enqueued on hip_stream; no allocation, no synchronisation, no
+ * jitter ladder (capturable into a hipGraph).  A fit with dinfo != 0 has NaN in all of its covariance. */
+int cgp_fit_predict_cov_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, int kernel_id,
+                                     const double *dX, const double *dy, const double *dXs, const double *dtheta,
+                                     const double *djitter, int include_noise, double *dmean, double *dcov,
+                                     double *dlogml, int *dinfo, void *hip_stream);
+/* cgp_fit_sample_batch: the fits of cgp_fit_predict_cov_batch and S sample paths of each, out (batch, S, M) = mean + C xi,
+ * where C is the lower Cholesky factor of
+ *   A = cov_latent (+ sigma_n^2 I when include_noise)  +  jitter_rel * mean(diag(cov_latent (+ sigma_n^2 I))) * I
+ * and xi (batch, S, M) are standard normals SUPPLIED BY THE CALLER: the library holds no random state.  Definition, argument
+ * rules and failure rule are cgp_window_sample's: jitter_rel >= 0 (pass 1e-6 unless you know better), no ladder on THIS
+ * factorisation -- a fit whose A is not positive definite gets NaN paths and sinfo[b] = the 1-based failing pivot (a fit whose
+ * info != 0 reports pivot 1); the fits themselves run the jitter ladder as cgp_fit_predict_batch does.  logml, info, sinfo may be
+ * NULL.  The dense covariance is never written to the caller.  Returns a negative error, else 0 or the 1-based index of the
+ * first fit whose paths are NaN.  Blocks. */
+int cgp_fit_sample_batch(cgp_ctx *ctx, int batch, int N, int d, int M, int kernel_id,
+                         const double *X, const double *y, const double *Xs, const double *theta,
+                         int theta_stride, int include_noise, int S, const double *xi, double jitter_rel,
+                         double *out, double *logml, int *info, int *sinfo);
+/* Device-resident variant: the fit schedule plus three launches on hip_stream, no allocation, no synchronisation (capturable
+ * into a hipGraph); dxi / dout (batch, S, M), dsinfo (batch ints) may be NULL.  Mean and variance stay in the context. */
+int cgp_fit_sample_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, int kernel_id,
+                                const double *dX, const double *dy, const double *dXs, const double *dtheta,
+                                const double *djitter, int include_noise, int S, const double *dxi, double jitter_rel,
+                                double *dout, double *dlogml, int *dinfo, int *dsinfo, void *hip_stream);
+/* After cgp_fit / cgp_optimize, the literal m.predict(Xs, full_cov=True) and m.posterior_samples_f(Xs, S): Xs (M, d),
+ * mean (M), cov (M, M), xi / out (S, M); mean and diag(cov) are bitwise cgp_predict's.  The resident fit is not modified.
+ * cgp_sample returns 0 or 1 (info: the failing pivot, may be NULL); CGP_ESTATE also without a successful fit.  Block. */
+int cgp_predict_cov(cgp_ctx *ctx, const double *Xs, int M, int include_noise, double *mean, double *cov);
+int cgp_sample(cgp_ctx *ctx, const double *Xs, int M, int S, const double *xi, int include_noise, double jitter_rel,
+               double *out, int *info);
+
 /* ---- multi-device sweep (SURVEY.md 8b "cgp_fit_predict_batch(ctx[], ...)", 8e) --------------------
  * One engine context and one host thread per listed device; a batch of independent windows is cut into
  * contiguous per-device blocks (device i gets fits [start_i, stop_i), the first batch % ndev devices
