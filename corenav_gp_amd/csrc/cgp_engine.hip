@@ -7,10 +7,12 @@
 #include "cgp_window.hpp"
 #include "cgp_window_forecast.hpp"
 #include "cgp_window_adapt.hpp"
+#include "cgp_window_loo.hpp"
 #include "cgp_window_joint.hpp"
 #include "cgp_joint.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
+#include "cgp_loo.hpp"
 #include "cgp_refine.hpp"
 #include "gp_predictor_core.hpp"
 #include "gp_predictor.h"
@@ -2807,4 +2809,153 @@ extern "C" int cgp_optimize_batch(cgp_ctx *c, int batch, int N, int d, int kid, 
     if (n_evals) n_evals[b] = r.evals;
   }
   return CGP_OK;
+}
+
+// ---- leave-one-out cross-validation from the factor (cgp_loo.hpp; fp64 contexts) -------------------------------------------
+namespace {
+struct LooOut {   // device pointers at the first fit of the call; each may be null
+  double *mean, *var, *lpd, *sum;
+};
+
+// Gradient-mode factorisation of `nfit` fits into slabs 0 .. nfit - 1 (grad_eval_batch's arguments: xid = 1, M = N, the tiled
+// schedules for every shape), then k_loo on Wt and alpha instead of k_grad, then the per-fit sums.  All on s, nothing allocated,
+// nothing synchronised.  dvar is free once k_finalize has run: it holds loo_lpd for k_loo_sum when the caller wants no loo_lpd.
+int loo_enqueue(cgp_ctx *c, int nfit, int N, int d, int kid, const double *dX, const double *dy, const double *dtheta,
+                const double *djitter, const LooOut &o, double *dlogml, int *dinfo, hipStream_t s) {
+  FitArgs a = base_args(c, N, d, /*M=*/N, kid, 0);
+  a.xid = 1;
+  a.X = dX;
+  a.Xs = dX;  // unused: the "test rows" are the identity
+  a.y = dy;
+  a.theta = dtheta;
+  a.jitter = djitter;
+  a.mean = c->dmean;
+  a.var = c->dvar;
+  a.logml = dlogml;
+  a.info = dinfo;
+  a.gpart = c->dgpart;
+  int rc = run(c, a, nfit, true, true, s);
+  if (rc != CGP_OK) return rc;
+  double *lpd = o.lpd ? o.lpd : static_cast<double *>(c->dvar);
+  hipLaunchKernelGGL(k_loo, dim3(cdiv(N, LOO_EB), nfit), dim3(LOO_WAVES * 64), 0, s, a, o.mean, o.var, lpd);
+  if (o.sum) hipLaunchKernelGGL(k_loo_sum, dim3(nfit), dim3(64), 0, s, lpd, dinfo, N, o.sum);
+  HIP_TRY(c, hipGetLastError());
+  return CGP_OK;
+}
+
+// Host buffers: the windows to slots 0 .. batch - 1 (cgp_optimize_batch's upload), one batched call, then GPy's jitter ladder
+// for the fits that failed, one fit at a time in slab 0 (cgp_fit_predict_batch's policy); LOO of a retried fit is computed on the
+// Ky that finally factored.  jit_out (batch) receives the jitter each fit ended with.
+int loo_batch_host(cgp_ctx *c, int batch, int N, int d, int kid, const double *X, const double *y, const double *theta,
+                   int theta_stride, double *loo_mean, double *loo_var, double *loo_lpd, double *lpd_sum, double *logml, int *info,
+                   double *jit_out) {
+  const int nth = ntheta(kid, d);
+  hipStream_t s = c->stream;
+  const size_t B = batch, BN = B * N;
+  c->have_fit = false;
+  c->lazy_fit = false;
+  if (!grow_device(c->draw, c->draw_cap, (3 * BN + B) * sizeof(double))) return CGP_ENOMEM;
+  double *dout = static_cast<double *>(c->draw);
+  const LooOut o{loo_mean ? dout : nullptr, loo_var ? dout + BN : nullptr, loo_lpd ? dout + 2 * BN : nullptr,
+                 lpd_sum ? dout + 3 * BN : nullptr};
+  std::vector<char> hx(BN * d * sizeof(double)), hy(BN * sizeof(double));
+  for (int b = 0; b < batch; ++b) {
+    pack_soa(X + (size_t)b * N * d, N, d, CGP_F64, hx, (size_t)b * d * N);
+    pack_vec(y + (size_t)b * N, N, CGP_F64, hy, (size_t)b * N);
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->dX, hx.data(), hx.size(), hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(c->dy, hy.data(), hy.size(), hipMemcpyHostToDevice, s));
+  std::vector<double> hth;
+  int rc = upload_theta(c, theta, theta_stride, nth, batch, s, hth);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->djitter, 0, sizeof(double) * batch, s));
+  const double *dX = static_cast<const double *>(c->dX), *dy = static_cast<const double *>(c->dy);
+  rc = loo_enqueue(c, batch, N, d, kid, dX, dy, c->dtheta, c->djitter, o, c->dlogml, c->dinfo, s);
+  if (rc != CGP_OK) return rc;
+  std::vector<int> hinfo(batch);
+  HIP_TRY(c, hipMemcpyAsync(hinfo.data(), c->dinfo, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  for (int b = 0; b < batch; ++b) {
+    jit_out[b] = 0.0;
+    if (hinfo[b] == 0) continue;
+    double jit = mean_diag(kid, theta + (size_t)b * theta_stride, d, X + (size_t)b * N * d, N) * 1e-6;
+    for (int attempt = 0; attempt < 5 && hinfo[b] != 0; ++attempt, jit *= 10.0) {
+      HIP_TRY(c, hipMemcpyAsync(c->djitter + b, &jit, sizeof(double), hipMemcpyHostToDevice, s));
+      const size_t off = (size_t)b * N;
+      const LooOut ob{o.mean ? o.mean + off : nullptr, o.var ? o.var + off : nullptr, o.lpd ? o.lpd + off : nullptr,
+                      o.sum ? o.sum + b : nullptr};
+      rc = loo_enqueue(c, 1, N, d, kid, dX + off * d, dy + off, c->dtheta + (size_t)b * CGP_MAX_THETA, c->djitter + b, ob,
+                       c->dlogml + b, c->dinfo + b, s);
+      if (rc != CGP_OK) return rc;
+      HIP_TRY(c, hipMemcpyAsync(&hinfo[b], c->dinfo + b, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipStreamSynchronize(s));
+      if (hinfo[b] == 0) jit_out[b] = jit;
+    }
+  }
+  if (loo_mean) HIP_TRY(c, hipMemcpyAsync(loo_mean, o.mean, BN * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (loo_var) HIP_TRY(c, hipMemcpyAsync(loo_var, o.var, BN * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (loo_lpd) HIP_TRY(c, hipMemcpyAsync(loo_lpd, o.lpd, BN * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (lpd_sum) HIP_TRY(c, hipMemcpyAsync(lpd_sum, o.sum, B * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (logml) HIP_TRY(c, hipMemcpyAsync(logml, c->dlogml, B * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  int first = 0;
+  for (int b = 0; b < batch; ++b) {
+    if (info) info[b] = hinfo[b];
+    if (first == 0 && hinfo[b] != 0) first = hinfo[b];
+  }
+  return first;
+}
+
+int loo_check(const cgp_ctx *c, int batch, int N, int d, int kid) {
+  if (!c || c->dtype != CGP_F64) return CGP_EINVAL;   // alpha_i / kd_i cancels against y_i: not promised in single precision
+  return check_shape(c, batch, N, d, N, kid);
+}
+}  // namespace
+
+extern "C" int cgp_loo_batch_device(cgp_ctx *c, int batch, int N, int d, int kid, const double *dX, const double *dy,
+                                    const double *dtheta, const double *djitter, double *dloo_mean, double *dloo_var,
+                                    double *dloo_lpd, double *dlpd_sum, double *dlogml, int *dinfo, void *hip_stream) {
+  int rc = loo_check(c, batch, N, d, kid);
+  if (rc != CGP_OK) return rc;
+  if (!dX || !dy || !dtheta || !dlogml || !dinfo) return CGP_EINVAL;
+  if (!dloo_mean && !dloo_var && !dloo_lpd && !dlpd_sum) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  c->have_fit = false;
+  c->lazy_fit = false;
+  return loo_enqueue(c, batch, N, d, kid, dX, dy, dtheta, djitter, LooOut{dloo_mean, dloo_var, dloo_lpd, dlpd_sum}, dlogml, dinfo,
+                     pick_stream(c, hip_stream));
+}
+
+extern "C" int cgp_loo_batch(cgp_ctx *c, int batch, int N, int d, int kid, const double *X, const double *y, const double *theta,
+                             int theta_stride, double *loo_mean, double *loo_var, double *loo_lpd, double *lpd_sum, double *logml,
+                             int *info) {
+  int rc = loo_check(c, batch, N, d, kid);
+  if (rc != CGP_OK) return rc;
+  if (!X || !y || !theta || theta_stride < ntheta(kid, d)) return CGP_EINVAL;
+  if (!loo_mean && !loo_var && !loo_lpd && !lpd_sum) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<double> jit(batch);
+  return loo_batch_host(c, batch, N, d, kid, X, y, theta, theta_stride, loo_mean, loo_var, loo_lpd, lpd_sum, logml, info, jit.data());
+}
+
+extern "C" int cgp_loo(cgp_ctx *c, const double *X, const double *y, int N, int d, int kid, const double *theta, double *loo_mean,
+                       double *loo_var, double *loo_lpd, double *lpd_sum) {
+  int rc = loo_check(c, 1, N, d, kid);
+  if (rc != CGP_OK) return rc;
+  if (!X || !y || !theta) return CGP_EINVAL;
+  if (!loo_mean && !loo_var && !loo_lpd && !lpd_sum) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int nth = ntheta(kid, d);
+  int info = 0;
+  double jit = 0.0;
+  rc = loo_batch_host(c, 1, N, d, kid, X, y, theta, nth, loo_mean, loo_var, loo_lpd, lpd_sum, nullptr, &info, &jit);
+  if (rc < 0) return rc;
+  // the factor panel of slab 0, alpha, the window, theta and the jitter are resident: fitted, as after cgp_nll_grad
+  c->fjitter = jit;
+  c->have_fit = (info == 0);
+  c->fN = N;
+  c->fd = d;
+  c->fkernel = kid;
+  memcpy(c->ftheta, theta, sizeof(double) * nth);
+  return info;
 }

@@ -681,6 +681,48 @@ extern "C" int cgp_window_nll_grad(cgp_ctx *c, double *nll, double *grad, int gr
   return CGP_OK;
 }
 
+// Leave-one-out cross-validation of the windows as they stand (cgp_window_loo.hpp): the gradient's first two launches, then the
+// forward half of its substitution and the finish.  Alpha and the chunks' partial sums live where the gradient keeps alpha and
+// its partial sums (winbuf[7]: one double per chunk against the gradient's GRAD_N).
+extern "C" int cgp_window_loo_device(cgp_ctx *c, double *dloo_mean, double *dloo_var, double *dloo_lpd, double *dlpd_sum,
+                                     void *hip_stream) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (!dloo_mean && !dloo_var && !dloo_lpd && !dlpd_sum) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  const AdaptArgs a = adapt_args(c);
+  const WindowLooOut out{dloo_mean, dloo_var, dloo_lpd, dlpd_sum, a.gpart};
+  const ForecastArgs f = forecast_args(c);   // k_window_diag_inv reads the windows and writes the inverses only
+  const long long chunks = (long long)c->nwin * a.NB;
+  if (chunks > (1ll << 30)) return CGP_EINVAL;
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, f);
+  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, a);
+  hipLaunchKernelGGL(k_window_loo, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a, out);
+  hipLaunchKernelGGL(k_window_loo_finish, dim3(c->nwin), dim3(64), 0, ws, a, out);
+  if (!hip_ok(c, hipGetLastError(), "window LOO launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_loo(cgp_ctx *c, double *loo_mean, double *loo_var, double *loo_lpd, double *lpd_sum) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (!loo_mean && !loo_var && !loo_lpd && !lpd_sum) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t W = c->nwin, WN = W * c->win.N, ndbl = 3 * WN + W;
+  double *h, *d;
+  if (!window_stage(c, ndbl * 8, ndbl * 8, h, d)) return CGP_ENOMEM;
+  hipStream_t s = c->stream;
+  int rc = cgp_window_loo_device(c, loo_mean ? d : nullptr, loo_var ? d + WN : nullptr, loo_lpd ? d + 2 * WN : nullptr,
+                                 lpd_sum ? d + 3 * WN : nullptr, s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h, d, ndbl * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (loo_mean) memcpy(loo_mean, h, WN * sizeof(double));
+  if (loo_var) memcpy(loo_var, h + WN, WN * sizeof(double));
+  if (loo_lpd) memcpy(loo_lpd, h + 2 * WN, WN * sizeof(double));
+  if (lpd_sum) memcpy(lpd_sum, h + 3 * WN, W * sizeof(double));
+  return CGP_OK;
+}
+
 // m.optimize() on the resident windows: cgp_optimize_batch's host loop (one batched evaluation per round, every window its own
 // LbfgsStepper and line search) with set_theta + nll_grad on the windows themselves as the evaluation.
 extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,

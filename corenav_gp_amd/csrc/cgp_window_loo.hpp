@@ -1,0 +1,136 @@
+// cgp_window_loo.hpp -- leave-one-out cross-validation of the resident sliding windows (cgp_window_loo), from the factor, z,
+// the inputs and the targets as they stand after any number of pushes (formulas: cgp_loo.hpp).
+//
+//   k_window_loo          One WAVE = one window x one chunk of 16 columns [c0, c0 + 16), k_window_kinv_grad's work unit, and its
+//                         forward half only: V = L^-1 E for the chunk (rows above the chunk are zero: the substitution starts at
+//                         the chunk's own block) with k_window_diag_inv's inverses, L(I, K) the A operand read down the slab's
+//                         columns, on v_mfma_f64_16x16x4_f64.  V lives where k_window_kinv_grad keeps it, transposed in the
+//                         chunk's tile row of the slab's strict upper triangle (the lower triangle, the diagonal, z, the samples
+//                         and the state words are NOT written).  The 16 column sums of squares are kd = diag(Ky^-1) of the
+//                         chunk's samples; with k_window_alpha's alpha and yw the wave writes its 16 entries of loo_mean /
+//                         loo_var / loo_lpd at the window-order index (0 = oldest sample) and one partial sum of loo_lpd.
+//   k_window_loo_finish   per window: the chunks' partial sums added in chunk order (no atomics); NaN for the entries [n, N) of a
+//                         window still filling; NaN everywhere (sum included) for a failed window; NaN rows and sum 0 for an
+//                         empty one.
+// Origin and size come from the window's state words: no host mirror, nothing depends on the slot.
+#pragma once
+#include "cgp_window_adapt.hpp"
+
+namespace cgp {
+
+struct WindowLooOut {
+  double *mean, *var, *lpd;   // [nwin][N], each may be null
+  double *sum;                // [nwin] or null
+  double *part;               // [nwin][NB] the chunks' partial sums of loo_lpd (scratch)
+};
+
+__global__ __launch_bounds__(256) void k_window_loo(AdaptArgs p, WindowLooOut out) {
+  typedef double d4 __attribute__((ext_vector_type(4)));
+  const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const long long gid = (long long)blockIdx.x * 4 + wave;
+  if (gid >= (long long)p.nwin * p.NB) return;
+  const int w = (int)(gid / p.NB), J = (int)(gid - (long long)w * p.NB);
+  const int CAP = p.CAP;
+  const int o = p.state[w * 4], n = p.state[w * 4 + 1], bad = p.state[w * 4 + 2];
+  const int nb = (n + WPB - 1) / WPB;
+  if (bad != 0 || J >= nb) {
+    if (lane == 0) out.part[(size_t)w * p.NB + J] = 0.0;
+    return;
+  }
+  double *S = p.L + (size_t)w * CAP * CAP + (size_t)o * CAP + o;   // the window's (0, 0): lower triangle read, strict upper triangle scratch
+  const double *dinv = p.dinv + (size_t)w * p.NB * (WPB * WPB);
+  const int J0 = J * WPB;
+  const int gj = J0 + l15;
+  const bool colok = gj < n;
+  // V(J) = L(J, J)^-1 stays in registers: register r = rows lq + 4 r, column l15
+  d4 VJ;
+  double ss = 0.0;   // this lane's share of column l15's sum of squares
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    VJ[r] = dinv[(size_t)J * (WPB * WPB) + l15 * WPB + lq + 4 * r];
+    if (J0 + lq + 4 * r < n && colok) ss = __builtin_fma(VJ[r], VJ[r], ss);   // rows past the window are identity rows: not counted
+  }
+  double *Sc = S + J0 + l15;   // + row * CAP: element (row, chunk column l15) of V, transposed into the chunk's tile row
+
+  // ---- forward: V(I) = L(I, I)^-1 (- sum_{J <= K < I} L(I, K) V(K))
+  for (int I = J + 1; I < nb; ++I) {
+    const int rowI = I * WPB + l15;
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 2
+    for (int K = J; K < I; ++K) {
+      const int k0 = K * WPB + lq;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const double a = rowI < n ? -S[(size_t)(k0 + 4 * ks) * CAP + rowI] : 0.0;
+        double b;
+        if (K == J) b = VJ[ks];
+        else b = colok ? Sc[(size_t)(k0 + 4 * ks) * CAP] : 0.0;
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+      }
+    }
+    d4 v = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const double di = dinv[(size_t)I * (WPB * WPB) + (lq + 4 * r) * WPB + l15];
+      v = __builtin_amdgcn_mfma_f64_16x16x4f64(di, acc[r], v, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = I * WPB + lq + 4 * r;
+      if (row < n && colok) {
+        Sc[(size_t)row * CAP] = v[r];
+        ss = __builtin_fma(v[r], v[r], ss);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // later steps of this wave read what other lanes stored
+  }
+
+  // ---- kd of column l15: the four row groups' shares (fixed order), then this sample's three outputs
+  ss += __shfl_xor(ss, 16);
+  ss += __shfl_xor(ss, 32);
+  const double nan = __builtin_nan("");
+  double m = nan, v = nan, l = 0.0;
+  if (colok) {
+    const double al = p.alpha[(size_t)w * p.NB * WPB + gj];
+    const double ye = p.yw[(size_t)w * CAP + o + gj];
+    v = 1.0 / ss;
+    const double r = al * v;   // y_j - loo_mean_j
+    m = ye - r;
+    l = -0.5 * log(6.283185307179586476925286766559 * v) - 0.5 * r * al;
+  }
+  double ls = l;   // columns past the window add 0
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) ls += __shfl_xor(ls, off);
+  if (lq == 0 && colok) {
+    const size_t oi = (size_t)w * p.N + gj;
+    if (out.mean) out.mean[oi] = m;
+    if (out.var) out.var[oi] = v;
+    if (out.lpd) out.lpd[oi] = l;
+  }
+  if (lane == 0) out.part[(size_t)w * p.NB + J] = ls;
+}
+
+__global__ __launch_bounds__(64) void k_window_loo_finish(AdaptArgs p, WindowLooOut out) {
+  const int w = blockIdx.x, lane = threadIdx.x;
+  const int n = p.state[w * 4 + 1], bad = p.state[w * 4 + 2];
+  const double nan = __builtin_nan("");
+  const int first = (bad != 0 || n <= 0) ? 0 : n;   // entries [first, N) hold no sample (or the window failed)
+  for (int i = first + lane; i < p.N; i += 64) {
+    const size_t oi = (size_t)w * p.N + i;
+    if (out.mean) out.mean[oi] = nan;
+    if (out.var) out.var[oi] = nan;
+    if (out.lpd) out.lpd[oi] = nan;
+  }
+  if (lane != 0 || !out.sum) return;
+  double s = 0.0;
+  if (bad != 0) {
+    s = nan;
+  } else if (n > 0) {
+    const int nb = (n + WPB - 1) / WPB;
+    for (int J = 0; J < nb; ++J) s += out.part[(size_t)w * p.NB + J];
+  }
+  out.sum[w] = s;
+}
+
+}  // namespace cgp

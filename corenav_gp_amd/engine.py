@@ -64,6 +64,9 @@ _SIGS = {
     "cgp_last_jitter": (ctypes.c_double, [_vp]),
     "cgp_nll_grad": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]),
     "cgp_optimize": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _dp, _ip]),
+    "cgp_loo": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "cgp_loo_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "cgp_loo_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 11),
     "cgp_slip_node_callback_opt": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp,
                                                   ctypes.c_int, _ip]),
     "cgp_slip_node_callback": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
@@ -100,6 +103,8 @@ _SIGS = {
     "cgp_window_set_theta_device": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "cgp_window_nll_grad": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int]),
     "cgp_window_nll_grad_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp]),
+    "cgp_window_loo": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    "cgp_window_loo_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cgp_window_optimize": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, ctypes.c_int, _dp, _ip]),
     "cgp_set_streams": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_set_refine": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -261,6 +266,40 @@ class Context:
         self._n = X.shape[0]
         return nll.value, grad
 
+    def loo(self, X, y, kernel_id, theta):
+        """Leave-one-out cross-validation of one window in closed form (fp64 contexts): (loo_mean, loo_var, loo_lpd), each
+        (N,), and lpd_sum.  Leaves the context fitted at theta, like nll_grad."""
+        X = _d(X)
+        if X.ndim == 1:
+            X = X[:, None]
+        y, theta = _d(y).reshape(-1), _d(theta)
+        N = X.shape[0]
+        mean, var, lpd, tot = np.empty(N), np.empty(N), np.empty(N), ctypes.c_double(0.0)
+        rc = self._chk(self.lib.cgp_loo(self.h, _p(X), _p(y), N, X.shape[1], kernel_id, _p(theta), _p(mean), _p(var), _p(lpd),
+                                        ctypes.byref(tot)))
+        if rc > 0:
+            raise CgpError(rc)
+        self._n = N
+        return mean, var, lpd, tot.value
+
+    def loo_batch(self, X, y, theta, kernel_id):
+        """Batched LOO: X (B, N, d), y (B, N), theta (B, nth) -> (rc, loo_mean, loo_var, loo_lpd (B, N), lpd_sum, logml, info
+        (B,)); a fit that stays not positive definite through the jitter ladder has NaN rows and a non-zero info."""
+        X, y, theta = _d(X), _d(y), _d(theta)
+        B, N, d = X.shape
+        mean, var, lpd = np.empty((B, N)), np.empty((B, N)), np.empty((B, N))
+        tot, logml, info = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_loo_batch(self.h, B, N, d, kernel_id, _p(X), _p(y), _p(theta), theta.shape[1], _p(mean),
+                                              _p(var), _p(lpd), _p(tot), _p(logml), info.ctypes.data_as(_ip)))
+        return rc, mean, var, lpd, tot, logml, info
+
+    def loo_batch_device(self, B, N, d, kernel_id, dX, dy, dtheta, djitter, dloo_mean, dloo_var, dloo_lpd, dlpd_sum, dlogml,
+                         dinfo, stream=0):
+        """Device pointers (ints, fit_predict_batch_device's layout, fp64) on a caller stream; 0 for an output not wanted."""
+        return self._chk(self.lib.cgp_loo_batch_device(self.h, B, N, d, kernel_id, dX, dy, dtheta, djitter or None,
+                                                       dloo_mean or None, dloo_var or None, dloo_lpd or None, dlpd_sum or None,
+                                                       dlogml, dinfo, ctypes.c_void_p(stream)))
+
     def optimize(self, X, y, kernel_id, theta0, max_evals=1000):
         """GPy m.optimize() equivalent; returns (theta_opt, logml, n_evals)."""
         X = _d(X)
@@ -420,6 +459,7 @@ class Context:
             theta = np.tile(theta, (nwin, 1))
         self._win = (nwin, d)
         self._win_nth = ntheta(kernel_id, d)
+        self._win_n = N
         self._chk(self.lib.cgp_window_init(self.h, nwin, N, d, kernel_id, _p(theta), theta.shape[1]))
 
     def window_push(self, xs, ys, include_noise=True, check=True):
@@ -545,6 +585,18 @@ class Context:
 
     def window_nll_grad_device(self, dnll, dgrad, grad_stride, stream=0):
         return self._chk(self.lib.cgp_window_nll_grad_device(self.h, dnll, dgrad, grad_stride, ctypes.c_void_p(stream)))
+
+    def window_loo(self):
+        """Leave-one-out cross-validation of every window as it stands: (loo_mean, loo_var, loo_lpd (nwin, N), lpd_sum (nwin,)),
+        rows in the window's own order (oldest sample first), NaN past the samples a window holds."""
+        nwin, N = self._win[0], self._win_n
+        mean, var, lpd, tot = np.empty((nwin, N)), np.empty((nwin, N)), np.empty((nwin, N)), np.empty(nwin)
+        self._chk(self.lib.cgp_window_loo(self.h, _p(mean), _p(var), _p(lpd), _p(tot)))
+        return mean, var, lpd, tot
+
+    def window_loo_device(self, dloo_mean, dloo_var, dloo_lpd, dlpd_sum, stream=0):
+        return self._chk(self.lib.cgp_window_loo_device(self.h, dloo_mean or None, dloo_var or None, dloo_lpd or None,
+                                                        dlpd_sum or None, ctypes.c_void_p(stream)))
 
     def window_optimize(self, max_evals=1000, select=None, nth=None):
         """m.optimize() on the resident windows, started at the theta each holds: (theta (nwin, nth), logml, n_evals);

@@ -177,6 +177,49 @@ typedef double (*cgp_objective_fn)(const double *x, double *grad, int n, void *u
 int cgp_lbfgs_minimize(cgp_objective_fn fn, void *user, double *x_inout, int n, int max_evals, double pgtol, double factr,
                        double *f_out, int *n_evals, int *n_iters, int *status);
 
+/* ---- leave-one-out cross-validation from the factor (fp64 contexts) ------------------------------------
+ * How well a fitted model explains its own samples, one sample at a time: GPy's inference_method.LOO(kern, X, Y, likelihood,
+ * posterior), i.e. Rasmussen & Williams eq. 5.10-5.12, in closed form from what an exact fit already has:
+ *     Ky = K + (sigma_n^2 + 1e-8 [+ jitter]) I,   alpha = Ky^-1 y,   kd_i = [Ky^-1]_ii
+ *     loo_var_i  = 1 / kd_i                 predictive variance of the NOISY y_i given all other samples
+ *     loo_mean_i = y_i - alpha_i / kd_i
+ *     loo_lpd_i  = -0.5 log(2 pi loo_var_i) - 0.5 (y_i - loo_mean_i)^2 / loo_var_i
+ *     lpd_sum    = sum_i loo_lpd_i          the LOO pseudo-likelihood; higher is better
+ * lpd_sum is the second opinion beside logML when kernels are compared; a strongly negative loo_lpd_i marks an outlier sample.
+ * The fit is a gradient-mode factorisation (cgp_nll_grad's: needs max_m >= N) on the tiled schedules for EVERY shape -- windows
+ * of at most 160 samples included, the one-launch short-window kernel leaves no L^-1 behind -- after which kd is one pass over
+ * (L^-1)^T: N^2 / 2 doubles per fit, no syrk.  All five kernel ids.
+ * Precision: CGP_F64 contexts only; a CGP_F32 context gets CGP_EINVAL before anything is enqueued and stays usable (alpha_i /
+ * kd_i is a cancellation against y_i that single precision does not promise; the joint forecast is fp64-only for the same reason).
+ * Shape errors are the gradient calls': CGP_EINVAL / CGP_ECAPACITY as for cgp_nll_grad / cgp_optimize_batch of the same shape.
+ * loo_mean, loo_var, loo_lpd and lpd_sum may each be NULL; with all four NULL the call returns CGP_EINVAL.
+ * Determinism: a fit's outputs depend on its own data and on the schedule its call size selects, never on its slot or its
+ * neighbours; no atomics, lpd_sum is added in a fixed order.
+ *
+ * cgp_loo: one window, arguments as cgp_nll_grad; loo_mean / loo_var / loo_lpd (N), *lpd_sum.  GPy's jitter ladder as cgp_nll_grad
+ * runs it; LOO is computed on the Ky that finally factored, the jitter included in loo_var (cgp_last_jitter reports it).  Returns
+ * 0, or the fit's positive status with NaN in every output.  Leaves the context fitted at theta: cgp_predict may follow.
+ * Bitwise cgp_loo_batch of that one fit. */
+int cgp_loo(cgp_ctx *ctx, const double *X, const double *y, int N, int d, int kernel_id, const double *theta,
+            double *loo_mean, double *loo_var, double *loo_lpd, double *lpd_sum);
+/* cgp_loo_batch: `batch` windows of identical shape, host buffers: X (batch, N, d), y (batch, N), theta (batch, theta_stride);
+ * loo_mean / loo_var / loo_lpd (batch, N), lpd_sum / logml / info (batch; logml and info may be NULL).  The jitter ladder runs per
+ * fit exactly as in cgp_fit_predict_batch (the fits that failed only, one at a time, mean(diag) 1e-6 10^k, k = 0..4).  A fit whose
+ * info stays non-zero gets NaN in all of its outputs, lpd_sum included; its neighbours are unaffected.  Returns 0 if every fit
+ * succeeded, else the first non-zero per-fit status (the convention of cgp_fit_predict_batch).  Blocks. */
+int cgp_loo_batch(cgp_ctx *ctx, int batch, int N, int d, int kernel_id, const double *X, const double *y,
+                  const double *theta, int theta_stride,
+                  double *loo_mean, double *loo_var, double *loo_lpd, double *lpd_sum, double *logml, int *info);
+/* Device-resident variant, fp64 buffers in cgp_fit_predict_batch_device's layout: dX (batch, d, N), dy (batch, N), dtheta (batch,
+ * CGP_MAX_THETA), djitter (batch) or NULL; dloo_mean / dloo_var / dloo_lpd (batch, N), dlpd_sum (batch), each or NULL; dlogml
+ * (batch) and dinfo (batch) int32 are required.  The fit schedule and two more launches on hip_stream (NULL = legacy default
+ * stream, CGP_STREAM_CTX = the context's own): no allocation, no synchronisation, no ladder -- read dinfo and re-submit the failed
+ * fits with djitter set.  A fit with dinfo != 0 gets NaN. */
+int cgp_loo_batch_device(cgp_ctx *ctx, int batch, int N, int d, int kernel_id, const double *dX, const double *dy,
+                         const double *dtheta, const double *djitter,
+                         double *dloo_mean, double *dloo_var, double *dloo_lpd, double *dlpd_sum,
+                         double *dlogml, int *dinfo, void *hip_stream);
+
 /* ---- the node callback in one call -------------------------------------------------------------
  * Everything gp_slip_node.py:16-63 computes between "GP Input Arrived" and pub.publish(), at fixed
  * theta: first int(0.9 n) samples train (:27-29), grid arange(min, max + 600, 1) (:45), output
@@ -451,6 +494,21 @@ int cgp_window_set_theta_device(cgp_ctx *ctx, const double *dtheta, int theta_st
 int cgp_window_nll_grad(cgp_ctx *ctx, double *nll, double *grad, int grad_stride);
 /* Device-resident variant: four launches on hip_stream, no allocation, no synchronisation (capturable into a hipGraph). */
 int cgp_window_nll_grad_device(cgp_ctx *ctx, double *dnll, double *dgrad, int grad_stride, void *hip_stream);
+/* cgp_window_loo: leave-one-out cross-validation (formulas: the cgp_loo section above) of every resident window as it stands
+ * after the last push, at the theta it holds, from the factor, z, the inputs and the targets; fp64 whatever the context's dtype,
+ * as cgp_window_predict is.  loo_mean / loo_var / loo_lpd (nwin, N) in the window's own order, oldest sample first; lpd_sum
+ * (nwin); each may be NULL, not all four.  Entries [n, N) of a window still filling are NaN; an empty window has all-NaN rows
+ * and lpd_sum = 0; a window that lost positive definiteness has NaN everywhere, lpd_sum included.  One wave per window and 16
+ * samples runs the forward half of cgp_window_nll_grad's substitution (n^3 / 3 flops per window on the fp64 matrix cores), so a
+ * call costs less than the gradient's.  The windows are not modified: the factor (lower triangle and diagonal), z, the
+ * samples and the state words are not written, and a push after the call gives bitwise what it gives without it.  The call uses
+ * the slabs' strict upper triangle and the scratch buffers of cgp_window_predict and cgp_window_nll_grad: it is not to run
+ * concurrently with cgp_window_predict, cgp_window_nll_grad or the joint forecast on other streams of the same context.
+ * Returns CGP_ESTATE without windows, CGP_EINVAL when every output is NULL, else 0.  Blocks. */
+int cgp_window_loo(cgp_ctx *ctx, double *loo_mean, double *loo_var, double *loo_lpd, double *lpd_sum);
+/* Device-resident variant: four launches on hip_stream, no allocation, no synchronisation (capturable into a hipGraph). */
+int cgp_window_loo_device(cgp_ctx *ctx, double *dloo_mean, double *dloo_var, double *dloo_lpd, double *dlpd_sum,
+                          void *hip_stream);
 /* cgp_window_optimize: m.optimize() on the resident windows.  One L-BFGS (the optimiser of cgp_optimize_batch: Logexp-
  * transformed parameters, pgtol 1e-5, factr 1e7, at most max_evals evaluations per window, <= 0 meaning 1000) per selected
  * window, started at the theta the window holds -- every entry must be > 0, else CGP_EINVAL before anything is changed.  One
