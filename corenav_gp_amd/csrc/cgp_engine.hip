@@ -10,6 +10,7 @@
 #include "cgp_window_loo.hpp"
 #include "cgp_window_joint.hpp"
 #include "cgp_joint.hpp"
+#include "cgp_multi.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
 #include "cgp_loo.hpp"
@@ -134,6 +135,13 @@ struct cgp_ctx {
   int fj_max_batch = 0, fj_max_m = 0;
   void *fj_dev = nullptr;
   size_t fj_dev_cap = 0;
+  // multi-target fits (cgp_multi_reserve): Z = L^-1 Y of up to mz_max_batch fits x mz_max_p targets, [fit][NT 128][P padded to 128];
+  // staging of the host call [Y | mean | logml], grown on demand and kept
+  void *mz = nullptr;
+  int mz_max_batch = 0, mz_max_p = 0;
+  int mz_form = 0;   // cgp_multi_set_form: 0 = the engine picks the solve's tile height, 64 / 128 = as told (tests)
+  void *mz_dev = nullptr;
+  size_t mz_dev_cap = 0;
   // cgp_window_push staging, grown on demand and kept: one pinned host block and one device block per direction
   void *win_pin = nullptr, *win_dev = nullptr;
   size_t win_pin_cap = 0, win_dev_cap = 0;
@@ -190,12 +198,18 @@ bool grow_pinned(void *&p, size_t &cap, size_t bytes);
 bool grow_device(void *&p, size_t &cap, size_t bytes);
 void window_free(cgp_ctx *c, bool joint_only);   // cgp_window_host.hpp
 // cgp_joint_host.hpp.  What a joint call adds to a batch of fits: the contraction of the fits' V rows into their covariance slots.
+struct MultiCall;   // cgp_multi_host.hpp: the targets of a multi-target call
 struct JointHook {
   double *dcov;   // output form (batch, M, M) on the device; null: the scratch form for the factorisation
+  const MultiCall *multi = nullptr;   // a multi-target call instead: solve + contraction of the fits' P targets (dcov unused)
 };
 void joint_free(cgp_ctx *c);
 int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, const double *dXs,
                      const double *dtheta, const double *dvar, const int *dinfo, hipStream_t s);
+void multi_free(cgp_ctx *c);
+int multi_hook_launch(cgp_ctx *c, const MultiCall &mc, int N, int M, int slab, int slot, int nfit, hipStream_t s);
+// what the hook of a batch call enqueues for the fits in slabs slab ... into the slots slot ... of the call's arrays
+inline int post_fit_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s);
 
 inline int ntheta(int kid, int d) { return k_ntheta(kid, d); }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -1381,6 +1395,7 @@ void cgp_destroy(cgp_ctx *c) {
     if (e) (void)hipEventDestroy(e);
   window_free(c, false);
   joint_free(c);
+  multi_free(c);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -1538,8 +1553,8 @@ int cgp_fit_predict_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int
                             false);
 }
 
-// jh: a joint call (cgp_joint_host.hpp, fp64).  Tiled schedules for every shape, and every fit's V rows are contracted into its
-// covariance slot while they are still in the panel: the whole batch before the ladder's first retry, a retried fit -- which runs
+// jh: a joint call (cgp_joint_host.hpp, fp64) or a multi-target call (cgp_multi_host.hpp).  Tiled schedules for every shape, and
+// every fit's V rows are contracted (post_fit_launch: into its covariance slot, or with its P solved targets) while they are still in the panel: the whole batch before the ladder's first retry, a retried fit -- which runs
 // as a call of one fit, in slab 0 -- right after its retry.  mean / var may be NULL then (the device copies stay in the context).
 static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, int kid, const double *X, const double *y,
                                   const double *Xs, const double *theta, int theta_stride, int include_noise,
@@ -1641,9 +1656,7 @@ static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, in
                           include_noise, c->dmean, c->dvar, c->dlogml, c->dinfo, CGP_STREAM_CTX, jh != nullptr);
   c->pending_tab = 0;
   if (rc != CGP_OK) return rc;
-  if (jh && (rc = joint_cov_launch(c, *jh, N, d, M, kid, 0, 0, batch, static_cast<const double *>(c->dXs), c->dtheta,
-                                   static_cast<const double *>(c->dvar), c->dinfo, s)) != CGP_OK)
-    return rc;
+  if (jh && (rc = post_fit_launch(c, *jh, N, d, M, kid, 0, 0, batch, s)) != CGP_OK) return rc;
   char *hout = static_cast<char *>(c->pin_out);
   double *hl = reinterpret_cast<double *>(hout + out_elems * esz);
   int *hinfo = reinterpret_cast<int *>(hl + B);
@@ -1679,9 +1692,7 @@ static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, in
           include_noise, (char *)c->dmean + (size_t)b * M * esz, (char *)c->dvar + (size_t)b * M * esz,
           c->dlogml + b, c->dinfo + b, CGP_STREAM_CTX, jh != nullptr);
       if (rc != CGP_OK) return rc;
-      if (jh && (rc = joint_cov_launch(c, *jh, N, d, M, kid, 0, b, 1, static_cast<const double *>(c->dXs), c->dtheta,
-                                       static_cast<const double *>(c->dvar), c->dinfo, s)) != CGP_OK)
-        return rc;
+      if (jh && (rc = post_fit_launch(c, *jh, N, d, M, kid, 0, b, 1, s)) != CGP_OK) return rc;
       HIP_TRY(c, hipMemcpyAsync(&hinfo[b], c->dinfo + b, sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_TRY(c, hipStreamSynchronize(s));
       hjit[b] = jit;
@@ -2478,6 +2489,8 @@ extern "C" int cgp_slip_node_callback_opt(cgp_ctx *c, const double *time_array, 
 #include "cgp_window_host.hpp"
 // joint forecast after batch / single fits: cgp_joint_reserve ... cgp_sample
 #include "cgp_joint_host.hpp"
+// multi-target fits: cgp_multi_reserve ... cgp_fit_predict_multi_batch_device
+#include "cgp_multi_host.hpp"
 
 struct cgp_recorder {
   corenav::SlipWindowRecorder r;

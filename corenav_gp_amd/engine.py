@@ -85,6 +85,12 @@ _SIGS = {
     "cgp_fit_sample_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp, _vp, ctypes.c_int,
                                                                                 ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp,
                                                                                 _vp, _vp]),
+    "cgp_multi_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "cgp_multi_set_form": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "cgp_fit_predict_multi_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_dp, _dp, _dp, _dp, ctypes.c_int,
+                                                                                ctypes.c_int, _dp, _dp, _dp, _ip]),
+    "cgp_fit_predict_multi_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp, _vp, _vp, _vp, _vp,
+                                                                                       ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cgp_predict_cov": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
     "cgp_sample": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_double, _dp, _ip]),
     "cgp_window_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int]),
@@ -427,6 +433,36 @@ class Context:
         return self._chk(self.lib.cgp_fit_sample_batch_device(self.h, B, N, d, M, kernel_id, dX, dy, dXs, dtheta,
                                                               djitter or None, int(include_noise), S, dxi, float(jitter_rel),
                                                               dout, dlogml, dinfo, dsinfo or None, ctypes.c_void_p(stream)))
+
+    # -- multi-target fits: P target columns share one factor (fp64 contexts) ------------------------------
+    def multi_reserve(self, max_batch, max_p):
+        """Scratch for the multi-target calls below (Z = L^-1 Y of up to max_batch fits x max_p targets)."""
+        return self._chk(self.lib.cgp_multi_reserve(self.h, int(max_batch), int(max_p)))
+
+    def multi_set_form(self, rows):
+        """Debug: 64 / 128 forces the tile height of the multi-target solve, 0 gives the choice back to the engine."""
+        return self._chk(self.lib.cgp_multi_set_form(self.h, int(rows)))
+
+    def fit_predict_multi_batch(self, X, Y, Xs, theta, kernel_id, include_noise=True):
+        """X (B, N, d), Y (B, P, N) -- P targets per fit sharing inputs and theta -- Xs (B, M, d), theta (B, nth) ->
+        (rc, mean (B, P, M), var (B, M), logml (B, P), info (B,)).  One factorisation per fit; a fit whose info stays
+        non-zero after the jitter ladder has NaN in all of its outputs."""
+        X, Y, Xs, theta = _d(X), _d(Y), _d(Xs), _d(theta)
+        B, N, d = X.shape
+        P, M = Y.shape[1], Xs.shape[1]
+        mean, var = np.empty((B, P, M)), np.empty((B, M))
+        logml, info = np.empty((B, P)), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_fit_predict_multi_batch(self.h, B, N, d, M, P, kernel_id, _p(X), _p(Y), _p(Xs), _p(theta),
+                                                            theta.shape[1], int(include_noise), _p(mean), _p(var),
+                                                            _p(logml), info.ctypes.data_as(_ip)))
+        return rc, mean, var, logml, info
+
+    def fit_predict_multi_batch_device(self, B, N, d, M, P, kernel_id, dX, dY, dXs, dtheta, djitter, include_noise, dmean,
+                                       dvar, dlogml, dinfo, stream=0):
+        """Device pointers as fit_predict_batch_device; dY (B, P, N), dmean (B, P, M), dvar (B, M), dlogml (B, P)."""
+        return self._chk(self.lib.cgp_fit_predict_multi_batch_device(self.h, B, N, d, M, P, kernel_id, dX, dY, dXs, dtheta,
+                                                                     djitter or None, int(include_noise), dmean, dvar,
+                                                                     dlogml, dinfo, ctypes.c_void_p(stream)))
 
     def predict_cov(self, Xs, include_noise=True):
         """After fit / optimize: mean (M,) and the full posterior covariance (M, M), m.predict(Xs, full_cov=True)."""

@@ -322,6 +322,70 @@ int cgp_predict_cov(cgp_ctx *ctx, const double *Xs, int M, int include_noise, do
 int cgp_sample(cgp_ctx *ctx, const double *Xs, int M, int S, const double *xi, int include_noise, double jitter_rel,
                double *out, int *info);
 
+/* ---- multi-target fits: P target columns share one factor ------------------------------------------
+ * The model the engine restates is GPy.models.GPRegression(X, Y, kernel) with Y (N, P): P independent outputs that share the
+ * inputs, the kernel and the hyper-parameters -- a Monte-Carlo ensemble on a common tick grid, the four wheels' slip series on one
+ * time base.  There is ONE factorisation, ONE predictive variance and one log marginal likelihood term per column.  Per fit, with
+ * Ky = K + (sigma_n^2 + 1e-8 [+ jitter]) I = L L^T:
+ *   Z = L^-1 Y  (N x P)          V = L^-1 K(X, Xs)
+ *   mean[p, m] = sum_i V[i, m] Z[i, p]
+ *   var[m]     = max(k(xs_m, xs_m) - sum_i V[i, m]^2, 1e-15) (+ sigma_n^2 when include_noise)      the fit's own variance
+ *   logml[p]   = -1/2 sum_i Z[i, p]^2 - sum_i log L_ii - N/2 log 2 pi
+ * sum_i log L_ii is read from the factor's diagonal in a fixed order (not recovered from the fit's own logML by subtraction);
+ * sum_p logml[p] is GPy's objective -P/2 log|Ky| - 1/2 tr(Y^T Ky^-1 Y) - N P / 2 log 2 pi.  Against P separate fits the call runs
+ * the fit once and adds N^2 P flops for Z and 2 N M P for the means, on the fp64 matrix cores, from what a tiled fit leaves
+ * resident (L, the images of L(k,k)^-1, V^T).  CGP_F64 contexts only: every entry point of this section returns CGP_EINVAL in a
+ * CGP_F32 context before anything is enqueued, and the context stays usable.  All five kernel ids.  Every shape takes the tiled
+ * schedules (the one-launch short-window kernel leaves no factor behind); among them a call takes the one cgp_fit_predict_batch
+ * takes for its number of fits.
+ *
+ * Layouts.  Host: X (batch, N, d), Y (batch, P, N) -- each target of a fit contiguous over its N samples -- Xs (batch, M, d),
+ * theta (batch, theta_stride).  Outputs: mean (batch, P, M), var (batch, M) (shared by the P targets of a fit), logml (batch, P),
+ * info (batch).  Device variant: dX / dXs / dtheta / djitter as cgp_fit_predict_batch_device (SoA (batch, d, N) / (batch, d, M),
+ * (batch, CGP_MAX_THETA), (batch) or NULL), dY (batch, P, N), outputs as above.
+ *
+ * Determinism.  A column's mean row and logml are a function of its own data and of the schedule the call's number of fits
+ * selects: never of its position p, of P, of the other columns, of the fit's slot or of neighbouring fits.  Permuting the columns
+ * of Y permutes mean and logml bitwise; the first columns of a wide call are bitwise the same columns run alone.  No atomics; every
+ * sum runs in a fixed order over the REAL N samples (padding is not summed).  var is bitwise what cgp_fit_predict_cov_batch
+ * reports as diag(cov) for the same fit in a call of the same number of fits: the unchanged schedule's own variance.  Between two
+ * schedules (a call small enough for the latency schedule against a larger one) results agree to rounding, 1e-9.
+ *
+ * cgp_multi_reserve: scratch for Z of up to max_batch fits with up to max_p targets: max_batch x (the context's max_n rounded up
+ * to 128) x (max_p rounded up to 128) doubles.  1 <= max_batch <= the context's, 1 <= max_p <= 4096, else CGP_EINVAL; CGP_ENOMEM
+ * leaves no reservation; calling it again replaces the reservation.  Blocks (it synchronises the device).  cgp_destroy frees it.
+ *
+ * Status of the two calls: without a reservation CGP_ESTATE; a batch or a P beyond it CGP_ECAPACITY; P < 1, M < 1, a NULL
+ * required pointer or theta_stride < ntheta CGP_EINVAL; shape errors otherwise as cgp_fit_predict_batch (CGP_EINVAL /
+ * CGP_ECAPACITY).  A fit whose info stays non-zero has NaN in all P of its means, in its var and in its P logml entries; its
+ * neighbours are unaffected.
+ *
+ * Cost.  The solve is one launch with one workgroup per (fit, 64 or 128 targets) that walks all of N itself (about N^2 flops per
+ * target at one SIMD's rate), so its length does not shrink with P: 1.2 ms at N = 2048 whether P is 1 or 512.  Below P ~ 16 on
+ * a lone fit of N = 2048, M = 599, replicating X through cgp_fit_predict_batch_device is as fast or faster (measured: P = 8 0.79 x,
+ * P = 16 1.23 x, P = 512 17 x the replicate route; 64 fits x P = 8: 5.2 x; DESIGN.md section 9d has the table).
+ *
+ * Not provided: hyper-parameter optimisation over the summed logML, multi-target leave-one-out or joint covariance, multi-target
+ * sliding windows, and a cgp_sweep_* form. */
+int cgp_multi_reserve(cgp_ctx *ctx, int max_batch, int max_p);
+/* cgp_fit_predict_multi_batch: blocks; GPy's jitter ladder per fit exactly as cgp_fit_predict_batch runs it (a failed fit is
+ * retried as a call of one fit; its targets are solved and contracted right after its retry, the whole batch's before the first
+ * retry).  logml and info may be NULL.  Returns a negative error, else 0 or the first non-zero per-fit status. */
+int cgp_fit_predict_multi_batch(cgp_ctx *ctx, int batch, int N, int d, int M, int P, int kernel_id,
+                                const double *X, const double *Y, const double *Xs, const double *theta,
+                                int theta_stride, int include_noise, double *mean, double *var, double *logml,
+                                int *info);
+/* Device-resident variant: the fit schedule plus four launches on hip_stream; no allocation, no synchronisation, no jitter
+ * ladder (capturable into a hipGraph).  dlogml and dinfo are required.  The underlying fit runs on each fit's column 0, gathered
+ * into a buffer of the context; its own mean / logML are by-products and are not returned. */
+int cgp_fit_predict_multi_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, int P, int kernel_id,
+                                       const double *dX, const double *dY, const double *dXs, const double *dtheta,
+                                       const double *djitter, int include_noise, double *dmean, double *dvar,
+                                       double *dlogml, int *dinfo, void *hip_stream);
+/* Test hook: rows = 64 / 128 forces the tile height of the solve launch, 0 gives the choice back to the engine (it picks from
+ * (batch, P) only).  The two forms agree bitwise per element; anything else is CGP_EINVAL. */
+int cgp_multi_set_form(cgp_ctx *ctx, int rows);
+
 /* ---- multi-device sweep (SURVEY.md 8b "cgp_fit_predict_batch(ctx[], ...)", 8e) --------------------
  * One engine context and one host thread per listed device; a batch of independent windows is cut into
  * contiguous per-device blocks (device i gets fits [start_i, stop_i), the first batch % ndev devices
