@@ -11,6 +11,7 @@
 #include "cgp_window_joint.hpp"
 #include "cgp_joint.hpp"
 #include "cgp_multi.hpp"
+#include "cgp_multi_grad.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
 #include "cgp_loo.hpp"
@@ -142,6 +143,12 @@ struct cgp_ctx {
   int mz_form = 0;   // cgp_multi_set_form: 0 = the engine picks the solve's tile height, 64 / 128 = as told (tests)
   void *mz_dev = nullptr;
   size_t mz_dev_cap = 0;
+  // multi-target objective (cgp_multi_grad_reserve): A = Ky^-1 Y of up to ma_max_batch fits x ma_max_p targets, [fit][P padded to 16][NT 128],
+  // then (ma_max_batch, ma_max_p) logml; staging of the host calls [Y | nll | grad | logml], grown on demand and kept
+  void *ma = nullptr;
+  int ma_max_batch = 0, ma_max_p = 0;
+  void *ma_dev = nullptr;
+  size_t ma_dev_cap = 0;
   // cgp_window_push staging, grown on demand and kept: one pinned host block and one device block per direction
   void *win_pin = nullptr, *win_dev = nullptr;
   size_t win_pin_cap = 0, win_dev_cap = 0;
@@ -207,6 +214,7 @@ void joint_free(cgp_ctx *c);
 int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, const double *dXs,
                      const double *dtheta, const double *dvar, const int *dinfo, hipStream_t s);
 void multi_free(cgp_ctx *c);
+void multi_grad_free(cgp_ctx *c);   // cgp_multi_grad_host.hpp
 int multi_hook_launch(cgp_ctx *c, const MultiCall &mc, int N, int M, int slab, int slot, int nfit, hipStream_t s);
 // what the hook of a batch call enqueues for the fits in slabs slab ... into the slots slot ... of the call's arrays
 inline int post_fit_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s);
@@ -1396,6 +1404,7 @@ void cgp_destroy(cgp_ctx *c) {
   window_free(c, false);
   joint_free(c);
   multi_free(c);
+  multi_grad_free(c);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -2972,3 +2981,6 @@ extern "C" int cgp_loo(cgp_ctx *c, const double *X, const double *y, int N, int 
   memcpy(c->ftheta, theta, sizeof(double) * nth);
   return info;
 }
+
+// multi-target objective: cgp_multi_grad_reserve ... cgp_optimize_multi_batch
+#include "cgp_multi_grad_host.hpp"

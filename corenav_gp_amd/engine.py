@@ -91,6 +91,12 @@ _SIGS = {
                                                                                 ctypes.c_int, _dp, _dp, _dp, _ip]),
     "cgp_fit_predict_multi_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp, _vp, _vp, _vp, _vp,
                                                                                        ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "cgp_multi_grad_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "cgp_multi_nll_grad_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp, _dp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                                                             _dp, _ip]),
+    "cgp_multi_nll_grad_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                                                                    _vp, _vp, _vp]),
+    "cgp_optimize_multi_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _ip]),
     "cgp_predict_cov": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
     "cgp_sample": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_double, _dp, _ip]),
     "cgp_window_init": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int]),
@@ -463,6 +469,47 @@ class Context:
         return self._chk(self.lib.cgp_fit_predict_multi_batch_device(self.h, B, N, d, M, P, kernel_id, dX, dY, dXs, dtheta,
                                                                      djitter or None, int(include_noise), dmean, dvar,
                                                                      dlogml, dinfo, ctypes.c_void_p(stream)))
+
+    # -- multi-target fits: gradient and optimiser of the summed logML (fp64 contexts) ------------------------
+    def multi_grad_reserve(self, max_batch, max_p):
+        """Scratch for the three calls below (A = Ky^-1 Y); needs a multi_reserve that covers it."""
+        return self._chk(self.lib.cgp_multi_grad_reserve(self.h, int(max_batch), int(max_p)))
+
+    def multi_nll_grad_batch(self, X, Y, theta, kernel_id, want_logml=True):
+        """X (B, N, d), Y (B, P, N), theta (B, nth) -> (rc, nll (B,), grad (B, nth), logml (B, P) or None, info (B,)):
+        nll = -sum_p logml[p] of each fit and its gradient with respect to the shared theta, from ONE factorisation per fit."""
+        X, Y, theta = _d(X), _d(Y), _d(theta)
+        B, N, d = X.shape
+        P, nth = Y.shape[1], theta.shape[1]
+        nll, grad = np.empty(B), np.empty((B, nth))
+        logml, info = (np.empty((B, P)) if want_logml else None), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_multi_nll_grad_batch(self.h, B, N, d, P, kernel_id, _p(X), _p(Y), _p(theta), nth, _p(nll),
+                                                         _p(grad), nth, _p(logml) if want_logml else None,
+                                                         info.ctypes.data_as(_ip)))
+        return rc, nll, grad, logml, info
+
+    def multi_nll_grad_batch_device(self, B, N, d, P, kernel_id, dX, dY, dtheta, djitter, dnll, dgrad, grad_stride, dlogml,
+                                    dinfo, stream=0):
+        """Device pointers as fit_predict_multi_batch_device; dnll (B,), dgrad (B, grad_stride), dlogml (B, P) or 0."""
+        return self._chk(self.lib.cgp_multi_nll_grad_batch_device(self.h, B, N, d, P, kernel_id, dX, dY, dtheta, djitter or None,
+                                                                  dnll, dgrad, int(grad_stride), dlogml or None, dinfo,
+                                                                  ctypes.c_void_p(stream)))
+
+    def optimize_multi_batch(self, X, Y, kernel_id, theta0, max_evals=1000):
+        """m.optimize() of the multi-column model: X (B, N, d), Y (B, P, N), theta0 (B, nth) or (nth,) ->
+        (theta_opt (B, nth), sum_p logml (B,), n_evals (B,))."""
+        X, Y = _d(X), _d(Y)
+        B, N, d = X.shape
+        theta = np.array(theta0, dtype=np.float64)
+        if theta.ndim == 1:
+            theta = np.tile(theta, (B, 1))
+        theta = np.ascontiguousarray(theta)
+        logml, nev = np.empty(B), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_optimize_multi_batch(self.h, B, N, d, Y.shape[1], kernel_id, _p(X), _p(Y), _p(theta),
+                                                         theta.shape[1], max_evals, _p(logml), nev.ctypes.data_as(_ip)))
+        if rc > 0:
+            raise CgpError(rc)
+        return theta, logml, nev
 
     def predict_cov(self, Xs, include_noise=True):
         """After fit / optimize: mean (M,) and the full posterior covariance (M, M), m.predict(Xs, full_cov=True)."""

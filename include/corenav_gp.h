@@ -365,8 +365,8 @@ int cgp_sample(cgp_ctx *ctx, const double *Xs, int M, int S, const double *xi, i
  * a lone fit of N = 2048, M = 599, replicating X through cgp_fit_predict_batch_device is as fast or faster (measured: P = 8 0.79 x,
  * P = 16 1.23 x, P = 512 17 x the replicate route; 64 fits x P = 8: 5.2 x; DESIGN.md section 9d has the table).
  *
- * Not provided: hyper-parameter optimisation over the summed logML, multi-target leave-one-out or joint covariance, multi-target
- * sliding windows, and a cgp_sweep_* form. */
+ * Not provided: multi-target leave-one-out or joint covariance, multi-target sliding windows, and a cgp_sweep_* form.  (The
+ * hyper-parameters of a multi-target model: the next section.) */
 int cgp_multi_reserve(cgp_ctx *ctx, int max_batch, int max_p);
 /* cgp_fit_predict_multi_batch: blocks; GPy's jitter ladder per fit exactly as cgp_fit_predict_batch runs it (a failed fit is
  * retried as a call of one fit; its targets are solved and contracted right after its retry, the whole batch's before the first
@@ -385,6 +385,65 @@ int cgp_fit_predict_multi_batch_device(cgp_ctx *ctx, int batch, int N, int d, in
 /* Test hook: rows = 64 / 128 forces the tile height of the solve launch, 0 gives the choice back to the engine (it picks from
  * (batch, P) only).  The two forms agree bitwise per element; anything else is CGP_EINVAL. */
 int cgp_multi_set_form(cgp_ctx *ctx, int rows);
+
+/* ---- multi-target fits: gradient and optimiser of the summed logML ------------------------------------
+ * m.optimize() of the multi-column model (gp_slip_node.py:36 with Y (N, P)): ONE theta per fit maximises
+ *   sum_p logml[p] = -P/2 log|Ky| - 1/2 tr(Y^T Ky^-1 Y) - N P / 2 log 2 pi.
+ * With Ky = L L^T, Z = L^-1 Y and A = Ky^-1 Y (N x P), GPy's ExactGaussianInference gives
+ *   nll = -sum_p logml[p],    dL/dK = 1/2 (A A^T - P Ky^-1),    grad = d nll / d theta (natural parameters, cgp_nll_grad's order)
+ * -- cgp_nll_grad's sums with w_ij = sum_p A_ip A_jp - P Ky^-1_ij; at P = 1 exactly cgp_nll_grad.  One gradient-mode
+ * factorisation (needs max_m >= N, as every gradient call) serves all P columns; on top of it come N^2 P flops for Z, N^2 P for
+ * A and N^2 P / 2 for the rank-P term, all on the fp64 matrix cores.  The only other route to this gradient is P calls of
+ * cgp_nll_grad at the same theta: P factorisations of the same matrix.  CGP_F64 contexts only (CGP_EINVAL in a CGP_F32 context
+ * before anything is enqueued; the context stays usable).  All five kernel ids.  Every shape takes the tiled schedules: the
+ * one-launch short-window kernel (k_small) holds no multi-column form, so windows of at most 160 samples run the large-window
+ * machinery here (as in the Matern and leave-one-out sections).
+ *
+ * cgp_multi_grad_reserve: scratch for A of up to max_batch fits with up to max_p targets: max_batch x (the context's max_n rounded
+ * up to 128) x (max_p rounded up to 16) doubles (+ max_batch x max_p).  It needs a cgp_multi_reserve that covers it (max_batch and
+ * max_p within that reservation), else CGP_ESTATE.  1 <= max_batch <= the context's, 1 <= max_p <= 4096, else CGP_EINVAL;
+ * CGP_ENOMEM leaves no reservation; calling it again replaces the reservation.  Blocks.  cgp_destroy frees it.  A call below must
+ * fit BOTH reservations as they are when it is made.
+ *
+ * Status of the three calls, before anything is enqueued: CGP_F32 context or P < 1: CGP_EINVAL; a reservation missing: CGP_ESTATE;
+ * batch or P beyond one: CGP_ECAPACITY; then the shape rules of cgp_nll_grad / cgp_optimize_batch (CGP_EINVAL / CGP_ECAPACITY,
+ * max_m >= N among them); a NULL required pointer, theta_stride or grad_stride < ntheta, and for the optimiser a theta <= 0:
+ * CGP_EINVAL.  A failed call leaves the context usable.
+ *
+ * Determinism.  Run to run bitwise.  A fit's nll, gradient and logml are a function of its own data and of the schedule the call's
+ * number of fits selects, never of its slot or its neighbours; no atomics, every sum in a fixed order.  The host form and the
+ * device form of the same call are bitwise equal.  NOT promised: bitwise invariance under a permutation of the columns of Y -- the
+ * sum over p is the inner dimension of a matrix-core loop; nll and gradient then agree to rounding only (logml[p] still permutes
+ * bitwise).
+ *
+ * Cost (one MI355X, N = 2048, d = 6, SE-ARD, one evaluation of a lone fit; DESIGN.md section 9e has the table): 3.3 - 3.6 ms for
+ * P = 1 ... 512, against 1.87 ms per column for P calls of cgp_nll_grad: P = 1 0.56 x, P = 8 4.5 x, P = 64 35 x, P = 512 263 x; 64 fits
+ * x P = 8: 45 x.  For P = 1 call cgp_nll_grad: the crossover is between P = 1 and P = 2 (the multi call carries the solve for Z, a
+ * 1.2 ms chain over N that does not shrink with P). */
+int cgp_multi_grad_reserve(cgp_ctx *ctx, int max_batch, int max_p);
+/* cgp_multi_nll_grad_batch: host buffers, layouts as cgp_fit_predict_multi_batch: X (batch, N, d), Y (batch, P, N), theta (batch,
+ * theta_stride); outputs nll (batch), grad (batch, grad_stride), logml (batch, P) or NULL, info (batch) or NULL.  GPy's jitter
+ * ladder per fit exactly as cgp_loo_batch runs it (the fits that failed only, one at a time, mean(diag) 1e-6 10^k, k = 0..4); the
+ * results of a retried fit are those on the Ky that finally factored.  A fit whose info stays non-zero has NaN in nll, in its
+ * gradient and in its P logml entries; its neighbours are unaffected.  Returns a negative error, else 0 or the first non-zero
+ * per-fit status (cgp_loo_batch's convention).  Blocks. */
+int cgp_multi_nll_grad_batch(cgp_ctx *ctx, int batch, int N, int d, int P, int kernel_id,
+                             const double *X, const double *Y, const double *theta, int theta_stride,
+                             double *nll, double *grad, int grad_stride, double *logml, int *info);
+/* Device-resident variant: dX (batch, d, N), dY (batch, P, N), dtheta (batch, CGP_MAX_THETA), djitter (batch) or NULL; dnll (batch),
+ * dgrad (batch, grad_stride), dlogml (batch, P) or NULL, dinfo (batch) int32 (required).  The gradient-mode fit schedule on each
+ * fit's column 0 plus seven launches on hip_stream: no allocation, no synchronisation, no ladder (capturable into a hipGraph) --
+ * read dinfo and re-submit the failed fits with djitter set.  A fit with dinfo != 0 gets NaN. */
+int cgp_multi_nll_grad_batch_device(cgp_ctx *ctx, int batch, int N, int d, int P, int kernel_id,
+                                    const double *dX, const double *dY, const double *dtheta, const double *djitter,
+                                    double *dnll, double *dgrad, int grad_stride, double *dlogml, int *dinfo,
+                                    void *hip_stream);
+/* cgp_optimize_multi_batch: cgp_optimize_batch's host L-BFGS (Logexp transform, pgtol 1e-5, factr 1e7, the jitter ladder per trial
+ * point, +inf for a point that stays infeasible) over the evaluation above: each fit's theta (batch, theta_stride) is replaced by
+ * its optimum; logml_sum (batch) = sum_p logml[p] there and n_evals (batch) may be NULL.  max_evals <= 0: 1000.  Blocks. */
+int cgp_optimize_multi_batch(cgp_ctx *ctx, int batch, int N, int d, int P, int kernel_id,
+                             const double *X, const double *Y, double *theta_inout, int theta_stride, int max_evals,
+                             double *logml_sum, int *n_evals);
 
 /* ---- multi-device sweep (SURVEY.md 8b "cgp_fit_predict_batch(ctx[], ...)", 8e) --------------------
  * One engine context and one host thread per listed device; a batch of independent windows is cut into
