@@ -1217,6 +1217,53 @@ int upload_theta(cgp_ctx *c, const double *theta, int theta_stride, int nth, int
   return CGP_OK;
 }
 
+// The windows of a batch -> slots 0 .. batch - 1 of c->dX (SoA, device dtype) and, unless y is null, c->dy
+int upload_batch_xy(cgp_ctx *c, int batch, int N, int d, const double *X, const double *y, hipStream_t s) {
+  std::vector<char> hx((size_t)batch * d * N * c->esz), hy(y ? (size_t)batch * N * c->esz : 0);
+  for (int b = 0; b < batch; ++b) {
+    pack_soa(X + (size_t)b * N * d, N, d, c->dtype, hx, (size_t)b * d * N);
+    if (y) pack_vec(y + (size_t)b * N, N, c->dtype, hy, (size_t)b * N);
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->dX, hx.data(), hx.size(), hipMemcpyHostToDevice, s));          // pageable sources: staged by the
+  if (y) HIP_TRY(c, hipMemcpyAsync(c->dy, hy.data(), hy.size(), hipMemcpyHostToDevice, s));   // runtime before the calls return
+  return CGP_OK;
+}
+
+// FitArgs of a gradient-mode factorisation (xid = 1, M = N: the "test rows" are the identity, Xs is unused, and the extra block of
+// the factor panel ends up holding Wt = (L^-1)^T) with the context's mean / var / gpart; the caller sets y, theta, jitter, logml, info
+FitArgs grad_mode_args(cgp_ctx *c, int N, int d, int kid, const void *dX) {
+  FitArgs a = base_args(c, N, d, /*M=*/N, kid, 0);
+  a.xid = 1;
+  a.X = dX;
+  a.Xs = dX;
+  a.mean = c->dmean;
+  a.var = c->dvar;
+  a.gpart = c->dgpart;
+  return a;
+}
+
+// GPy's jitchol policy for the fits of a batched call that failed (hinfo[b] != 0, not marked in skip), one fit at a time (rare
+// path): jitter = mean(diag Ky) 1e-6 10^k, k = 0..4, goes to c->djitter[b], resubmit(b) queues the fit again on s, and its info
+// word is read back from c->dinfo[b].  jit_last[b]: the last jitter fit b was tried with (0: it never failed).
+template <typename F>
+int jitter_ladder(cgp_ctx *c, int batch, int N, int d, int kid, const double *theta, int theta_stride, const double *X, int *hinfo,
+                  const std::vector<char> *skip, double *jit_last, hipStream_t s, F &&resubmit) {
+  for (int b = 0; b < batch; ++b) {
+    jit_last[b] = 0.0;
+    if (hinfo[b] == 0 || (skip && (*skip)[b])) continue;
+    double jit = mean_diag(kid, theta + (size_t)b * theta_stride, d, X + (size_t)b * N * d, N) * 1e-6;
+    for (int attempt = 0; attempt < 5 && hinfo[b] != 0; ++attempt, jit *= 10.0) {
+      HIP_TRY(c, hipMemcpyAsync(c->djitter + b, &jit, sizeof(double), hipMemcpyHostToDevice, s));
+      const int rc = resubmit(b);
+      if (rc != CGP_OK) return rc;
+      HIP_TRY(c, hipMemcpyAsync(&hinfo[b], c->dinfo + b, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipStreamSynchronize(s));
+      jit_last[b] = jit;
+    }
+  }
+  return CGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1684,29 +1731,20 @@ static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, in
   HIP_TRY(c, queue_results());
   HIP_TRY(c, hipStreamSynchronize(s));
   lap("device done (info + results)");
-  bool retried = false;
-  // GPy jitchol policy for the fits that failed: jitter = mean(diag) * 1e-6 * 10^k, k = 0..4,
-  // re-submitted one fit at a time (rare path) into the same device slots.
+  // the fits that failed climb the jitter ladder, re-submitted into the same device slots
+  const bool retried = std::any_of(hinfo, hinfo + batch, [](int v) { return v != 0; });
   std::vector<double> hjit(batch, 0.0);
-  for (int b = 0; b < batch; ++b) {
-    if (hinfo[b] == 0) continue;
-    double jit = mean_diag(kid, theta + (size_t)b * theta_stride, d, X + (size_t)b * N * d, N) * 1e-6;
-    retried = true;
-    for (int attempt = 0; attempt < 5 && hinfo[b] != 0; ++attempt, jit *= 10.0) {
-      HIP_TRY(c, hipMemcpyAsync(c->djitter + b, &jit, sizeof(double), hipMemcpyHostToDevice, s));
-      c->pending_tab = tick_tab;
-      rc = fit_predict_device(
-          c, 1, N, d, M, kid, (char *)c->dX + (size_t)b * d * N * esz, (char *)c->dy + (size_t)b * N * esz,
-          (char *)c->dXs + (size_t)b * d * M * esz, c->dtheta + (size_t)b * CGP_MAX_THETA, c->djitter + b,
-          include_noise, (char *)c->dmean + (size_t)b * M * esz, (char *)c->dvar + (size_t)b * M * esz,
-          c->dlogml + b, c->dinfo + b, CGP_STREAM_CTX, jh != nullptr);
-      if (rc != CGP_OK) return rc;
-      if (jh && (rc = post_fit_launch(c, *jh, N, d, M, kid, 0, b, 1, s)) != CGP_OK) return rc;
-      HIP_TRY(c, hipMemcpyAsync(&hinfo[b], c->dinfo + b, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIP_TRY(c, hipStreamSynchronize(s));
-      hjit[b] = jit;
-    }
-  }
+  rc = jitter_ladder(c, batch, N, d, kid, theta, theta_stride, X, hinfo, nullptr, hjit.data(), s, [&](int b) {
+    c->pending_tab = tick_tab;
+    int r = fit_predict_device(
+        c, 1, N, d, M, kid, (char *)c->dX + (size_t)b * d * N * esz, (char *)c->dy + (size_t)b * N * esz,
+        (char *)c->dXs + (size_t)b * d * M * esz, c->dtheta + (size_t)b * CGP_MAX_THETA, c->djitter + b,
+        include_noise, (char *)c->dmean + (size_t)b * M * esz, (char *)c->dvar + (size_t)b * M * esz,
+        c->dlogml + b, c->dinfo + b, CGP_STREAM_CTX, jh != nullptr);
+    if (r == CGP_OK && jh) r = post_fit_launch(c, *jh, N, d, M, kid, 0, b, 1, s);
+    return r;
+  });
+  if (rc != CGP_OK) return rc;
   c->fjitter = hjit[0];
   if (retried) {
     HIP_TRY(c, queue_results());
@@ -1967,20 +2005,14 @@ template <typename T> void launch_grad(const FitArgs &a, int npairs, int batch, 
 template <typename T>
 int grad_eval(cgp_ctx *c, int N, int d, int kid, double *logml, double sums[GRAD_N], int *info) {
   hipStream_t s = c->stream;
-  FitArgs a = base_args(c, N, d, /*M=*/N, kid, 0);
-  a.xid = 1;
-  a.X = c->dX;
-  a.Xs = c->dX;  // unused: the "test rows" are the identity
+  FitArgs a = grad_mode_args(c, N, d, kid, c->dX);
   a.y = c->dy;
   a.theta = c->dtheta;
   a.jitter = c->djitter;
-  a.mean = c->dmean;
-  a.var = c->dvar;
   // logML and info of this one window live right behind its partial sums: [sums | logml | info] comes back in ONE copy,
   // into the pinned block (a real asynchronous copy, no pageable staging)
   const int npairs = a.NT * (a.NT + 1) / 2;
   const size_t npart = (size_t)npairs * GRAD_N;
-  a.gpart = c->dgpart;
   a.logml = c->dgpart + npart;
   a.info = reinterpret_cast<int *>(c->dgpart + npart + 1);
   int rc = run(c, a, 1, true, true, s);
@@ -1999,8 +2031,6 @@ int grad_eval(cgp_ctx *c, int N, int d, int kid, double *logml, double sums[GRAD
     for (int i = 0; i < GRAD_N; ++i) sums[i] += part[(size_t)pz * GRAD_N + i];
   return CGP_OK;
 }
-
-void grad_from_sums(int kid, int d, const double *theta, const double *sums, double *grad);   // below, with the batched optimiser
 
 // The window of a gradient-mode evaluation -> slot 0 (once per cgp_nll_grad call, once per cgp_optimize run)
 int upload_window(cgp_ctx *c, const double *X, const double *y, int N, int d, hipStream_t s) {
@@ -2359,13 +2389,10 @@ extern "C" int cgp_optimize(cgp_ctx *c, const double *X, const double *y, int N,
   if (rc != CGP_OK) return rc;
   if (!X || !y || !theta) return CGP_EINVAL;
   const int nth = ntheta(kid, d);
-  // Logexp transform (GPy paramz.transformations.Logexp): theta = log(1 + exp(x))
-  auto to_theta = [](double x) { return x > 35.0 ? x : std::log1p(std::exp(x)); };
-  auto to_x = [](double th) { return th > 35.0 ? th : std::log(std::expm1(th)); };
-  std::vector<double> x(nth), th(nth), g(nth);
+  std::vector<double> x(nth), th(nth), g(nth);   // x: the Logexp image of theta
   for (int i = 0; i < nth; ++i) {
     if (!(theta[i] > 0.0)) return CGP_EINVAL;
-    x[i] = to_x(theta[i]);
+    x[i] = corenav::logexp_x(theta[i]);
   }
   int hard_error = CGP_OK;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2374,17 +2401,17 @@ extern "C" int cgp_optimize(cgp_ctx *c, const double *X, const double *y, int N,
   rc = upload_window(c, X, y, N, d, c->stream);   // the window does not change between evaluations: only theta travels
   if (rc != CGP_OK) return rc;
   auto fg = [&](const std::vector<double> &xx, std::vector<double> &gx) -> double {
-    for (int i = 0; i < nth; ++i) th[i] = std::max(to_theta(xx[i]), 1e-300);
+    for (int i = 0; i < nth; ++i) th[i] = corenav::logexp_theta_eval(xx[i]);
     double nll = 0.0;
     const int r = nll_grad_resident(c, X, N, d, kid, th.data(), &nll, g.data());
     if (r < 0) hard_error = r;
     if (r != 0) return INFINITY;  // not PD even with jitter: infeasible point
-    for (int i = 0; i < nth; ++i) gx[i] = g[i] * (xx[i] > 35.0 ? 1.0 : -std::expm1(-th[i]));  // dtheta/dx = 1 - exp(-theta)
+    for (int i = 0; i < nth; ++i) gx[i] = g[i] * corenav::logexp_dtheta_dx(xx[i], th[i]);
     return nll;
   };
   corenav::LbfgsResult res = corenav::lbfgs_minimize(fg, x, max_evals > 0 ? max_evals : 1000);
   if (hard_error != CGP_OK) return hard_error;
-  for (int i = 0; i < nth; ++i) theta[i] = to_theta(x[i]);
+  for (int i = 0; i < nth; ++i) theta[i] = corenav::logexp_theta(x[i]);
   // leave the context fitted at the optimum
   double nll = 0.0;
   rc = nll_grad_resident(c, X, N, d, kid, theta, &nll, g.data());
@@ -2664,18 +2691,12 @@ template <typename T>
 int grad_eval_batch(cgp_ctx *c, int batch, int N, int d, int kid, std::vector<double> &logml, std::vector<double> &sums,
                     std::vector<int> &info) {
   hipStream_t s = c->stream;
-  FitArgs a = base_args(c, N, d, /*M=*/N, kid, 0);
-  a.xid = 1;
-  a.X = c->dX;
-  a.Xs = c->dX;
+  FitArgs a = grad_mode_args(c, N, d, kid, c->dX);
   a.y = c->dy;
   a.theta = c->dtheta;
   a.jitter = c->djitter;  // per window; zero unless the jitter ladder of cgp_optimize_batch is climbing
-  a.mean = c->dmean;
-  a.var = c->dvar;
   a.logml = c->dlogml;
   a.info = c->dinfo;
-  a.gpart = c->dgpart;
   int rc = run(c, a, batch, true, true, s);
   if (rc != CGP_OK) return rc;
   const int npairs = a.NT * (a.NT + 1) / 2;
@@ -2694,26 +2715,6 @@ int grad_eval_batch(cgp_ctx *c, int batch, int N, int d, int kid, std::vector<do
       for (int i = 0; i < GRAD_N; ++i) sums[(size_t)b * GRAD_N + i] += part[((size_t)b * npairs + pz) * GRAD_N + i];
   return CGP_OK;
 }
-
-// d(-logML)/dtheta from the k_grad sums (same formulas as cgp_nll_grad)
-void grad_from_sums(int kid, int d, const double *theta, const double *sums, double *grad) {
-  if (kid == CGP_KERNEL_SE_ISO) {
-    double se = 0;
-    for (int q = 0; q < d; ++q) se += sums[1 + q];
-    grad[0] = -0.5 * sums[0] / theta[0];
-    grad[1] = -0.5 * se / theta[1];
-    grad[2] = -0.5 * sums[9];
-  } else if (k_is_ard(kid)) {   // Matern: k_grad<T, MAT> put -2 dk/dr^2 where the squared exponential has k, so the formulas are SE_ARD's
-    grad[0] = -0.5 * sums[0] / theta[0];
-    for (int q = 0; q < d; ++q) grad[1 + q] = -0.5 * sums[1 + q] / theta[1 + q];
-    grad[d + 1] = -0.5 * sums[9];
-  } else {
-    grad[0] = -0.5 * sums[0] / theta[0];
-    grad[1] = -0.5 * sums[1] / theta[1];
-    grad[2] = -0.5 * sums[0] / theta[2];
-    grad[3] = -0.5 * sums[9];
-  }
-}
 }  // namespace
 
 extern "C" int cgp_optimize_batch(cgp_ctx *c, int batch, int N, int d, int kid, const double *X, const double *y,
@@ -2725,20 +2726,13 @@ extern "C" int cgp_optimize_batch(cgp_ctx *c, int batch, int N, int d, int kid, 
   if (theta_stride < nth) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  const size_t esz = c->esz;
-  std::vector<char> hx((size_t)batch * d * N * esz), hy((size_t)batch * N * esz);
-  for (int b = 0; b < batch; ++b) {
-    pack_soa(X + (size_t)b * N * d, N, d, c->dtype, hx, (size_t)b * d * N);
-    pack_vec(y + (size_t)b * N, N, c->dtype, hy, (size_t)b * N);
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->dX, hx.data(), hx.size(), hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(c->dy, hy.data(), hy.size(), hipMemcpyHostToDevice, s));
+  if ((rc = upload_batch_xy(c, batch, N, d, X, y, s)) != CGP_OK) return rc;
   c->lazy_fit = false;
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < nth; ++i)
+      if (!(theta[(size_t)b * theta_stride + i] > 0.0)) return CGP_EINVAL;
   if (small_ok(c, N, kid)) {
     // short windows: ONE launch, one workgroup per window, each running its own L-BFGS loop on the device (cgp_small.hpp)
-    for (int b = 0; b < batch; ++b)
-      for (int i = 0; i < nth; ++i)
-        if (!(theta[(size_t)b * theta_stride + i] > 0.0)) return CGP_EINVAL;
     std::vector<double> hth;
     rc = upload_theta(c, theta, theta_stride, nth, batch, s, hth);
     if (rc == CGP_OK) rc = small_launch(c, batch, N, d, kid, SM_MODE_OPT, max_evals, s, nullptr, nullptr, tick_table_entries_batch(kid, d, batch, X, N, nullptr, 0));
@@ -2756,34 +2750,16 @@ extern "C" int cgp_optimize_batch(cgp_ctx *c, int batch, int N, int d, int kid, 
     }
     return CGP_OK;
   }
-  auto to_theta = [](double x) { return x > 35.0 ? x : std::log1p(std::exp(x)); };
-  auto to_x = [](double th) { return th > 35.0 ? th : std::log(std::expm1(th)); };
-  std::vector<corenav::LbfgsStepper> st;
-  st.reserve(batch);
-  for (int b = 0; b < batch; ++b) {
-    std::vector<double> x0(nth);
-    for (int i = 0; i < nth; ++i) {
-      if (!(theta[(size_t)b * theta_stride + i] > 0.0)) return CGP_EINVAL;
-      x0[i] = to_x(theta[(size_t)b * theta_stride + i]);
-    }
-    st.emplace_back(x0, max_evals > 0 ? max_evals : 1000, 1e-5, 1e7);
-  }
-  std::vector<double> th((size_t)batch * nth), hth, lml, sums, g(nth), gx(nth), jit(batch, 0.0), lml2, sums2;
+  std::vector<double> hth, lml, sums, jit(batch, 0.0), lml2, sums2;
   std::vector<int> info, info2;
   c->have_fit = false;
   auto eval = [&](std::vector<double> &l, std::vector<double> &sm, std::vector<int> &inf) {
     return c->dtype == CGP_F64 ? grad_eval_batch<double>(c, batch, N, d, kid, l, sm, inf)
                                : grad_eval_batch<float>(c, batch, N, d, kid, l, sm, inf);
   };
-  for (int round = 0; round < (max_evals > 0 ? max_evals : 1000) + 40; ++round) {
-    bool any = false;
-    for (int b = 0; b < batch; ++b) {
-      any = any || !st[b].done();
-      const std::vector<double> &xx = st[b].done() ? st[b].best() : st[b].trial();
-      for (int i = 0; i < nth; ++i) th[(size_t)b * nth + i] = std::max(to_theta(xx[i]), 1e-300);
-    }
-    if (!any) break;
-    rc = upload_theta(c, th.data(), nth, nth, batch, s, hth);
+  // one round of the optimiser: every window is evaluated (a finished one at its best point), only active ones climb the ladder
+  auto round = [&](const double *th, const char *active, double *f, double *g, char *feasible) -> int {
+    int rc = upload_theta(c, th, nth, nth, batch, s, hth);
     if (rc != CGP_OK) return rc;
     HIP_TRY(c, hipMemsetAsync(c->djitter, 0, sizeof(double) * batch, s));
     rc = eval(lml, sums, info);
@@ -2794,16 +2770,16 @@ extern "C" int cgp_optimize_batch(cgp_ctx *c, int batch, int N, int d, int kid, 
     for (int attempt = 0; attempt < 5; ++attempt) {
       bool any_bad = false;
       for (int b = 0; b < batch; ++b) {
-        if (st[b].done() || info[b] == 0) continue;
+        if (!active[b] || info[b] == 0) continue;
         any_bad = true;
-        jit[b] = attempt == 0 ? mean_diag(kid, th.data() + (size_t)b * nth, d, X + (size_t)b * N * d, N) * 1e-6 : jit[b] * 10.0;
+        jit[b] = attempt == 0 ? mean_diag(kid, th + (size_t)b * nth, d, X + (size_t)b * N * d, N) * 1e-6 : jit[b] * 10.0;
       }
       if (!any_bad) break;
       HIP_TRY(c, hipMemcpyAsync(c->djitter, jit.data(), sizeof(double) * batch, hipMemcpyHostToDevice, s));
       rc = eval(lml2, sums2, info2);
       if (rc != CGP_OK) return rc;
       for (int b = 0; b < batch; ++b) {
-        if (st[b].done() || info[b] == 0) continue;
+        if (!active[b] || info[b] == 0) continue;
         info[b] = info2[b];
         lml[b] = lml2[b];
         std::copy(sums2.begin() + (size_t)b * GRAD_N, sums2.begin() + (size_t)(b + 1) * GRAD_N, sums.begin() + (size_t)b * GRAD_N);
@@ -2811,24 +2787,20 @@ extern "C" int cgp_optimize_batch(cgp_ctx *c, int batch, int N, int d, int kid, 
     }
     std::fill(jit.begin(), jit.end(), 0.0);
     for (int b = 0; b < batch; ++b) {
-      if (st[b].done()) continue;
-      const double *tb = th.data() + (size_t)b * nth;
-      double f = INFINITY;
-      if (info[b] == 0) {
-        grad_from_sums(kid, d, tb, sums.data() + (size_t)b * GRAD_N, g.data());
-        const std::vector<double> &xx = st[b].trial();
-        for (int i = 0; i < nth; ++i) gx[i] = g[i] * (xx[i] > 35.0 ? 1.0 : -std::expm1(-tb[i]));
-        f = -lml[b];
-      }
-      st[b].tell(f, gx);
+      if (!active[b]) continue;
+      feasible[b] = info[b] == 0;
+      if (!feasible[b]) continue;
+      grad_from_sums(kid, d, th + (size_t)b * nth, sums.data() + (size_t)b * GRAD_N, g + (size_t)b * nth);
+      f[b] = -lml[b];
     }
-  }
+    return CGP_OK;
+  };
+  corenav::LbfgsBatchResult res;
+  if ((rc = corenav::lbfgs_minimize_logexp_batch(batch, nth, theta, theta_stride, nullptr, max_evals, round, res)) != CGP_OK) return rc;
   for (int b = 0; b < batch; ++b) {
-    const std::vector<double> &xb = st[b].best();
-    for (int i = 0; i < nth; ++i) theta[(size_t)b * theta_stride + i] = to_theta(xb[i]);
-    const corenav::LbfgsResult r = st[b].result();
-    if (logml_out) logml_out[b] = -r.f;
-    if (n_evals) n_evals[b] = r.evals;
+    for (int i = 0; i < nth; ++i) theta[(size_t)b * theta_stride + i] = res.theta[(size_t)b * nth + i];
+    if (logml_out) logml_out[b] = -res.f[b];
+    if (n_evals) n_evals[b] = res.evals[b];
   }
   return CGP_OK;
 }
@@ -2844,18 +2816,12 @@ struct LooOut {   // device pointers at the first fit of the call; each may be n
 // nothing synchronised.  dvar is free once k_finalize has run: it holds loo_lpd for k_loo_sum when the caller wants no loo_lpd.
 int loo_enqueue(cgp_ctx *c, int nfit, int N, int d, int kid, const double *dX, const double *dy, const double *dtheta,
                 const double *djitter, const LooOut &o, double *dlogml, int *dinfo, hipStream_t s) {
-  FitArgs a = base_args(c, N, d, /*M=*/N, kid, 0);
-  a.xid = 1;
-  a.X = dX;
-  a.Xs = dX;  // unused: the "test rows" are the identity
+  FitArgs a = grad_mode_args(c, N, d, kid, dX);
   a.y = dy;
   a.theta = dtheta;
   a.jitter = djitter;
-  a.mean = c->dmean;
-  a.var = c->dvar;
   a.logml = dlogml;
   a.info = dinfo;
-  a.gpart = c->dgpart;
   int rc = run(c, a, nfit, true, true, s);
   if (rc != CGP_OK) return rc;
   double *lpd = o.lpd ? o.lpd : static_cast<double *>(c->dvar);
@@ -2880,16 +2846,10 @@ int loo_batch_host(cgp_ctx *c, int batch, int N, int d, int kid, const double *X
   double *dout = static_cast<double *>(c->draw);
   const LooOut o{loo_mean ? dout : nullptr, loo_var ? dout + BN : nullptr, loo_lpd ? dout + 2 * BN : nullptr,
                  lpd_sum ? dout + 3 * BN : nullptr};
-  std::vector<char> hx(BN * d * sizeof(double)), hy(BN * sizeof(double));
-  for (int b = 0; b < batch; ++b) {
-    pack_soa(X + (size_t)b * N * d, N, d, CGP_F64, hx, (size_t)b * d * N);
-    pack_vec(y + (size_t)b * N, N, CGP_F64, hy, (size_t)b * N);
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->dX, hx.data(), hx.size(), hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(c->dy, hy.data(), hy.size(), hipMemcpyHostToDevice, s));
-  std::vector<double> hth;
-  int rc = upload_theta(c, theta, theta_stride, nth, batch, s, hth);
+  int rc = upload_batch_xy(c, batch, N, d, X, y, s);
   if (rc != CGP_OK) return rc;
+  std::vector<double> hth;
+  if ((rc = upload_theta(c, theta, theta_stride, nth, batch, s, hth)) != CGP_OK) return rc;
   HIP_TRY(c, hipMemsetAsync(c->djitter, 0, sizeof(double) * batch, s));
   const double *dX = static_cast<const double *>(c->dX), *dy = static_cast<const double *>(c->dy);
   rc = loo_enqueue(c, batch, N, d, kid, dX, dy, c->dtheta, c->djitter, o, c->dlogml, c->dinfo, s);
@@ -2897,23 +2857,16 @@ int loo_batch_host(cgp_ctx *c, int batch, int N, int d, int kid, const double *X
   std::vector<int> hinfo(batch);
   HIP_TRY(c, hipMemcpyAsync(hinfo.data(), c->dinfo, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  for (int b = 0; b < batch; ++b) {
-    jit_out[b] = 0.0;
-    if (hinfo[b] == 0) continue;
-    double jit = mean_diag(kid, theta + (size_t)b * theta_stride, d, X + (size_t)b * N * d, N) * 1e-6;
-    for (int attempt = 0; attempt < 5 && hinfo[b] != 0; ++attempt, jit *= 10.0) {
-      HIP_TRY(c, hipMemcpyAsync(c->djitter + b, &jit, sizeof(double), hipMemcpyHostToDevice, s));
-      const size_t off = (size_t)b * N;
-      const LooOut ob{o.mean ? o.mean + off : nullptr, o.var ? o.var + off : nullptr, o.lpd ? o.lpd + off : nullptr,
-                      o.sum ? o.sum + b : nullptr};
-      rc = loo_enqueue(c, 1, N, d, kid, dX + off * d, dy + off, c->dtheta + (size_t)b * CGP_MAX_THETA, c->djitter + b, ob,
+  rc = jitter_ladder(c, batch, N, d, kid, theta, theta_stride, X, hinfo.data(), nullptr, jit_out, s, [&](int b) {
+    const size_t off = (size_t)b * N;
+    const LooOut ob{o.mean ? o.mean + off : nullptr, o.var ? o.var + off : nullptr, o.lpd ? o.lpd + off : nullptr,
+                    o.sum ? o.sum + b : nullptr};
+    return loo_enqueue(c, 1, N, d, kid, dX + off * d, dy + off, c->dtheta + (size_t)b * CGP_MAX_THETA, c->djitter + b, ob,
                        c->dlogml + b, c->dinfo + b, s);
-      if (rc != CGP_OK) return rc;
-      HIP_TRY(c, hipMemcpyAsync(&hinfo[b], c->dinfo + b, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIP_TRY(c, hipStreamSynchronize(s));
-      if (hinfo[b] == 0) jit_out[b] = jit;
-    }
-  }
+  });
+  if (rc != CGP_OK) return rc;
+  for (int b = 0; b < batch; ++b)
+    if (hinfo[b] != 0) jit_out[b] = 0.0;   // only a fit that factored reports a jitter
   if (loo_mean) HIP_TRY(c, hipMemcpyAsync(loo_mean, o.mean, BN * sizeof(double), hipMemcpyDeviceToHost, s));
   if (loo_var) HIP_TRY(c, hipMemcpyAsync(loo_var, o.var, BN * sizeof(double), hipMemcpyDeviceToHost, s));
   if (loo_lpd) HIP_TRY(c, hipMemcpyAsync(loo_lpd, o.lpd, BN * sizeof(double), hipMemcpyDeviceToHost, s));

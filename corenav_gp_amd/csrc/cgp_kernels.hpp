@@ -55,6 +55,24 @@ enum { K_SE_ISO = 0, K_SE_ARD = 1, K_RBF_BROWNIAN = 2, K_MATERN32_ARD = 3, K_MAT
 __host__ __device__ __forceinline__ constexpr bool k_is_ard(int kid) { return kid == K_SE_ARD || kid >= K_MATERN32_ARD; }
 __host__ __device__ __forceinline__ constexpr bool k_is_matern(int kid) { return kid >= K_MATERN32_ARD; }
 __host__ __device__ __forceinline__ constexpr int k_ntheta(int kid, int d) { return kid == K_SE_ISO ? 3 : (k_is_ard(kid) ? d + 2 : 4); }
+// d(-logML)/dtheta (natural parameters) from the GRAD_N sums of a gradient contraction: dlogML/dtheta = 0.5 sum_ij w_ij dK_ij/dtheta.
+// Matern: the contraction put -2 dk/dr^2 where the squared exponential has k, so the formulas are SE_ARD's.
+__host__ __device__ inline void grad_from_sums(int kid, int d, const double *th, const double *s, double *g) {
+  g[0] = -0.5 * s[0] / th[0];
+  if (kid == K_SE_ISO) {
+    double se = 0.0;
+    for (int q = 0; q < d; ++q) se += s[1 + q];
+    g[1] = -0.5 * se / th[1];
+    g[2] = -0.5 * s[9];
+  } else if (k_is_ard(kid)) {
+    for (int q = 0; q < d; ++q) g[1 + q] = -0.5 * s[1 + q] / th[1 + q];
+    g[d + 1] = -0.5 * s[9];
+  } else {
+    g[1] = -0.5 * s[1] / th[1];
+    g[2] = -0.5 * s[0] / th[2];
+    g[3] = -0.5 * s[9];
+  }
+}
 
 struct FitArgs {
   void *Lw;              // [batch][NT*128 cols][ld rows]

@@ -2751,39 +2751,32 @@ __global__ __launch_bounds__(64 * TRMM_WAVES) void k_trmm_sk(FitArgs p, int k) {
 // MAT = 1 / 2 (fp64): Matern 3/2 / 5/2, a kernel of its own so that the squared-exponential one is the code it was.  S_ell[q] then
 // carries -2 dk/dr^2 in K_ij's place (matern_radial), and the host's SE_ARD formulas turn the sums into the gradient unchanged.
 // --------------------------------------------------------------------------------------------------
-template <typename T, int MAT = 0>
-__global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
-  static_assert(MAT == 0 || sizeof(T) == 8, "the Matern kernels are fp64 only");
-  using P = Prec<T>;
-  using acc_t = typename P::acc_t;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  T *smem = reinterpret_cast<T *>(smem_raw);
-  const int b = blockIdx.y, pair = blockIdx.x;
-  int ti = 0, rem = pair;
+// tile pair -> (ti, tj), ti >= tj: pairs are numbered row by row of the lower triangle
+__device__ __forceinline__ void grad_pair_tiles(int pair, int &ti, int &tj) {
+  ti = 0;
+  int rem = pair;
   while (rem > ti) {
     rem -= ti + 1;
     ++ti;
   }
-  const int tj = rem;  // ti >= tj
-  const T *Lw = reinterpret_cast<const T *>(p.Lw) + (size_t)b * p.lw_stride;
-  const int ld = p.ld, N = p.N, d = p.d, kid = p.kernel_id;
+  tj = rem;
+}
+
+// What k_grad and k_multi_grad (cgp_multi_grad.hpp) share once tile (ti, tj) is in the accumulators: the scaled coordinates
+// [MAXD][128] of the tile's rows and columns go to LDS (the barrier behind them also covers what the caller staged before
+// the call), element (rl, cl) gets its weight from wij(acc[cb][j][r], rl, cl) and is contracted with dK/dtheta, and the
+// workgroup's sums are reduced in a fixed order (wave shuffles, then LDS) into gpart, off-diagonal tiles counted twice.
+template <typename T, int MAT, typename W>
+__device__ __forceinline__ void grad_tile_contract(const FitArgs &p, int b, int pair, int npairs, int ti, int tj,
+                                                   const typename Prec<T>::acc_t (&acc)[NCB][2], T *smem, char *smem_raw, W &&wij) {
+  using P = Prec<T>;
+  const int N = p.N, d = p.d, kid = p.kernel_id;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15;
-  const size_t rb = (size_t)p.NT * TS;
-
-  acc_t acc[NCB][2];
-#pragma unroll
-  for (int cb = 0; cb < NCB; ++cb) acc[cb][0] = acc[cb][1] = acc_t{0, 0, 0, 0};
-  const T *gR = Lw + rb + (size_t)ti * TS + (size_t)(ti * TS) * ld;
-  const T *gC = Lw + rb + (size_t)tj * TS + (size_t)(ti * TS) * ld;
-  mfma_rowpanel_loop<T, false>(acc, gR, (size_t)ld, gC, (size_t)ld, (p.NT - ti) * (TS / KT), smem, tid);
-
-  // inputs of the tile: scaled coordinates [MAXD][128] of rows and columns, alpha of both
   const double *__restrict__ pr = p.prep + (size_t)b * PREP_N;
-  T *xr = smem, *xc = smem + MAXD * TS, *ar = smem + 2 * MAXD * TS, *ac = ar + TS;
+  T *xr = smem, *xc = smem + MAXD * TS;
   const T *__restrict__ Xb = reinterpret_cast<const T *>(p.X) + (size_t)b * d * N;
-  const T *__restrict__ al = reinterpret_cast<const T *>(p.alpha) + (size_t)b * p.alpha_stride;
   const bool brown = kid == K_RBF_BROWNIAN;
   for (int idx = tid; idx < MAXD * TS; idx += 256) {
     const int q = idx >> 7, r = idx & 127;
@@ -2791,11 +2784,6 @@ __global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
     const int gi = ti * TS + r, gj = tj * TS + r;
     xr[idx] = (q < d && gi < N) ? Xb[(size_t)q * N + gi] * sc : T(0);
     xc[idx] = (q < d && gj < N) ? Xb[(size_t)q * N + gj] * sc : T(0);
-  }
-  if (tid < TS) {
-    const int gi = ti * TS + tid, gj = tj * TS + tid;
-    ar[tid] = gi < N ? al[gi] : T(0);
-    ac[tid] = gj < N ? al[gj] : T(0);
   }
   __syncthreads();
   const T amp = T(pr[9]), amp_b = T(pr[10]);
@@ -2813,9 +2801,8 @@ __global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
       for (int j = 0; j < 2; ++j) {
         const int rl = wave * 32 + 2 * l15 + j;
         const int grow = ti * TS + rl;
-        const T kinv = acc[cb][j][r];
         if (grow < N && gcol < N) {
-          const T w = ar[rl] * ac[cl] - kinv;
+          const T w = wij(acc[cb][j][r], rl, cl);
           T kv, dq2[MAXD];
           T kg = T(0);   // what multiplies dq2 in the length-scale sums: k itself, Matern: -2 dk/dr^2
           if (!brown) {
@@ -2880,6 +2867,38 @@ __global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
     const double v = (red[tid] + red[GRAD_N + tid]) + (red[2 * GRAD_N + tid] + red[3 * GRAD_N + tid]);
     p.gpart[((size_t)b * npairs + pair) * GRAD_N + tid] = wgt * v;
   }
+}
+
+template <typename T, int MAT = 0>
+__global__ __launch_bounds__(256, 2) void k_grad(FitArgs p, int npairs) {
+  static_assert(MAT == 0 || sizeof(T) == 8, "the Matern kernels are fp64 only");
+  using acc_t = typename Prec<T>::acc_t;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T *smem = reinterpret_cast<T *>(smem_raw);
+  const int b = blockIdx.y, pair = blockIdx.x, tid = threadIdx.x;
+  int ti, tj;
+  grad_pair_tiles(pair, ti, tj);
+  const T *Lw = reinterpret_cast<const T *>(p.Lw) + (size_t)b * p.lw_stride;
+  const int ld = p.ld, N = p.N;
+  const size_t rb = (size_t)p.NT * TS;
+
+  acc_t acc[NCB][2];
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb) acc[cb][0] = acc[cb][1] = acc_t{0, 0, 0, 0};
+  const T *gR = Lw + rb + (size_t)ti * TS + (size_t)(ti * TS) * ld;
+  const T *gC = Lw + rb + (size_t)tj * TS + (size_t)(ti * TS) * ld;
+  mfma_rowpanel_loop<T, false>(acc, gR, (size_t)ld, gC, (size_t)ld, (p.NT - ti) * (TS / KT), smem, tid);
+
+  // alpha of the tile's rows and columns, behind the coordinates that grad_tile_contract stages (its barrier covers both)
+  T *ar = smem + 2 * MAXD * TS, *ac = ar + TS;
+  const T *__restrict__ al = reinterpret_cast<const T *>(p.alpha) + (size_t)b * p.alpha_stride;
+  if (tid < TS) {
+    const int gi = ti * TS + tid, gj = tj * TS + tid;
+    ar[tid] = gi < N ? al[gi] : T(0);
+    ac[tid] = gj < N ? al[gj] : T(0);
+  }
+  grad_tile_contract<T, MAT>(p, b, pair, npairs, ti, tj, acc, smem, smem_raw,
+                             [&](T kinv, int rl, int cl) { return ar[rl] * ac[cl] - kinv; });
 }
 
 }  // namespace cgp

@@ -1,7 +1,7 @@
 // cgp_multi_grad_host.hpp -- host side of the multi-target objective: value and gradient of -sum_p logml[p] over one shared theta
 // and its L-BFGS (kernels: cgp_multi_grad.hpp).  Not a translation unit of its own: cgp_engine.hip includes it after
-// cgp_multi_host.hpp and after the gradient-mode entry points it builds on (base_args / run as loo_enqueue uses them, mean_diag,
-// upload_theta, the LbfgsStepper loop of cgp_optimize_batch).  fp64 contexts only.
+// cgp_multi_host.hpp and after the gradient-mode entry points it builds on (grad_mode_args / run as loo_enqueue uses them,
+// upload_batch_xy, upload_theta, jitter_ladder).  fp64 contexts only.
 #pragma once
 
 namespace {
@@ -38,18 +38,12 @@ int multi_grad_enqueue(cgp_ctx *c, int slot, int nfit, int N, int d, int P, int 
   MultiArgs ma = multi_args(c, N, 0, P, 0, slot, nfit, dY, dy0, nullptr, nullptr, dlogml, dinfo);
   int rc = multi_pack_launch(c, ma, s);
   if (rc != CGP_OK) return rc;
-  FitArgs a = base_args(c, N, d, /*M=*/N, kid, 0);
-  a.xid = 1;
-  a.X = dX + (size_t)slot * d * N;
-  a.Xs = a.X;  // unused: the "test rows" are the identity
+  FitArgs a = grad_mode_args(c, N, d, kid, dX + (size_t)slot * d * N);
   a.y = dy0 + (size_t)slot * N;
   a.theta = dtheta + (size_t)slot * CGP_MAX_THETA;
   a.jitter = djitter ? djitter + slot : nullptr;
-  a.mean = c->dmean;
-  a.var = c->dvar;
   a.logml = c->dlogml + slot;   // column 0's own logML: a by-product
   a.info = dinfo + slot;
-  a.gpart = c->dgpart;
   rc = run(c, a, nfit, true, true, s);
   if (rc != CGP_OK) return rc;
   const bool h64 = multi_rows64(c, nfit, P);
@@ -100,10 +94,9 @@ int multi_grad_stage(cgp_ctx *c, int batch, int N, int P, MultiGradStage &st) {
   return CGP_OK;
 }
 int multi_grad_upload(cgp_ctx *c, int batch, int N, int d, int P, const double *X, const double *Y, const MultiGradStage &st) {
-  std::vector<char> hx((size_t)batch * N * d * sizeof(double));
-  for (int b = 0; b < batch; ++b) pack_soa(X + (size_t)b * N * d, N, d, CGP_F64, hx, (size_t)b * d * N);
-  HIP_TRY(c, hipMemcpyAsync(c->dX, hx.data(), hx.size(), hipMemcpyHostToDevice, c->stream));   // pageable sources: staged by the
-  HIP_TRY(c, hipMemcpyAsync(st.dY, Y, (size_t)batch * P * N * sizeof(double), hipMemcpyHostToDevice, c->stream));   // runtime before the calls return
+  const int rc = upload_batch_xy(c, batch, N, d, X, nullptr, c->stream);   // Y travels as it is: k_multi_pack reads it in place
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(st.dY, Y, (size_t)batch * P * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return CGP_OK;
 }
 int multi_grad_eval_host(cgp_ctx *c, int batch, int N, int d, int P, int kid, const double *X, const double *theta, int theta_stride,
@@ -116,18 +109,12 @@ int multi_grad_eval_host(cgp_ctx *c, int batch, int N, int d, int P, int kid, co
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(info, c->dinfo, sizeof(int) * batch, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  for (int b = 0; b < batch; ++b) {
-    if (info[b] == 0 || (skip && (*skip)[b])) continue;
-    double jit = mean_diag(kid, theta + (size_t)b * theta_stride, d, X + (size_t)b * N * d, N) * 1e-6;
-    for (int attempt = 0; attempt < 5 && info[b] != 0; ++attempt, jit *= 10.0) {
-      HIP_TRY(c, hipMemcpyAsync(c->djitter + b, &jit, sizeof(double), hipMemcpyHostToDevice, s));
-      rc = multi_grad_enqueue(c, b, 1, N, d, P, kid, dX, st.dY, c->dtheta, c->djitter, st.dnll, st.dgrad, CGP_MAX_THETA, st.dlogml,
+  std::vector<double> jit(batch);
+  rc = jitter_ladder(c, batch, N, d, kid, theta, theta_stride, X, info, skip, jit.data(), s, [&](int b) {
+    return multi_grad_enqueue(c, b, 1, N, d, P, kid, dX, st.dY, c->dtheta, c->djitter, st.dnll, st.dgrad, CGP_MAX_THETA, st.dlogml,
                               c->dinfo, s);
-      if (rc != CGP_OK) return rc;
-      HIP_TRY(c, hipMemcpyAsync(&info[b], c->dinfo + b, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIP_TRY(c, hipStreamSynchronize(s));
-    }
-  }
+  });
+  if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(nll, st.dnll, sizeof(double) * batch, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(grad, st.dgrad, sizeof(double) * batch * CGP_MAX_THETA, hipMemcpyDeviceToHost, s));
   if (logml) HIP_TRY(c, hipMemcpyAsync(logml, st.dlogml, sizeof(double) * batch * P, hipMemcpyDeviceToHost, s));
@@ -217,52 +204,32 @@ extern "C" int cgp_optimize_multi_batch(cgp_ctx *c, int batch, int N, int d, int
   MultiGradStage stg{};
   if ((rc = multi_grad_stage(c, batch, N, P, stg)) != CGP_OK) return rc;
   if ((rc = multi_grad_upload(c, batch, N, d, P, X, Y, stg)) != CGP_OK) return rc;
-  // cgp_optimize_batch's host loop (Logexp transform, pgtol 1e-5, factr 1e7) over the summed objective
-  auto to_theta = [](double x) { return x > 35.0 ? x : std::log1p(std::exp(x)); };
-  auto to_x = [](double th) { return th > 35.0 ? th : std::log(std::expm1(th)); };
-  const int cap = max_evals > 0 ? max_evals : 1000;
-  std::vector<corenav::LbfgsStepper> st;
-  st.reserve(batch);
-  for (int b = 0; b < batch; ++b) {
-    std::vector<double> x0(nth);
-    for (int i = 0; i < nth; ++i) x0[i] = to_x(theta[(size_t)b * theta_stride + i]);
-    st.emplace_back(x0, cap, 1e-5, 1e7);
-  }
-  std::vector<double> th((size_t)batch * nth), hth, nll(batch), hg((size_t)batch * CGP_MAX_THETA), gx(nth);
+  // the batched L-BFGS driver over the summed objective; a finished fit is evaluated at its best point and never retried
+  std::vector<double> hth, nll(batch), hg((size_t)batch * CGP_MAX_THETA);
   std::vector<int> info(batch);
   std::vector<char> skip(batch, 0);
-  for (int round = 0; round < cap + 40; ++round) {
-    bool any = false;
-    for (int b = 0; b < batch; ++b) {
-      any = any || !st[b].done();
-      skip[b] = st[b].done();
-      const std::vector<double> &xx = st[b].done() ? st[b].best() : st[b].trial();
-      for (int i = 0; i < nth; ++i) th[(size_t)b * nth + i] = std::max(to_theta(xx[i]), 1e-300);
-    }
-    if (!any) break;
-    if ((rc = upload_theta(c, th.data(), nth, nth, batch, c->stream, hth)) != CGP_OK) return rc;
+  auto round = [&](const double *th, const char *active, double *f, double *g, char *feasible) -> int {
+    for (int b = 0; b < batch; ++b) skip[b] = !active[b];
+    int rc = upload_theta(c, th, nth, nth, batch, c->stream, hth);
+    if (rc != CGP_OK) return rc;
     // GPy jitchol inside m.optimize(): a trial point whose matrix is not positive definite climbs the ladder; one that stays
     // infeasible is +inf for the line search
-    rc = multi_grad_eval_host(c, batch, N, d, P, kid, X, th.data(), nth, stg, &skip, nll.data(), hg.data(), nullptr, info.data());
+    rc = multi_grad_eval_host(c, batch, N, d, P, kid, X, th, nth, stg, &skip, nll.data(), hg.data(), nullptr, info.data());
     if (rc != CGP_OK) return rc;
     for (int b = 0; b < batch; ++b) {
-      if (st[b].done()) continue;
-      const double *tb = th.data() + (size_t)b * nth, *g = hg.data() + (size_t)b * CGP_MAX_THETA;
-      double f = INFINITY;
-      if (info[b] == 0) {
-        const std::vector<double> &xx = st[b].trial();
-        for (int i = 0; i < nth; ++i) gx[i] = g[i] * (xx[i] > 35.0 ? 1.0 : -std::expm1(-tb[i]));
-        f = nll[b];
-      }
-      st[b].tell(f, gx);
+      if (!active[b]) continue;
+      feasible[b] = info[b] == 0;
+      f[b] = nll[b];
+      std::copy(hg.data() + (size_t)b * CGP_MAX_THETA, hg.data() + (size_t)b * CGP_MAX_THETA + nth, g + (size_t)b * nth);
     }
-  }
+    return CGP_OK;
+  };
+  corenav::LbfgsBatchResult res;
+  if ((rc = corenav::lbfgs_minimize_logexp_batch(batch, nth, theta, theta_stride, nullptr, max_evals, round, res)) != CGP_OK) return rc;
   for (int b = 0; b < batch; ++b) {
-    const std::vector<double> &xb = st[b].best();
-    for (int i = 0; i < nth; ++i) theta[(size_t)b * theta_stride + i] = to_theta(xb[i]);
-    const corenav::LbfgsResult r = st[b].result();
-    if (logml_sum) logml_sum[b] = -r.f;
-    if (n_evals) n_evals[b] = r.evals;
+    for (int i = 0; i < nth; ++i) theta[(size_t)b * theta_stride + i] = res.theta[(size_t)b * nth + i];
+    if (logml_sum) logml_sum[b] = -res.f[b];
+    if (n_evals) n_evals[b] = res.evals[b];
   }
   return CGP_OK;
 }

@@ -897,7 +897,7 @@ __device__ __attribute__((noinline)) void sm_lbfgs_tell_wave(corenav::LbfgsCore 
 }
 
 // Wave 0 after an evaluation, one lane per parameter: the gradient component from the sums (the host twin is
-// grad_from_sums, cgp_engine.hip), then either the L-BFGS step (OPT) or the outputs (EVAL).
+// grad_from_sums, cgp_kernels.hpp), then either the L-BFGS step (OPT) or the outputs (EVAL).
 __device__ __forceinline__ void sm_wave0_tell(const SmallLds &s, const SmallArgs &p, int kid, int d, int nth, double *ob, int lane) {
   const bool ok = s.flag[0] == 0;
   const int j = lane & 15;

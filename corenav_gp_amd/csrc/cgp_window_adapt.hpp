@@ -556,22 +556,8 @@ __global__ __launch_bounds__(64) void k_window_grad_finish(AdaptArgs p) {
   for (int i = 0; i < GRAD_N; ++i) s[i] = 0.0;
   for (int J = 0; J < nb; ++J)
     for (int i = 0; i < GRAD_N; ++i) s[i] += p.gpart[((size_t)w * p.NB + J) * GRAD_N + i];
-  const double *th = p.theta + (size_t)w * MAX_THETA;
   p.nll[w] = p.nllv[w];
-  g[0] = -0.5 * s[0] / th[0];
-  if (kid == K_SE_ISO) {
-    double se = 0.0;
-    for (int q = 0; q < d; ++q) se += s[1 + q];
-    g[1] = -0.5 * se / th[1];
-    g[2] = -0.5 * s[9];
-  } else if (k_is_ard(kid)) {
-    for (int q = 0; q < d; ++q) g[1 + q] = -0.5 * s[1 + q] / th[1 + q];
-    g[d + 1] = -0.5 * s[9];
-  } else {
-    g[1] = -0.5 * s[1] / th[1];
-    g[2] = -0.5 * s[0] / th[2];
-    g[3] = -0.5 * s[9];
-  }
+  grad_from_sums(kid, d, p.theta + (size_t)w * MAX_THETA, s, g);
 }
 
 }  // namespace cgp

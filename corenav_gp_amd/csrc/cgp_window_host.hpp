@@ -723,8 +723,8 @@ extern "C" int cgp_window_loo(cgp_ctx *c, double *loo_mean, double *loo_var, dou
   return CGP_OK;
 }
 
-// m.optimize() on the resident windows: cgp_optimize_batch's host loop (one batched evaluation per round, every window its own
-// LbfgsStepper and line search) with set_theta + nll_grad on the windows themselves as the evaluation.
+// m.optimize() on the resident windows: the batched L-BFGS driver of cgp_optimize_batch (one batched evaluation per round, every
+// window its own stepper and line search) with set_theta + nll_grad on the windows themselves as the evaluation.
 extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
                                    double *logml_out, int *n_evals) {
   if (!c || c->nwin < 1) return CGP_ESTATE;
@@ -733,7 +733,6 @@ extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned cha
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t W = c->nwin;
-  const int cap = max_evals > 0 ? max_evals : 1000;
   std::vector<double> cur(W * MAX_THETA);
   HIP_TRY(c, hipStreamSynchronize(s));
   HIP_TRY(c, hipMemcpy(cur.data(), c->win.theta, cur.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -741,15 +740,6 @@ extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned cha
   for (size_t w = 0; w < W; ++w)
     for (int i = 0; i < nth; ++i)
       if (sel(w) && !(cur[w * MAX_THETA + i] > 0.0)) return CGP_EINVAL;
-  auto to_theta = [](double x) { return x > 35.0 ? x : std::log1p(std::exp(x)); };
-  auto to_x = [](double th) { return th > 35.0 ? th : std::log(std::expm1(th)); };
-  std::vector<corenav::LbfgsStepper> st;
-  st.reserve(W);
-  for (size_t w = 0; w < W; ++w) {
-    std::vector<double> x0(nth);
-    for (int i = 0; i < nth; ++i) x0[i] = sel(w) ? to_x(cur[w * MAX_THETA + i]) : 0.0;
-    st.emplace_back(x0, cap, 1e-5, 1e7);
-  }
   // staging: [theta | nll | grad | logml | info | select], pinned and on the device
   const size_t nt = W * nth, ni = (W + 1) / 2, ns = (W + 7) / 8, ndbl = 2 * nt + 2 * W + ni + ns;
   double *h, *d;
@@ -758,69 +748,47 @@ extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned cha
   int *hinfo = reinterpret_cast<int *>(hlm + W);
   unsigned char *hsel = reinterpret_cast<unsigned char *>(hlm + W + ni);
   const size_t o_nll = nt, o_grad = nt + W, o_lm = 2 * nt + W, o_info = o_lm + W, o_sel = o_info + ni;
-  std::vector<double> gx(nth);
-  std::vector<char> at_best(W, 1);   // the window holds the factor of its stepper's best point
   auto set_theta = [&]() -> int {    // the windows marked in hsel take hth
     HIP_TRY(c, hipMemcpyAsync(d, hth, nt * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(d + o_sel, hsel, ns * 8, hipMemcpyHostToDevice, s));
     return cgp_window_set_theta_device(c, d, nth, reinterpret_cast<unsigned char *>(d + o_sel), d + o_lm, reinterpret_cast<int *>(d + o_info), s);
   };
-  for (int round = 0; round < cap + 40; ++round) {
-    bool any = false;
-    for (size_t w = 0; w < W; ++w) {
-      const bool act = sel(w) && !st[w].done();
-      hsel[w] = act ? 1 : 0;
-      any = any || act;
-      const std::vector<double> &xx = st[w].trial();
-      for (int i = 0; i < nth; ++i) hth[w * nth + i] = act ? std::max(to_theta(xx[i]), 1e-300) : cur[w * MAX_THETA + i];
-    }
-    if (!any) break;
+  // one round: the active windows take their trial theta and are evaluated where they stand; the others stay deselected, with
+  // the theta they have.  A trial point that is not positive definite is infeasible (no jitter ladder).
+  auto round = [&](const double *th, const char *active, double *f, double *g, char *feasible) -> int {
+    memcpy(hth, th, nt * sizeof(double));
+    for (size_t w = 0; w < W; ++w) hsel[w] = active[w] ? 1 : 0;
     int rc = set_theta();
     if (rc != CGP_OK) return rc;
     rc = cgp_window_nll_grad_device(c, d + o_nll, d + o_grad, nth, s);
     if (rc != CGP_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(hnll, d + o_nll, (2 * W + nt + ni) * 8, hipMemcpyDeviceToHost, s));   // nll | grad | logml | info
     HIP_TRY(c, hipStreamSynchronize(s));
-    for (size_t w = 0; w < W; ++w) {
-      if (!hsel[w]) continue;
-      const double *tb = hth + w * nth;
-      for (int i = 0; i < nth; ++i) cur[w * MAX_THETA + i] = tb[i];
-      double f = INFINITY;
-      if (hinfo[w] == 0 && std::isfinite(hnll[w])) {   // a trial point that is not positive definite is infeasible (no jitter ladder)
-        const std::vector<double> &xx = st[w].trial();
-        for (int i = 0; i < nth; ++i) gx[i] = hgrad[w * nth + i] * (xx[i] > 35.0 ? 1.0 : -std::expm1(-tb[i]));
-        f = hnll[w];
-      } else {
-        std::fill(gx.begin(), gx.end(), 0.0);
-      }
-      const std::vector<double> xt = st[w].trial();
-      st[w].tell(f, gx);
-      at_best[w] = st[w].best() == xt;
-    }
-  }
+    for (size_t w = 0; w < W; ++w) feasible[w] = hinfo[w] == 0 && std::isfinite(hnll[w]);
+    memcpy(f, hnll, W * sizeof(double));
+    memcpy(g, hgrad, nt * sizeof(double));
+    return CGP_OK;
+  };
+  corenav::LbfgsBatchResult res;
+  int rc = corenav::lbfgs_minimize_logexp_batch((int)W, nth, cur.data(), MAX_THETA, select, max_evals, round, res);
+  if (rc != CGP_OK) return rc;
   // a window whose last trial was not its best point gets the best theta's factor back
   bool again = false;
   for (size_t w = 0; w < W; ++w) {
-    hsel[w] = 0;
-    if (!sel(w)) continue;
-    const std::vector<double> &xb = st[w].best();
-    for (int i = 0; i < nth; ++i) hth[w * nth + i] = std::max(to_theta(xb[i]), 1e-300);
-    if (!at_best[w]) {
-      hsel[w] = 1;
-      again = true;
-    }
+    hsel[w] = sel(w) && !res.last_is_best[w];
+    again = again || hsel[w];
+    for (int i = 0; i < nth; ++i) hth[w * nth + i] = std::max(res.theta[w * nth + i], 1e-300);
   }
   if (again) {
-    int rc = set_theta();
+    rc = set_theta();
     if (rc != CGP_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
   }
   for (size_t w = 0; w < W; ++w) {
     if (!sel(w)) continue;
-    const corenav::LbfgsResult r = st[w].result();
     if (theta_out) memcpy(theta_out + w * theta_stride, hth + w * nth, nth * sizeof(double));
-    if (logml_out) logml_out[w] = -r.f;
-    if (n_evals) n_evals[w] = r.evals;
+    if (logml_out) logml_out[w] = -res.f[w];
+    if (n_evals) n_evals[w] = res.evals[w];
   }
   return CGP_OK;
 }

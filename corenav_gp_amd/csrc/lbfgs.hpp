@@ -2,11 +2,13 @@
 // role scipy.optimize.fmin_l_bfgs_b (no bounds) plays under GPy's `m.optimize()`
 // (core_navigation/script/gp_slip_node.py:36; paramz 'lbfgsb': factr 1e7, pgtol 1e-5, maxfun 1000).
 // Written as an ask/tell stepper so that many independent problems can share one batched objective
-// evaluation per round (cgp_optimize_batch); lbfgs_minimize drives a single stepper.
+// evaluation per round; lbfgs_minimize drives a single stepper, lbfgs_minimize_logexp_batch a batch of
+// them over positive parameters (cgp_optimize_batch, cgp_optimize_multi_batch, cgp_window_optimize).
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <cstddef>
 #include <vector>
 
 #include "lbfgs_core.hpp"
@@ -62,6 +64,88 @@ inline LbfgsResult lbfgs_minimize(const std::function<double(const std::vector<d
   }
   x = st.best();
   return st.result();
+}
+
+// Logexp transform of a positive parameter (GPy paramz.transformations.Logexp): theta = log(1 + exp(x)), its inverse,
+// and dtheta/dx = 1 - exp(-theta)
+inline double logexp_theta(double x) { return x > 35.0 ? x : std::log1p(std::exp(x)); }
+inline double logexp_x(double th) { return th > 35.0 ? th : std::log(std::expm1(th)); }
+inline double logexp_dtheta_dx(double x, double th) { return x > 35.0 ? 1.0 : -std::expm1(-th); }
+// the theta an objective is evaluated at: never exactly zero
+inline double logexp_theta_eval(double x) { return std::max(logexp_theta(x), 1e-300); }
+
+struct LbfgsBatchResult {
+  std::vector<double> theta;        // [n][nth] logexp_theta(best point) of a selected problem, theta0 of an unselected one
+  std::vector<double> f;            // [n] the objective there
+  std::vector<int> evals, status;   // [n] (LbfgsResult)
+  std::vector<char> last_is_best;   // [n] the last point the problem was evaluated at is its best point
+  int rounds = 0;                   // calls of the evaluation
+};
+
+// One evaluation of the whole batch: theta [n][nth] (a selected problem that has finished stands at its best point, an
+// unselected one at its theta0) and active [n] in; f [n], the gradient with respect to theta [n][nth] and feasible [n] out,
+// for the active problems only.  Returns 0, or a code that ends the run.
+using LbfgsBatchEval = std::function<int(const double *theta, const char *active, double *f, double *grad, char *feasible)>;
+
+// n independent minimisations over theta > 0 (nth parameters each, Logexp-transformed; pgtol 1e-5, factr 1e7) that share one
+// evaluation per round: each selected problem is the lbfgs_minimize run of its own transformed objective, where an infeasible
+// point counts as +inf.  select == nullptr selects every problem; theta0 of a selected problem must be positive.  Ends when
+// no problem is active, after max_evals + 40 rounds at the latest (max_evals <= 0: 1000).  Returns 0 or eval's code.
+inline int lbfgs_minimize_logexp_batch(int n, int nth, const double *theta0, size_t theta_stride, const unsigned char *select,
+                                       int max_evals, const LbfgsBatchEval &eval, LbfgsBatchResult &out) {
+  const int cap = max_evals > 0 ? max_evals : 1000;
+  auto sel = [&](int b) { return !select || select[b] != 0; };
+  std::vector<LbfgsStepper> st;
+  st.reserve(n);
+  std::vector<double> x0(nth);
+  for (int b = 0; b < n; ++b) {
+    for (int i = 0; i < nth; ++i) x0[i] = sel(b) ? logexp_x(theta0[b * theta_stride + i]) : 0.0;
+    st.emplace_back(x0, cap, 1e-5, 1e7);
+  }
+  const size_t nt = (size_t)n * nth;
+  std::vector<double> th(nt), f(n, 0.0), g(nt, 0.0), gx(nth, 0.0);
+  std::vector<char> active(n, 0), feasible(n, 0);
+  out.last_is_best.assign(n, 1);
+  out.rounds = 0;
+  for (int round = 0; round < cap + 40; ++round) {
+    bool any = false;
+    for (int b = 0; b < n; ++b) {
+      active[b] = sel(b) && !st[b].done();
+      any = any || active[b];
+      const std::vector<double> &xx = active[b] ? st[b].trial() : st[b].best();
+      for (int i = 0; i < nth; ++i) th[(size_t)b * nth + i] = sel(b) ? logexp_theta_eval(xx[i]) : theta0[b * theta_stride + i];
+    }
+    if (!any) break;
+    const int rc = eval(th.data(), active.data(), f.data(), g.data(), feasible.data());
+    if (rc != 0) return rc;
+    ++out.rounds;
+    for (int b = 0; b < n; ++b) {
+      if (!active[b]) continue;
+      const std::vector<double> xt = st[b].trial();
+      const double *tb = th.data() + (size_t)b * nth, *gb = g.data() + (size_t)b * nth;
+      double fv = INFINITY;   // tell() gives an infeasible point a zero gradient itself
+      if (feasible[b]) {
+        for (int i = 0; i < nth; ++i) gx[i] = gb[i] * logexp_dtheta_dx(xt[i], tb[i]);
+        fv = f[b];
+      }
+      st[b].tell(fv, gx);
+      out.last_is_best[b] = st[b].best() == xt;
+    }
+  }
+  out.theta.resize(nt);
+  out.f.assign(n, 0.0);
+  out.evals.assign(n, 0);
+  out.status.assign(n, 0);
+  for (int b = 0; b < n; ++b) {
+    const std::vector<double> &xb = st[b].best();
+    for (int i = 0; i < nth; ++i) out.theta[(size_t)b * nth + i] = sel(b) ? logexp_theta(xb[i]) : theta0[b * theta_stride + i];
+    if (!sel(b)) continue;
+    const LbfgsResult r = st[b].result();
+    out.f[b] = r.f;
+    out.evals[b] = r.evals;
+    out.status[b] = r.status;
+  }
+  return 0;
 }
 
 }  // namespace corenav
