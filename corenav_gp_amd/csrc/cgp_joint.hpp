@@ -7,17 +7,18 @@
 // [NT 128, NT 128 + M) of slab b, column-major, every block column stored), so the covariance needs no second solve:
 //   k_joint_cov           cov(J, I) = K**(J, I) - sum_c V^T(J, c) V^T(I, c) on v_mfma_f64_16x16x4_f64, operands straight from the
 //                         slab: for a fixed column c the 64 rows of a super-tile's side are 512 contiguous bytes.  The scheme is
-//                         k_window_joint_cov's: one WAVE owns a 64 x 64 super-tile of the lower triangle and runs the whole sum
-//                         over c itself, in column order (no split over waves, no atomics: a fit's result is a function of its own
-//                         data only, whatever its slot and its neighbours); the Gram tile, evaluated in registers from the SoA test
-//                         points, is the accumulators' start value; the next 16 columns' operands are requested before this
-//                         block's MFMAs; the workgroups of a fit run on one XCD, so its V rows come from HBM once.  The sum runs
-//                         over the REAL N columns: the last, partial block of 16 is read masked, after the prefetched loop.
-//                         Output form: both triangles of the caller's (M, M) matrix from the same register, the diagonal
-//                         replaced by the fit's own variance (clip and noise included).  Scratch form (sampling): the lower
-//                         triangle, column-major, leading dimension M padded to 16, identity in the padding -- what
-//                         k_window_joint_chol / k_window_joint_paths (cgp_window_joint.hpp) read; they are launched unchanged
-//                         with the fit index where they take a window index.
+//                         k_window_joint_cov's, written out a second time (a shared super-tile body was slower for the windows:
+//                         docs/negatives.md item 20; a fix goes into both kernels): one WAVE owns a 64 x 64 super-tile of the lower
+//                         triangle and runs the whole sum over c itself, in column order (no split over waves, no atomics: a fit's
+//                         result is a function of its own data only, whatever its slot and its neighbours); the Gram tile,
+//                         evaluated in registers from the SoA test points, is the accumulators' start value; the next 16 columns'
+//                         operands are requested before this block's MFMAs; the workgroups of a fit run on one XCD, so its V rows
+//                         come from HBM once.  The sum runs over the REAL N columns: the last, partial block of 16 is read masked,
+//                         after the prefetched loop.  Output form: both triangles of the caller's (M, M) matrix from the same
+//                         register, the diagonal replaced by the fit's own variance (clip and noise included).  Scratch form
+//                         (sampling): the lower triangle, column-major, leading dimension M padded to 16, identity in the padding
+//                         -- what k_window_joint_chol / k_window_joint_paths (cgp_window_joint.hpp) read; they are launched
+//                         unchanged with the fit index where they take a window index.
 // A fit whose info word is set gets NaN in all of its covariance (and, through the factorisation's failure word, in its paths).
 // Read-only on the factor panel.  fp64 only.
 #pragma once
@@ -42,7 +43,6 @@ struct JointFitArgs {
 
 template <bool SCRATCH>
 __global__ __launch_bounds__(WJ_THREADS) void k_joint_cov(JointFitArgs p) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
   // workgroup -> (fit, group of super-tile pairs): consecutive ids on ONE XCD
   const int per = gridDim.x / WF_XCDS;
   const int lid = (blockIdx.x % WF_XCDS) * per + blockIdx.x / WF_XCDS;
@@ -57,14 +57,7 @@ __global__ __launch_bounds__(WJ_THREADS) void k_joint_cov(JointFitArgs p) {
   const int BJ = pair - BI * (BI + 1) / 2;   // BJ <= BI
   const int M = p.M, N = p.N, mt = p.mt, d = p.d, kid = p.kernel_id;
   const bool bad = p.info != nullptr && p.info[f] != 0;
-  const double *th = p.theta + (size_t)f * MAX_THETA;
-  WaCov cv;
-  cv.kid = kid;
-  cv.d = d;
-#pragma unroll
-  for (int q = 0; q < MAXD; ++q) cv.pr[q] = q < d ? 1.0 / (k_is_ard(kid) ? th[1 + q] : th[1]) : 0.0;   // k_prep's
-  cv.amp = th[0];
-  cv.ampb = kid == K_RBF_BROWNIAN ? th[2] : 0.0;
+  const WaCov cv = WaCov::from_theta(kid, d, p.theta + (size_t)f * MAX_THETA);
   const double *xs = p.Xs + (size_t)f * d * M;
   // tile (b, a): rows j = (BJ 4 + b) 16 + lq + 4 r (A operand), columns i = (BI 4 + a) 16 + l15 (B operand)
   auto live = [&](int b, int a) { return BI * WJ_ST + a < mt && BJ * WJ_ST + b <= BI * WJ_ST + a; };

@@ -1,7 +1,8 @@
 // cgp_joint_host.hpp -- host side of the joint forecast after batch / single fits (kernel: cgp_joint.hpp; the factorisation and the
 // paths are the windows' k_window_joint_chol / k_window_joint_paths, launched with the fit index).  Not a translation unit of its
 // own: cgp_engine.hip includes it after the fit entry points it builds on (fit_predict_device, fit_predict_batch_host,
-// predict_enqueue).  fp64 contexts only: every entry point answers CGP_EINVAL in a CGP_F32 context before anything is enqueued.
+// predict_enqueue) and after cgp_window_host.hpp, whose joint_cov_grid and joint_chol_paths_launch the launches here use.
+// fp64 contexts only: every entry point answers CGP_EINVAL in a CGP_F32 context before anything is enqueued.
 #pragma once
 
 namespace {
@@ -22,7 +23,8 @@ void joint_free(cgp_ctx *c) {   // (declared in cgp_engine.hip for cgp_destroy)
 int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, const double *dXs,
                      const double *dtheta, const double *dvar, const int *dinfo, hipStream_t s) {
   JointFitArgs j{};
-  j.mt = cdiv(M, WPB);
+  const unsigned grid = joint_cov_grid(M, nfit, j.mt, j.nsup, j.npair, j.per_fit);
+  if (grid == 0) return CGP_EINVAL;
   const size_t mpad = (size_t)j.mt * WPB;
   j.Lw = static_cast<const double *>(c->Lw) + (size_t)slab * c->lw_stride;
   j.lw_stride = c->lw_stride;
@@ -35,19 +37,14 @@ int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int ki
   j.cov = h.dcov ? h.dcov + (size_t)slot * M * M : nullptr;
   j.C = static_cast<double *>(c->fjbuf[0]) + (size_t)slot * mpad * mpad;
   j.N = N; j.d = d; j.M = M; j.kernel_id = kid; j.nfit = nfit;
-  j.nsup = cdiv(j.mt, WJ_ST);
-  j.npair = j.nsup * (j.nsup + 1) / 2;
-  j.per_fit = cdiv(j.npair, WJ_WAVES);
-  const long long total = (long long)nfit * j.per_fit;
-  if (total > (1ll << 30)) return CGP_EINVAL;
-  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
   if (h.dcov) hipLaunchKernelGGL(k_joint_cov<false>, dim3(grid), dim3(WJ_THREADS), 0, s, j);
   else hipLaunchKernelGGL(k_joint_cov<true>, dim3(grid), dim3(WJ_THREADS), 0, s, j);
   if (!hip_ok(c, hipGetLastError(), "joint covariance launch")) return CGP_EHIP;
   return CGP_OK;
 }
 
-// C C^T = scratch matrix + jitter I in place, then out = mean + C xi, for the fits in slots [0, nfit): the windows' kernels
+// C C^T = scratch matrix + jitter I in place, then out = mean + C xi, for the fits in slots [0, nfit): the windows' kernels through
+// the windows' launcher (joint_chol_paths_launch, cgp_window_host.hpp)
 int joint_paths_launch(cgp_ctx *c, int nfit, int M, int S, const double *dmean, const double *dvar, const double *dxi, double jitter_rel,
                        double *dout, int *dsinfo, hipStream_t s) {
   JointArgs j{};
@@ -57,12 +54,8 @@ int joint_paths_launch(cgp_ctx *c, int nfit, int M, int S, const double *dmean, 
   j.jitter_rel = jitter_rel;
   j.M = M; j.S = S; j.nwin = nfit;
   j.mt = cdiv(M, WPB);
-  const long long per_fit = ((long long)j.mt * cdiv(S, WPB) + WJ_WAVES - 1) / WJ_WAVES;   // one wave per 16 x 16 tile of the paths
-  if (per_fit * nfit > (1ll << 30)) return CGP_EINVAL;
-  j.per_win = (int)per_fit;
-  if (j.mt <= 4 * WA_WAVES) hipLaunchKernelGGL(k_window_joint_chol<4>, dim3(nfit), dim3(WA_THREADS), 0, s, j);
-  else hipLaunchKernelGGL(k_window_joint_chol<8>, dim3(nfit), dim3(WA_THREADS), 0, s, j);
-  hipLaunchKernelGGL(k_window_joint_paths, dim3((unsigned)(j.per_win * nfit)), dim3(WJ_THREADS), 0, s, j);
+  const int rc = joint_chol_paths_launch(j, nfit, s);
+  if (rc != CGP_OK) return rc;
   if (!hip_ok(c, hipGetLastError(), "joint sample launches")) return CGP_EHIP;
   return CGP_OK;
 }

@@ -63,10 +63,34 @@ struct AdaptArgs {
   int N, CAP, d, kernel_id, nwin, NB;
 };
 
+typedef double d4 __attribute__((ext_vector_type(4)));   // one lane's share of a 16 x 16 fp64 MFMA tile
+
 // the covariance of two points held in registers: win_cov's formulas (as k_window_forecast evaluates K*)
 struct WaCov {
   double pr[MAXD], amp, ampb;
   int kid, d;
+  // from theta in natural parameters: the prep record's fields as cgp_window_init derives them on the host
+  static __device__ __forceinline__ WaCov from_theta(int kid, int d, const double *th) {
+    WaCov cv;
+    cv.kid = kid;
+    cv.d = d;
+#pragma unroll
+    for (int q = 0; q < MAXD; ++q) cv.pr[q] = q < d ? 1.0 / (k_is_ard(kid) ? th[1 + q] : th[1]) : 0.0;
+    cv.amp = th[0];
+    cv.ampb = kid == K_RBF_BROWNIAN ? th[2] : 0.0;
+    return cv;
+  }
+  // from a window's prep record
+  static __device__ __forceinline__ WaCov from_prep(int kid, int d, const double *pr) {
+    WaCov cv;
+    cv.kid = kid;
+    cv.d = d;
+#pragma unroll
+    for (int q = 0; q < MAXD; ++q) cv.pr[q] = q < d ? pr[q] : 0.0;
+    cv.amp = pr[9];
+    cv.ampb = pr[10];
+    return cv;
+  }
   __device__ __forceinline__ double kss(double x0) const { return kid == K_RBF_BROWNIAN ? amp * ampb * fabs(x0) : amp; }
   // k(a, b) for a != b; dq2[q] = the squared length-scaled differences (Brownian: dq2[0] = r^2 / ell^2) for the gradient.
   // Matern: dq2 comes back times (-2 dk/dr^2) / k = 3 / (1 + s) resp. (5/3) (1 + s) / (1 + s + s^2 / 3) -- a quotient whose
@@ -117,7 +141,6 @@ __device__ __forceinline__ int wa_ntheta(int kid, int d) { return k_ntheta(kid, 
 // ---------------------------------------------------------------------------------------------------------------------
 template <int TPW, bool MAT = false>   // MAT: the windows hold a Matern kernel (an instantiation of its own)
 __global__ __launch_bounds__(WA_THREADS) void k_window_refactor(AdaptArgs p) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
   __shared__ double tile[WPB * WPB];   // the diagonal tile, [c * 16 + r]
   __shared__ double winv[WPB * WPB];   // L(J, J)^-1, element (row m, column k) at k * 16 + m
   __shared__ double red[4];
@@ -132,6 +155,7 @@ __global__ __launch_bounds__(WA_THREADS) void k_window_refactor(AdaptArgs p) {
   const int o = st[0], n = st[1];
   // the new theta and its derived record (what cgp_window_init computes on the host)
   const double *tn = p.new_theta + (size_t)w * p.theta_stride;
+  // written out, not WaCov::from_theta: the factory compiles this kernel to another, slower listing (docs/negatives.md item 20)
   WaCov cv;
   cv.kid = kid;
   cv.d = d;
@@ -387,36 +411,23 @@ __global__ __launch_bounds__(256) void k_window_alpha(AdaptArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_window_kinv_grad(AdaptArgs p) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
-  const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long long gid = (long long)blockIdx.x * 4 + wave;
-  if (gid >= (long long)p.nwin * p.NB) return;
-  const int w = (int)(gid / p.NB), J = (int)(gid - (long long)w * p.NB);
-  const int CAP = p.CAP, d = p.d, kid = p.kernel_id;
-  const int o = p.state[w * 4], n = p.state[w * 4 + 1], bad = p.state[w * 4 + 2];
-  const int nb = (n + WPB - 1) / WPB;
-  double *gp = p.gpart + ((size_t)w * p.NB + J) * GRAD_N;
-  if (bad != 0 || J >= nb) {
-    if (lane < GRAD_N) gp[lane] = 0.0;
-    return;
-  }
-  double *S = p.L + (size_t)w * CAP * CAP + (size_t)o * CAP + o;   // the window's (0, 0): lower triangle read, strict upper triangle scratch
-  const double *xw = p.xw + (size_t)w * d * CAP + o;
-  const double *dinv = p.dinv + (size_t)w * p.NB * (WPB * WPB);
-  const double *alpha = p.alpha + (size_t)w * p.NB * WPB;
-  const double *pr = p.prep + (size_t)w * PREP_N;
+// Forward half of a wave's work unit (one window x the chunk of 16 columns of block J), shared by k_window_kinv_grad and
+// k_window_loo (cgp_window_loo.hpp): V = L^-1 E for the chunk.  V(J) = L(J, J)^-1 stays in registers and is returned (register r =
+// rows lq + 4 r, column l15); V(I) = L(I, I)^-1 (- sum_{J <= K < I} L(I, K) V(K)) for I > J goes, transposed, into the chunk's
+// tile row of S's strict upper triangle.  L(I, K) is the A operand down the slab's columns, V(K) the B operand.
+// SUMSQ: ss = this lane's share of column l15's sum of squares over the window's rows (identity rows past it are not counted).
+template <bool SUMSQ>
+__device__ __forceinline__ d4 chunk_forward_solve(double *S, const double *dinv, int CAP, int n, int nb, int J, int l15, int lq, double &ss) {
   const int J0 = J * WPB;
-  const int gj = J0 + l15;
-  const bool colok = gj < n;
-  // V(J) = L(J, J)^-1 stays in registers: register r = rows lq + 4 r, column l15
+  const bool colok = J0 + l15 < n;
+  double *Sc = S + J0 + l15;
   d4 VJ;
+  if (SUMSQ) ss = 0.0;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) VJ[r] = dinv[(size_t)J * (WPB * WPB) + l15 * WPB + lq + 4 * r];
-  double *Sc = S + J0 + l15;   // + row * CAP: element (row, chunk column l15) of V / U, transposed into the chunk's tile row
-
-  // ---- forward: V(I) = L(I, I)^-1 (- sum_{J <= K < I} L(I, K) V(K))
+  for (int r = 0; r < 4; ++r) {
+    VJ[r] = dinv[(size_t)J * (WPB * WPB) + l15 * WPB + lq + 4 * r];
+    if (SUMSQ && J0 + lq + 4 * r < n && colok) ss = __builtin_fma(VJ[r], VJ[r], ss);
+  }
   for (int I = J + 1; I < nb; ++I) {
     const int rowI = I * WPB + l15;
     d4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -441,19 +452,43 @@ __global__ __launch_bounds__(256) void k_window_kinv_grad(AdaptArgs p) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = I * WPB + lq + 4 * r;
-      if (row < n && colok) Sc[(size_t)row * CAP] = v[r];
+      if (row < n && colok) {
+        Sc[(size_t)row * CAP] = v[r];
+        if (SUMSQ) ss = __builtin_fma(v[r], v[r], ss);
+      }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // later steps of this wave read what other lanes stored
   }
+  return VJ;
+}
+
+__global__ __launch_bounds__(256) void k_window_kinv_grad(AdaptArgs p) {
+  const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const long long gid = (long long)blockIdx.x * 4 + wave;
+  if (gid >= (long long)p.nwin * p.NB) return;
+  const int w = (int)(gid / p.NB), J = (int)(gid - (long long)w * p.NB);
+  const int CAP = p.CAP, d = p.d, kid = p.kernel_id;
+  const int o = p.state[w * 4], n = p.state[w * 4 + 1], bad = p.state[w * 4 + 2];
+  const int nb = (n + WPB - 1) / WPB;
+  double *gp = p.gpart + ((size_t)w * p.NB + J) * GRAD_N;
+  if (bad != 0 || J >= nb) {
+    if (lane < GRAD_N) gp[lane] = 0.0;
+    return;
+  }
+  double *S = p.L + (size_t)w * CAP * CAP + (size_t)o * CAP + o;   // the window's (0, 0): lower triangle read, strict upper triangle scratch
+  const double *xw = p.xw + (size_t)w * d * CAP + o;
+  const double *dinv = p.dinv + (size_t)w * p.NB * (WPB * WPB);
+  const double *alpha = p.alpha + (size_t)w * p.NB * WPB;
+  const int J0 = J * WPB;
+  const int gj = J0 + l15;
+  const bool colok = gj < n;
+  double *Sc = S + J0 + l15;   // + row * CAP: element (row, chunk column l15) of V / U, transposed into the chunk's tile row
+  double unused;
+  const d4 VJ = chunk_forward_solve<false>(S, dinv, CAP, n, nb, J, l15, lq, unused);
 
   // ---- backward: U(I) = L(I, I)^-T (V(I) - sum_{K > I} L(K, I)^T U(K)), contracted as it is finished
-  WaCov cv;
-  cv.kid = kid;
-  cv.d = d;
-#pragma unroll
-  for (int q = 0; q < MAXD; ++q) cv.pr[q] = q < d ? pr[q] : 0.0;
-  cv.amp = pr[9];
-  cv.ampb = pr[10];
+  const WaCov cv = WaCov::from_prep(kid, d, p.prep + (size_t)w * PREP_N);
   double xj[MAXD];
 #pragma unroll
   for (int q = 0; q < MAXD; ++q) xj[q] = (q < d && colok) ? xw[(size_t)q * CAP + gj] : 0.0;

@@ -471,6 +471,35 @@ extern "C" int cgp_window_joint_reserve(cgp_ctx *c, int max_m) {
 }
 
 namespace {
+// The super-tile grid of a joint covariance launch (k_window_joint_cov, k_joint_cov) over nunit windows or fits: fills the args'
+// grid fields and returns the number of workgroups, a multiple of WF_XCDS, or 0 when it would pass 2^30.
+unsigned joint_cov_grid(int M, int nunit, int &mt, int &nsup, int &npair, int &per_unit) {
+  mt = cdiv(M, WPB);
+  nsup = cdiv(mt, WJ_ST);
+  npair = nsup * (nsup + 1) / 2;
+  per_unit = cdiv(npair, WJ_WAVES);
+  const long long total = (long long)nunit * per_unit;
+  return total > (1ll << 30) ? 0u : (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
+}
+// C C^T = scratch matrix + jitter I in place, then out = mean + C xi, for the nunit windows or fits whose buffers, M, mt and S j
+// names: the tail of every sampling route.  CGP_EINVAL (nothing enqueued) when the paths' grid would pass 2^30.
+int joint_chol_paths_launch(JointArgs &j, int nunit, hipStream_t s) {
+  const long long per = ((long long)j.mt * cdiv(j.S, WPB) + WJ_WAVES - 1) / WJ_WAVES;   // one wave per 16 x 16 tile of the paths
+  if (per * nunit > (1ll << 30)) return CGP_EINVAL;
+  j.per_win = (int)per;
+  if (j.mt <= 4 * WA_WAVES) hipLaunchKernelGGL(k_window_joint_chol<4>, dim3(nunit), dim3(WA_THREADS), 0, s, j);
+  else hipLaunchKernelGGL(k_window_joint_chol<8>, dim3(nunit), dim3(WA_THREADS), 0, s, j);
+  hipLaunchKernelGGL(k_window_joint_paths, dim3((unsigned)(j.per_win * nunit)), dim3(WJ_THREADS), 0, s, j);
+  return CGP_OK;
+}
+// the checks every window joint call starts with: windows and reservation, the arguments, the reservation's capacity
+int window_joint_check(const cgp_ctx *c, int M, bool args_ok) {
+  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
+  if (M < 1 || !args_ok) return CGP_EINVAL;
+  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  return CGP_OK;
+}
+
 // the launches both entry points share: diagonal inverses, the solve with V kept (mean to dmean, variance to the scratch), and
 // the contraction -- into the caller's dcov, or (dcov == nullptr) into the scratch matrix for the factorisation
 int window_joint_launch(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dcov, JointArgs &j, hipStream_t ws) {
@@ -485,13 +514,10 @@ int window_joint_launch(cgp_ctx *c, int M, const double *dxs, int include_noise,
   j = joint_args(c);
   j.xs = dxs; j.mean = dmean; j.var = a.var; j.cov = dcov;
   j.M = M;
-  j.mt = a.mt;
-  j.nsup = cdiv(j.mt, WJ_ST);
-  j.npair = j.nsup * (j.nsup + 1) / 2;
-  j.per_win = cdiv(j.npair, WJ_WAVES);
-  const long long total = (long long)c->nwin * a.nchunk, jtotal = (long long)c->nwin * j.per_win;
-  if (total > (1ll << 30) || jtotal > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS), jgrid = (unsigned)(cdiv((int)jtotal, WF_XCDS) * WF_XCDS);
+  const unsigned jgrid = joint_cov_grid(M, c->nwin, j.mt, j.nsup, j.npair, j.per_win);
+  const long long total = (long long)c->nwin * a.nchunk;
+  if (total > (1ll << 30) || jgrid == 0 || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
+  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
   hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
   hipLaunchKernelGGL(form.kernel, dim3(grid), dim3(WF_THREADS), form.lds, ws, a);
   if (dcov) hipLaunchKernelGGL(k_window_joint_cov<false>, dim3(jgrid), dim3(WJ_THREADS), 0, ws, j);
@@ -502,12 +528,11 @@ int window_joint_launch(cgp_ctx *c, int M, const double *dxs, int include_noise,
 
 extern "C" int cgp_window_predict_cov_device(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dcov,
                                              void *hip_stream) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
-  if (M < 1 || !dxs || !dmean || !dcov) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  int rc = window_joint_check(c, M, dxs && dmean && dcov);
+  if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   JointArgs j;
-  int rc = window_joint_launch(c, M, dxs, include_noise, dmean, dcov, j, pick_stream(c, hip_stream));
+  rc = window_joint_launch(c, M, dxs, include_noise, dmean, dcov, j, pick_stream(c, hip_stream));
   if (rc != CGP_OK) return rc;
   if (!hip_ok(c, hipGetLastError(), "window joint covariance launches")) return CGP_EHIP;
   return CGP_OK;
@@ -515,29 +540,22 @@ extern "C" int cgp_window_predict_cov_device(cgp_ctx *c, int M, const double *dx
 
 extern "C" int cgp_window_sample_device(cgp_ctx *c, int M, const double *dxs, int S, const double *dxi, int include_noise,
                                         double jitter_rel, double *dout, int *dinfo, void *hip_stream) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
-  if (M < 1 || S < 1 || !dxs || !dxi || !dout || !(jitter_rel >= 0.0)) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  int rc = window_joint_check(c, M, S >= 1 && dxs && dxi && dout && jitter_rel >= 0.0);
+  if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t ws = pick_stream(c, hip_stream);
   JointArgs j;
-  int rc = window_joint_launch(c, M, dxs, include_noise, static_cast<double *>(c->jointbuf[2]), nullptr, j, ws);
+  rc = window_joint_launch(c, M, dxs, include_noise, static_cast<double *>(c->jointbuf[2]), nullptr, j, ws);
   if (rc != CGP_OK) return rc;
   j.xi = dxi; j.out = dout; j.S = S; j.info = dinfo; j.jitter_rel = jitter_rel;
-  if (j.mt <= 4 * WA_WAVES) hipLaunchKernelGGL(k_window_joint_chol<4>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, j);
-  else hipLaunchKernelGGL(k_window_joint_chol<8>, dim3(c->nwin), dim3(WA_THREADS), 0, ws, j);
-  const long long per_win = ((long long)j.mt * cdiv(S, WPB) + WJ_WAVES - 1) / WJ_WAVES;   // one wave per 16 x 16 tile of the paths
-  if (per_win * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  j.per_win = (int)per_win;
-  hipLaunchKernelGGL(k_window_joint_paths, dim3((unsigned)(j.per_win * c->nwin)), dim3(WJ_THREADS), 0, ws, j);
+  if ((rc = joint_chol_paths_launch(j, c->nwin, ws)) != CGP_OK) return rc;
   if (!hip_ok(c, hipGetLastError(), "window sample launches")) return CGP_EHIP;
   return CGP_OK;
 }
 
 extern "C" int cgp_window_predict_cov(cgp_ctx *c, int M, const double *xs, int include_noise, double *mean, double *cov) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
-  if (M < 1 || !xs || !mean || !cov) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  int rc = window_joint_check(c, M, xs && mean && cov);
+  if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   // device block [xs | mean | cov]; the copies are ordered on the context's stream with the launches
   const size_t W = c->nwin, nx = W * M * c->win.d, ny = W * M, nc = W * M * M;
@@ -546,7 +564,7 @@ extern "C" int cgp_window_predict_cov(cgp_ctx *c, int M, const double *xs, int i
   int *hst = reinterpret_cast<int *>(h);
   hipStream_t s = c->stream;
   HIP_TRY(c, hipMemcpyAsync(d, xs, nx * 8, hipMemcpyHostToDevice, s));
-  int rc = cgp_window_predict_cov_device(c, M, d, include_noise, d + nx, d + nx + ny, s);
+  rc = cgp_window_predict_cov_device(c, M, d, include_noise, d + nx, d + nx + ny, s);
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(mean, d + nx, ny * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(cov, d + nx + ny, nc * 8, hipMemcpyDeviceToHost, s));
@@ -556,9 +574,8 @@ extern "C" int cgp_window_predict_cov(cgp_ctx *c, int M, const double *xs, int i
 
 extern "C" int cgp_window_sample(cgp_ctx *c, int M, const double *xs, int S, const double *xi, int include_noise, double jitter_rel,
                                  double *out, int *info) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
-  if (M < 1 || S < 1 || !xs || !xi || !out || !(jitter_rel >= 0.0)) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  int rc = window_joint_check(c, M, S >= 1 && xs && xi && out && jitter_rel >= 0.0);
+  if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   // device block [xs | xi | out | info]
   const size_t W = c->nwin, nx = W * M * c->win.d, np = W * (size_t)S * M, ni = (W + 1) / 2;
@@ -568,7 +585,7 @@ extern "C" int cgp_window_sample(cgp_ctx *c, int M, const double *xs, int S, con
   hipStream_t s = c->stream;
   HIP_TRY(c, hipMemcpyAsync(d, xs, nx * 8, hipMemcpyHostToDevice, s));
   HIP_TRY(c, hipMemcpyAsync(d + nx, xi, np * 8, hipMemcpyHostToDevice, s));
-  int rc = cgp_window_sample_device(c, M, d, S, d + nx, include_noise, jitter_rel, d + nx + np, reinterpret_cast<int *>(d + nx + 2 * np), s);
+  rc = cgp_window_sample_device(c, M, d, S, d + nx, include_noise, jitter_rel, d + nx + np, reinterpret_cast<int *>(d + nx + 2 * np), s);
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(out, d + nx + np, np * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(hi, d + nx + 2 * np, W * sizeof(int), hipMemcpyDeviceToHost, s));

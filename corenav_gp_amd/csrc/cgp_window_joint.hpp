@@ -18,10 +18,11 @@
 //                         Output form: both triangles of the caller's (M, M) matrix from the same register (exactly symmetric),
 //                         the diagonal replaced by the forecast's variance (clip and noise included).  Scratch form (sampling):
 //                         the lower triangle, column-major with leading dimension M padded to 16, identity in the padding.
-//   k_window_joint_chol   k_window_refactor's left-looking block Cholesky (transposed tiles, diagonal block by one wave in
-//                         registers with factor_block16_repair, L(J, J)^-1 applied with four chained MFMAs) with the start tile
-//                         read from the scratch matrix instead of evaluated, the jitter added to the diagonal as it is read; in
-//                         place.  A non-positive pivot is repaired (nothing faults) and reported.
+//   k_window_joint_chol   k_window_refactor's left-looking block Cholesky, written out a second time: a shared block-column step
+//                         was slower (docs/negatives.md item 20), so a fix there goes into both kernels (transposed tiles, diagonal
+//                         block by one wave in registers with factor_block16_repair, L(J, J)^-1 applied with four chained MFMAs)
+//                         with the start tile read from the scratch matrix instead of evaluated, the jitter added to the diagonal
+//                         as it is read; in place.  A non-positive pivot is repaired (nothing faults) and reported.
 //   k_window_joint_paths  out = mean + C xi: one wave per (16 test points) x (16 paths) tile, sum over the block columns up to
 //                         the diagonal one (masked above the diagonal).  NaN for a window whose factorisation failed.
 // Forms by the window length N alone, as in the forecast (N <= 512 tuned, the two longer forms correct only); the Cholesky
@@ -55,7 +56,6 @@ struct JointArgs {
 
 template <bool SCRATCH>
 __global__ __launch_bounds__(WJ_THREADS) void k_window_joint_cov(JointArgs p) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
   // workgroup -> (window, group of super-tile pairs): consecutive ids on ONE XCD
   const int per = gridDim.x / WF_XCDS;
   const int lid = (blockIdx.x % WF_XCDS) * per + blockIdx.x / WF_XCDS;
@@ -71,14 +71,7 @@ __global__ __launch_bounds__(WJ_THREADS) void k_window_joint_cov(JointArgs p) {
   const int M = p.M, mt = p.mt, d = p.d, kid = p.kernel_id;
   const int n = p.state[w * 4 + 1], bad = p.state[w * 4 + 2];
   const int nb = (bad != 0 || n <= 0) ? 0 : (n + WPB - 1) / WPB;
-  const double *pr = p.prep + (size_t)w * PREP_N;
-  WaCov cv;
-  cv.kid = kid;
-  cv.d = d;
-#pragma unroll
-  for (int q = 0; q < MAXD; ++q) cv.pr[q] = q < d ? pr[q] : 0.0;
-  cv.amp = pr[9];
-  cv.ampb = pr[10];
+  const WaCov cv = WaCov::from_prep(kid, d, p.prep + (size_t)w * PREP_N);
   const double *xs = p.xs + (size_t)w * M * d;
   // tile (b, a): rows j = (BJ 4 + b) 16 + lq + 4 r (A operand), columns i = (BI 4 + a) 16 + l15 (B operand)
   auto live = [&](int b, int a) { return BI * WJ_ST + a < mt && BJ * WJ_ST + b <= BI * WJ_ST + a; };
@@ -173,7 +166,6 @@ __global__ __launch_bounds__(WJ_THREADS) void k_window_joint_cov(JointArgs p) {
 // In-place Cholesky of the scratch matrix (k_window_refactor's scheme, the start tile from memory).  One workgroup per window.
 template <int TPW>
 __global__ __launch_bounds__(WA_THREADS) void k_window_joint_chol(JointArgs p) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
   __shared__ double tile[WPB * WPB];   // the diagonal tile, [c * 16 + r]
   __shared__ double winv[WPB * WPB];   // L(J, J)^-1, element (row m, column k) at k * 16 + m
   const int w = blockIdx.x;
@@ -275,7 +267,6 @@ __global__ __launch_bounds__(WA_THREADS) void k_window_joint_chol(JointArgs p) {
 
 // out = mean + C xi.  One wave per (tile of 16 test points) x (tile of 16 paths).
 __global__ __launch_bounds__(WJ_THREADS) void k_window_joint_paths(JointArgs p) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int M = p.M, S = p.S, mt = p.mt, mpad = mt * WPB;

@@ -1,14 +1,13 @@
 // cgp_window_loo.hpp -- leave-one-out cross-validation of the resident sliding windows (cgp_window_loo), from the factor, z,
 // the inputs and the targets as they stand after any number of pushes (formulas: cgp_loo.hpp).
 //
-//   k_window_loo          One WAVE = one window x one chunk of 16 columns [c0, c0 + 16), k_window_kinv_grad's work unit, and its
-//                         forward half only: V = L^-1 E for the chunk (rows above the chunk are zero: the substitution starts at
-//                         the chunk's own block) with k_window_diag_inv's inverses, L(I, K) the A operand read down the slab's
-//                         columns, on v_mfma_f64_16x16x4_f64.  V lives where k_window_kinv_grad keeps it, transposed in the
-//                         chunk's tile row of the slab's strict upper triangle (the lower triangle, the diagonal, z, the samples
-//                         and the state words are NOT written).  The 16 column sums of squares are kd = diag(Ky^-1) of the
-//                         chunk's samples; with k_window_alpha's alpha and yw the wave writes its 16 entries of loo_mean /
-//                         loo_var / loo_lpd at the window-order index (0 = oldest sample) and one partial sum of loo_lpd.
+//   k_window_loo          One WAVE = one window x one chunk of 16 columns [c0, c0 + 16): chunk_forward_solve<true>
+//                         (cgp_window_adapt.hpp, the forward half k_window_kinv_grad also runs) gives V = L^-1 E for the chunk
+//                         and the columns' sums of squares; V lives, transposed, in the chunk's tile row of the slab's strict
+//                         upper triangle (the lower triangle, the diagonal, z, the samples and the state words are NOT
+//                         written).  The 16 sums are kd = diag(Ky^-1) of the chunk's samples; with k_window_alpha's alpha and
+//                         yw the wave writes its 16 entries of loo_mean / loo_var / loo_lpd at the window-order index
+//                         (0 = oldest sample) and one partial sum of loo_lpd.
 //   k_window_loo_finish   per window: the chunks' partial sums added in chunk order (no atomics); NaN for the entries [n, N) of a
 //                         window still filling; NaN everywhere (sum included) for a failed window; NaN rows and sum 0 for an
 //                         empty one.
@@ -25,7 +24,6 @@ struct WindowLooOut {
 };
 
 __global__ __launch_bounds__(256) void k_window_loo(AdaptArgs p, WindowLooOut out) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long long gid = (long long)blockIdx.x * 4 + wave;
@@ -40,51 +38,10 @@ __global__ __launch_bounds__(256) void k_window_loo(AdaptArgs p, WindowLooOut ou
   }
   double *S = p.L + (size_t)w * CAP * CAP + (size_t)o * CAP + o;   // the window's (0, 0): lower triangle read, strict upper triangle scratch
   const double *dinv = p.dinv + (size_t)w * p.NB * (WPB * WPB);
-  const int J0 = J * WPB;
-  const int gj = J0 + l15;
+  const int gj = J * WPB + l15;
   const bool colok = gj < n;
-  // V(J) = L(J, J)^-1 stays in registers: register r = rows lq + 4 r, column l15
-  d4 VJ;
-  double ss = 0.0;   // this lane's share of column l15's sum of squares
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    VJ[r] = dinv[(size_t)J * (WPB * WPB) + l15 * WPB + lq + 4 * r];
-    if (J0 + lq + 4 * r < n && colok) ss = __builtin_fma(VJ[r], VJ[r], ss);   // rows past the window are identity rows: not counted
-  }
-  double *Sc = S + J0 + l15;   // + row * CAP: element (row, chunk column l15) of V, transposed into the chunk's tile row
-
-  // ---- forward: V(I) = L(I, I)^-1 (- sum_{J <= K < I} L(I, K) V(K))
-  for (int I = J + 1; I < nb; ++I) {
-    const int rowI = I * WPB + l15;
-    d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 2
-    for (int K = J; K < I; ++K) {
-      const int k0 = K * WPB + lq;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const double a = rowI < n ? -S[(size_t)(k0 + 4 * ks) * CAP + rowI] : 0.0;
-        double b;
-        if (K == J) b = VJ[ks];
-        else b = colok ? Sc[(size_t)(k0 + 4 * ks) * CAP] : 0.0;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-      }
-    }
-    d4 v = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const double di = dinv[(size_t)I * (WPB * WPB) + (lq + 4 * r) * WPB + l15];
-      v = __builtin_amdgcn_mfma_f64_16x16x4f64(di, acc[r], v, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = I * WPB + lq + 4 * r;
-      if (row < n && colok) {
-        Sc[(size_t)row * CAP] = v[r];
-        ss = __builtin_fma(v[r], v[r], ss);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // later steps of this wave read what other lanes stored
-  }
+  double ss;   // this lane's share of column l15's sum of squares
+  chunk_forward_solve<true>(S, dinv, CAP, n, nb, J, l15, lq, ss);
 
   // ---- kd of column l15: the four row groups' shares (fixed order), then this sample's three outputs
   ss += __shfl_xor(ss, 16);

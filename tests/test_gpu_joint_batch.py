@@ -197,7 +197,7 @@ def test_latency_range_calls_agree_with_larger_ones_to_rounding(engine):
         assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("kid,N,d", [(0, 100, 2), (2, 100, 1), (1, 16, 3), (4, 100, 3)])
+@pytest.mark.parametrize("kid,N,d", [(0, 100, 2), (2, 100, 1), (1, 16, 3), (4, 100, 3), (1, 9, 2)])   # N = 9: the masked tail alone
 def test_short_windows_take_the_tiled_schedules(engine, kid, N, d):
     """Shapes the marginal call sends to the one-launch short-window kernel: the joint calls answer from the tiled schedules;
     mean / diag(cov) agree with the marginal call to rounding."""

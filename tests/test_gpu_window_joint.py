@@ -232,7 +232,7 @@ def test_host_device_and_graph_replay_agree_bitwise(engine):
         check()
 
 
-@pytest.mark.parametrize("kid,N,d,M", [(1, 64, 3, 45), (2, 40, 1, 100), (0, 33, 2, 16)])
+@pytest.mark.parametrize("kid,N,d,M", [(1, 64, 3, 45), (2, 40, 1, 100), (0, 33, 2, 16), (0, 33, 2, 520)])   # M = 520: eight tiles per wave
 def test_paths_factor_and_random_draws(engine, kid, N, d, M):
     """xi = unit vectors returns C: lower triangular, C C^T = the oracle's matrix (cov + noise + jitter) to 1e-9; random xi
     against sample_paths, S = 1 and S = 50."""
