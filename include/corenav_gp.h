@@ -253,7 +253,21 @@ int cgp_fit_predict_batch(cgp_ctx *ctx, int batch, int N, int d, int M, int kern
  *   djitter (batch) fp64 or NULL, dmean/dvar (batch, M), dlogml (batch) fp64, dinfo (batch) int32.
  * Work is enqueued on `hip_stream` (see CGP_STREAM_CTX above: NULL = the legacy default stream,
  * CGP_STREAM_CTX = the context's own stream) and the call returns without synchronising.  No jitter retry happens here: read dinfo and re-submit the failed
- * fits with djitter set (cgp_fit_predict_batch does exactly that). */
+ * fits with djitter set (cgp_fit_predict_batch does exactly that).
+ *
+ * Extents of caller buffers -- this call and EVERY `*_device` entry point of this header (the joint, multi-target, leave-one-out,
+ * sweep and window forms).  The kernels work in padded shapes (128-row tiles, 16-column panels, M rounded up to 16); the caller's
+ * arrays are exactly the shapes stated with each call, and the contract is:
+ *   - the alignment of the element type suffices (8 bytes for fp64, 4 for fp32 / int32, 1 for dselect): a slice of a larger
+ *     array is a valid argument;
+ *   - nothing outside the documented extents is written, the gap columns [ntheta, stride) of a strided array and the entries of
+ *     unselected windows included; inputs are never written;
+ *   - no output depends on memory outside the documented extents (a padded lane never reads the caller's memory into a result);
+ *   - every documented element of every output that is passed is written by every call that returns 0, for every fit / window
+ *     whose status word is 0; the rows of a failed fit or window hold NaN where its section promises NaN, its status word is
+ *     always written, and what its remaining rows hold (dmean / dvar / dlogml of cgp_fit_predict_batch_device and the sweep, the
+ *     ticks of a push on a failed window) is unspecified -- but it stays inside those rows.
+ * tests/test_gpu_device_extents.py holds every entry point to it on guard-band allocations. */
 int cgp_fit_predict_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, int kernel_id,
                                  const void *dX, const void *dy, const void *dXs, const double *dtheta,
                                  const double *djitter, int include_noise, void *dmean, void *dvar,
