@@ -1745,7 +1745,7 @@ static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, in
     return r;
   });
   if (rc != CGP_OK) return rc;
-  c->fjitter = hjit[0];
+  c->fjitter = hinfo[0] == 0 ? hjit[0] : 0.0;   // only a fit that factored reports a jitter (cgp_last_jitter; as the gradient-mode and short-window paths)
   if (retried) {
     HIP_TRY(c, queue_results());
     HIP_TRY(c, hipStreamSynchronize(s));

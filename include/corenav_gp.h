@@ -128,7 +128,8 @@ int cgp_predict(cgp_ctx *ctx, const double *Xs, int M, int include_noise, double
 int cgp_get_alpha(cgp_ctx *ctx, double *alpha);
 /* Lower Cholesky factor of the last fit, (N, N) row-major, upper triangle zero (GPy `LW`). */
 int cgp_get_factor(cgp_ctx *ctx, double *L);
-/* Jitter that was added to the diagonal for the last fit to succeed (0 if none). */
+/* Jitter that was added to the diagonal for the last fit to succeed (0 if none).  Only a fit that factored reports a jitter:
+ * after a fit that returned a positive status (the ladder ran out) this is 0, not the last rung that was tried. */
 double cgp_last_jitter(const cgp_ctx *ctx);
 
 /* ---- hyper-parameter optimisation (the reference's `m.optimize()`, gp_slip_node.py:36) ----------
@@ -604,7 +605,8 @@ int cgp_window_predict_device(cgp_ctx *ctx, int M, const double *dxs, int includ
  * (logml[w]; 0 for an empty window).  Origin, size and tick count do not change; a window still filling or empty works (its size
  * is read from the device state).  The window's failure word is SET from the result: 0 when the factorisation succeeded -- this
  * is how a window that lost positive definiteness in a push (cgp_window_state info != 0, NaN forecasts) is revived, e.g. with a
- * larger sigma_n^2 -- and otherwise the LAPACK-style 1-based index of the first non-positive pivot, which info[w] also
+ * larger sigma_n^2 -- and otherwise the LAPACK-style 1-based index of the first non-positive pivot, counted in the window's
+ * order, oldest first (sample 1 is the oldest the window holds, however far its ring has moved), which info[w] also
  * receives: cgp_window_state, the forecast's NaN rule and later pushes then treat the window exactly like one a push failed
  * (logml[w] is NaN).  No jitter ladder (the pushes have none).  theta is validated no more than cgp_window_init validates it:
  * a theta under which Ky is not positive definite, or a non-finite one, shows up as a failed window, not as an argument error.
