@@ -12,6 +12,7 @@
 #include "cgp_joint.hpp"
 #include "cgp_multi.hpp"
 #include "cgp_multi_grad.hpp"
+#include "cgp_pgrad.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
 #include "cgp_loo.hpp"
@@ -149,6 +150,12 @@ struct cgp_ctx {
   int ma_max_batch = 0, ma_max_p = 0;
   void *ma_dev = nullptr;
   size_t ma_dev_cap = 0;
+  // predictive gradients (cgp_pgrad_reserve): B^T = (Ky^-1 K*)^T and alpha of up to pg_max_batch fits x pg_max_m test points,
+  // [fit][NT 128][M + 1 padded to 128]; the host calls' outputs [dmean | dvar], grown on demand and kept
+  void *pgbuf = nullptr;
+  int pg_max_batch = 0, pg_max_m = 0;
+  void *pg_dev = nullptr;
+  size_t pg_dev_cap = 0;
   // cgp_window_push staging, grown on demand and kept: one pinned host block and one device block per direction
   void *win_pin = nullptr, *win_dev = nullptr;
   size_t win_pin_cap = 0, win_dev_cap = 0;
@@ -206,15 +213,19 @@ bool grow_device(void *&p, size_t &cap, size_t bytes);
 void window_free(cgp_ctx *c, bool joint_only);   // cgp_window_host.hpp
 // cgp_joint_host.hpp.  What a joint call adds to a batch of fits: the contraction of the fits' V rows into their covariance slots.
 struct MultiCall;   // cgp_multi_host.hpp: the targets of a multi-target call
+struct PgradCall;   // cgp_pgrad_host.hpp: the arrays of a predictive-gradient call
 struct JointHook {
   double *dcov;   // output form (batch, M, M) on the device; null: the scratch form for the factorisation
   const MultiCall *multi = nullptr;   // a multi-target call instead: solve + contraction of the fits' P targets (dcov unused)
+  const PgradCall *pgrad = nullptr;   // a predictive-gradient call instead: backward solve + contraction (dcov unused)
 };
 void joint_free(cgp_ctx *c);
 int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, const double *dXs,
                      const double *dtheta, const double *dvar, const int *dinfo, hipStream_t s);
 void multi_free(cgp_ctx *c);
 void multi_grad_free(cgp_ctx *c);   // cgp_multi_grad_host.hpp
+void pgrad_free(cgp_ctx *c);        // cgp_pgrad_host.hpp
+int pgrad_launch(cgp_ctx *c, const PgradCall &pc, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s);
 int multi_hook_launch(cgp_ctx *c, const MultiCall &mc, int N, int M, int slab, int slot, int nfit, hipStream_t s);
 // what the hook of a batch call enqueues for the fits in slabs slab ... into the slots slot ... of the call's arrays
 inline int post_fit_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s);
@@ -1452,6 +1463,7 @@ void cgp_destroy(cgp_ctx *c) {
   joint_free(c);
   multi_free(c);
   multi_grad_free(c);
+  pgrad_free(c);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -2937,3 +2949,4 @@ extern "C" int cgp_loo(cgp_ctx *c, const double *X, const double *y, int N, int 
 
 // multi-target objective: cgp_multi_grad_reserve ... cgp_optimize_multi_batch
 #include "cgp_multi_grad_host.hpp"
+#include "cgp_pgrad_host.hpp"

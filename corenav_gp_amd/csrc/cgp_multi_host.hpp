@@ -98,6 +98,7 @@ int multi_hook_launch(cgp_ctx *c, const MultiCall &mc, int N, int M, int slab, i
 
 inline int post_fit_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s) {
   if (h.multi) return multi_hook_launch(c, *h.multi, N, M, slab, slot, nfit, s);
+  if (h.pgrad) return pgrad_launch(c, *h.pgrad, N, d, M, kid, slab, slot, nfit, s);
   return joint_cov_launch(c, h, N, d, M, kid, slab, slot, nfit, static_cast<const double *>(c->dXs), c->dtheta,
                           static_cast<const double *>(c->dvar), c->dinfo, s);
 }

@@ -85,6 +85,13 @@ _SIGS = {
     "cgp_fit_sample_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp, _vp, ctypes.c_int,
                                                                                 ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp,
                                                                                 _vp, _vp]),
+    "cgp_pgrad_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "cgp_fit_predict_grad_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp, _dp, _dp, _dp, ctypes.c_int,
+                                                                               ctypes.c_int, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "cgp_fit_predict_grad_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp, _vp, _vp, _vp, _vp,
+                                                                                      ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                                                      _vp]),
+    "cgp_predict_gradients": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
     "cgp_multi_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
     "cgp_multi_set_form": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_fit_predict_multi_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_dp, _dp, _dp, _dp, ctypes.c_int,
@@ -416,6 +423,46 @@ class Context:
         return self._chk(self.lib.cgp_fit_predict_cov_batch_device(self.h, B, N, d, M, kernel_id, dX, dy, dXs, dtheta,
                                                                    djitter or None, int(include_noise), dmean, dcov,
                                                                    dlogml, dinfo, ctypes.c_void_p(stream)))
+
+    # -- predictive gradients after batch / single fits (fp64 contexts) ----------------------------------
+    def pgrad_reserve(self, max_batch, max_m):
+        """Scratch for the predictive-gradient calls below (B^T = (Ky^-1 K*)^T and alpha of up to max_batch fits at up to max_m
+        test points: max_batch x max_n x (max_m + 1) doubles, both rounded up to 128)."""
+        return self._chk(self.lib.cgp_pgrad_reserve(self.h, int(max_batch), int(max_m)))
+
+    def fit_predict_grad_batch(self, X, y, Xs, theta, kernel_id, include_noise=True):
+        """fit_predict_batch plus d mean / d x* and d var / d x*, each (B, M, d): (code, mean, var, logml, info, dmean, dvar).
+        A fit whose info stays non-zero after the jitter ladder has NaN in its gradients."""
+        X, y, Xs, theta = _d(X), _d(y), _d(Xs), _d(theta)
+        B, N, d = X.shape
+        M = Xs.shape[1]
+        mean, var = np.empty((B, M)), np.empty((B, M))
+        dmean, dvar = np.empty((B, M, d)), np.empty((B, M, d))
+        logml, info = np.empty(B), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_fit_predict_grad_batch(self.h, B, N, d, M, kernel_id, _p(X), _p(y), _p(Xs), _p(theta),
+                                                           theta.shape[1], int(include_noise), _p(mean), _p(var),
+                                                           _p(logml), info.ctypes.data_as(_ip), _p(dmean), _p(dvar)))
+        return rc, mean, var, logml, info, dmean, dvar
+
+    def fit_predict_grad_batch_device(self, B, N, d, M, kernel_id, dX, dy, dXs, dtheta, djitter, include_noise, dmean,
+                                      dvar, dlogml, dinfo, ddmean, ddvar, stream=0):
+        """Device pointers as fit_predict_batch_device, plus ddmean / ddvar (B, M, d); either may be 0, not both."""
+        return self._chk(self.lib.cgp_fit_predict_grad_batch_device(self.h, B, N, d, M, kernel_id, dX, dy, dXs, dtheta,
+                                                                    djitter or None, int(include_noise), dmean, dvar,
+                                                                    dlogml, dinfo, ddmean or None, ddvar or None,
+                                                                    ctypes.c_void_p(stream)))
+
+    def predict_gradients(self, Xs):
+        """After fit / optimize: m.predictive_gradients(Xs) with the marginals -> (mean (M,), var (M,) without the noise
+        variance, dmean (M, d), dvar (M, d))."""
+        Xs = _d(Xs)
+        if Xs.ndim == 1:
+            Xs = Xs[:, None]
+        M, d = Xs.shape
+        mean, var = np.empty(M), np.empty(M)
+        dmean, dvar = np.empty((M, d)), np.empty((M, d))
+        self._chk(self.lib.cgp_predict_gradients(self.h, _p(Xs), M, _p(mean), _p(var), _p(dmean), _p(dvar)))
+        return mean, var, dmean, dvar
 
     def fit_sample_batch(self, X, y, Xs, theta, kernel_id, xi, include_noise=False, jitter_rel=1e-6):
         """Fits and sample paths of their joint posterior: xi (B, S, M) standard normals drawn by the caller -> (code, paths

@@ -337,6 +337,55 @@ int cgp_predict_cov(cgp_ctx *ctx, const double *Xs, int M, int include_noise, do
 int cgp_sample(cgp_ctx *ctx, const double *Xs, int M, int S, const double *xi, int include_noise, double jitter_rel,
                double *out, int *info);
 
+/* ---- predictive gradients after batch / single fits: d mean / d x*, d var / d x* ----------------------
+ * The reference's model also offers m.predictive_gradients(Xnew): the derivative of the predictive mean and of the predictive
+ * variance with respect to the test inputs -- for the d = 1 slip series the slip rate and the rate at which the confidence band
+ * opens along the horizon, for the multi-input windows the sensitivity of predicted slip to each input.  With
+ * Ky = K(X, X) + (sigma_n^2 + 1e-8 + jitter) I = L L^T, alpha = Ky^-1 y and B = Ky^-1 K(X, Xs) (N x M):
+ *   dmean[m][q] =                     sum_i dk(x*_m, x_i)/dx*_q alpha_i
+ *   dvar [m][q] = dk(x*_m, x*_m)/dx*_q - 2 sum_i dk(x*_m, x_i)/dx*_q B[i][m]
+ * dmean / dvar are (batch, M, d) row-major.  include_noise adds a constant and does not enter; neither does the variance's clip
+ * at 1e-15: the gradient is that of the unclipped expression.  Kernel derivatives, r^2 = sum_q ((x*_q - x_iq) / ell_q)^2 and
+ * g = -2 dk/dr^2: ids 0 / 1 / 3 / 4 have dk/dx*_q = g (x_iq - x*_q) / ell_q^2 with g = k (squared exponentials),
+ * 3 sigma_f^2 e^-s (Matern 3/2), (5/3) sigma_f^2 (1 + s) e^-s (Matern 5/2) -- finite at r = 0, no quotient by r -- and
+ * d k(x*, x*) / dx* = 0.  Id 2 (RBF x Brownian, d = 1), R = sigma_r^2 exp(-(x* - x_i)^2 / 2 ell^2), W = sigma_b^2 min(|x*|, |x_i|) for
+ * equal signs, else 0:
+ *   dk/dx* = R W (x_i - x*) / ell^2 + R sigma_b^2 sign(x*) [|x*| < |x_i| and equal signs],   d k(x*, x*) / dx* = sigma_r^2 sigma_b^2 sign(x*)
+ * with sign(0) = 0 and the bracket 0 at a tie |x*| = |x_i| (test points on the tick grid inside a window hit one).
+ * After a tiled fit the factor panel holds V^T = (L^-1 K*)^T and z^T = (L^-1 y)^T beside L; B^T and alpha are ONE backward
+ * triangular solve with M + 1 right-hand sides against the tiled factor, N^2 (M + 1) flops per fit on the fp64 matrix cores, and
+ * the two sums one pass of N M evaluations of g.  CGP_F64 contexts only: every entry point of this section returns CGP_EINVAL in
+ * a CGP_F32 context before anything is enqueued.  All five kernel ids.  Every shape takes the tiled schedules here (the one-launch
+ * short-window kernel leaves no V^T behind), and among them the one the marginal call of its size takes: for N > 160
+ * mean / var / logml / info are bitwise cgp_fit_predict_batch[_device]'s.  A fit's gradients are a function of its own data and
+ * of that schedule only, never of its slot or its neighbours.
+ *
+ * cgp_pgrad_reserve: scratch for B^T and alpha of up to max_batch fits at up to max_m test points, one slab per fit in the
+ * factor panel's layout: max_batch x (the context's max_n rounded up to 128) x (max_m + 1 rounded up to 128) doubles (N = 2048,
+ * M = 599: 10.5 MB per fit, 5.4 GB for 512 fits -- the caller decides).  1 <= max_batch <= the context's, 1 <= max_m <= the
+ * context's max_m, else CGP_EINVAL; CGP_ENOMEM leaves no reservation; calling it again replaces the reservation.  Blocks (it
+ * synchronises the device).  Without a reservation the calls below return CGP_ESTATE, for a batch or an M beyond it
+ * CGP_ECAPACITY; M < 1 and NULL pointers are CGP_EINVAL. */
+int cgp_pgrad_reserve(cgp_ctx *ctx, int max_batch, int max_m);
+/* cgp_fit_predict_grad_batch: arguments, status words, jitter ladder and return value as cgp_fit_predict_batch, plus
+ * dmean / dvar (batch, M, d); either may be NULL, not both.  A fit whose info stays non-zero has NaN in all of its gradients;
+ * the other fits of the call are unaffected.  A fit the ladder repaired has the gradients of its final jitter.  Blocks. */
+int cgp_fit_predict_grad_batch(cgp_ctx *ctx, int batch, int N, int d, int M, int kernel_id,
+                               const double *X, const double *y, const double *Xs, const double *theta,
+                               int theta_stride, int include_noise, double *mean, double *var,
+                               double *logml, int *info, double *dmean, double *dvar);
+/* Device-resident variant: pointers as cgp_fit_predict_batch_device (fp64), plus ddmean / ddvar (batch, M, d), either may be
+ * NULL, not both.  The fit schedule plus two launches, enqueued on hip_stream; no allocation, no synchronisation, no jitter
+ * ladder (capturable into a hipGraph).  A fit with dinfo != 0 has NaN in all of its gradients. */
+int cgp_fit_predict_grad_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, int kernel_id,
+                                      const double *dX, const double *dy, const double *dXs, const double *dtheta,
+                                      const double *djitter, int include_noise, double *dmean, double *dvar,
+                                      double *dlogml, int *dinfo, double *ddmean, double *ddvar, void *hip_stream);
+/* After cgp_fit / cgp_optimize, the literal m.predictive_gradients(Xs): Xs (M, d), dmean / dvar (M, d), either may be NULL, not
+ * both; mean / var (M), each may be NULL, are bitwise cgp_predict's with include_noise = 0.  The extra rows are computed against
+ * the resident factor as cgp_predict does; the resident fit is not modified.  CGP_ESTATE also without a successful fit.  Blocks. */
+int cgp_predict_gradients(cgp_ctx *ctx, const double *Xs, int M, double *mean, double *var, double *dmean, double *dvar);
+
 /* ---- multi-target fits: P target columns share one factor ------------------------------------------
  * The model the engine restates is GPy.models.GPRegression(X, Y, kernel) with Y (N, P): P independent outputs that share the
  * inputs, the kernel and the hyper-parameters -- a Monte-Carlo ensemble on a common tick grid, the four wheels' slip series on one
