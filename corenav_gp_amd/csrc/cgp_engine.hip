@@ -56,6 +56,16 @@ struct ProfRec {
   double flops;
 };
 
+// What a feature's cgp_*_reserve leaves in the context: the device scratch its kernels work in, sized for up to max_batch fits x
+// max_dim test points or targets (0: nothing reserved), and the staging block of its host calls, grown on demand and kept
+// (scratch_free / scratch_check / scratch_reserve below)
+struct Scratch {
+  void *buf = nullptr;
+  int max_batch = 0, max_dim = 0;
+  void *stage = nullptr;
+  size_t stage_cap = 0;
+};
+
 }  // namespace
 
 struct cgp_ctx {
@@ -132,30 +142,18 @@ struct cgp_ctx {
   void *jointbuf[4] = {nullptr};
   int joint_max_m = 0;
   // joint forecast after batch / single fits (cgp_joint_reserve): the posterior covariance or its factor [max_batch][(mt * 16)^2],
-  // the factorisations' failure words [max_batch]; staging of the host sampling calls [xi | out], grown on demand and kept
-  void *fjbuf[2] = {nullptr};
-  int fj_max_batch = 0, fj_max_m = 0;
-  void *fj_dev = nullptr;
-  size_t fj_dev_cap = 0;
-  // multi-target fits (cgp_multi_reserve): Z = L^-1 Y of up to mz_max_batch fits x mz_max_p targets, [fit][NT 128][P padded to 128];
-  // staging of the host call [Y | mean | logml], grown on demand and kept
-  void *mz = nullptr;
-  int mz_max_batch = 0, mz_max_p = 0;
+  // then the factorisations' failure words [max_batch]; staging of the host sampling calls [xi | out]
+  Scratch fj;
+  // multi-target fits (cgp_multi_reserve): Z = L^-1 Y of up to max_batch fits x max_dim targets, [fit][NT 128][P padded to 128];
+  // staging of the host call [Y | mean | logml]
+  Scratch mz;
   int mz_form = 0;   // cgp_multi_set_form: 0 = the engine picks the solve's tile height, 64 / 128 = as told (tests)
-  void *mz_dev = nullptr;
-  size_t mz_dev_cap = 0;
-  // multi-target objective (cgp_multi_grad_reserve): A = Ky^-1 Y of up to ma_max_batch fits x ma_max_p targets, [fit][P padded to 16][NT 128],
-  // then (ma_max_batch, ma_max_p) logml; staging of the host calls [Y | nll | grad | logml], grown on demand and kept
-  void *ma = nullptr;
-  int ma_max_batch = 0, ma_max_p = 0;
-  void *ma_dev = nullptr;
-  size_t ma_dev_cap = 0;
-  // predictive gradients (cgp_pgrad_reserve): B^T = (Ky^-1 K*)^T and alpha of up to pg_max_batch fits x pg_max_m test points,
-  // [fit][NT 128][M + 1 padded to 128]; the host calls' outputs [dmean | dvar], grown on demand and kept
-  void *pgbuf = nullptr;
-  int pg_max_batch = 0, pg_max_m = 0;
-  void *pg_dev = nullptr;
-  size_t pg_dev_cap = 0;
+  // multi-target objective (cgp_multi_grad_reserve): A = Ky^-1 Y of up to max_batch fits x max_dim targets, [fit][P padded to 16][NT 128],
+  // then (max_batch, max_dim) logml; staging of the host calls [Y | nll | grad | logml]
+  Scratch ma;
+  // predictive gradients (cgp_pgrad_reserve): B^T = (Ky^-1 K*)^T and alpha of up to max_batch fits x max_dim test points,
+  // [fit][NT 128][M + 1 padded to 128]; the host calls' outputs [dmean | dvar]
+  Scratch pg;
   // cgp_window_push staging, grown on demand and kept: one pinned host block and one device block per direction
   void *win_pin = nullptr, *win_dev = nullptr;
   size_t win_pin_cap = 0, win_dev_cap = 0;
@@ -194,6 +192,131 @@ struct cgp_ctx {
 
 namespace {
 
+// cgp_ctx::GroupTune's state machine: two stream groups or one for this eligible call (fp32, mid-size, 56 ... 96 fits, the
+// engine decides) of `batch` fits and NT block steps on the caller's stream s.
+// Whether the two groups really run side by side depends on how the runtime mapped the caller's stream and the worker
+// stream onto its few hardware queues -- the process's history, which nothing reports: the same 64-fit call took 0.89 ms
+// on the legacy stream and 1.28 ms (the two groups in order: worse than one group's 0.98) on a fresh torch stream or on a
+// context created later in the process (tools/sweep_probe.py, stream_probe.py; a probe with spin kernels did not predict
+// it, both groups on the context's own streams was no better, and a single timed call does not show it: it is a
+// steady-state effect of calls issued back to back).  So the default does not assume: per caller stream, after two
+// warm-up calls, four eligible calls run as two groups and four as one, each run bracketed by events on the caller's
+// stream, and from then on the faster form is used.  Results are bitwise the same either way.
+// Every kRetune calls the two runs are repeated (a caller that first synchronises after every call and later issues calls
+// back to back sees the other behaviour: sweep_probe.py's 1.24 ms): 8 calls in 264, half of them at the slower setting.
+// The measurement never blocks the caller and never touches a stream that is being captured: the decision is read with
+// hipEventQuery (until the last timed call has finished the call keeps two groups and asks again next time), an entry is
+// keyed by (stream, fits, block steps) -- a caller that mixes shapes on one stream gets one decision per shape --, a pair
+// of spans that differ by more than 4 x is the caller's own host gaps, not the schedules (discarded, measured again), and
+// while the stream is capturing (cgp_set_streams documents fixing the form for graphs; this keeps the default safe) the
+// call takes the form already decided, or two groups, without recording or reading any timing event.
+struct TuneStep {
+  int groups = 2;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // events to record on the caller's stream before / after this call
+  cgp_ctx::GroupTune *entry = nullptr;       // non-null: this call belongs to the tuning runs (++entry->state once it is enqueued)
+};
+TuneStep tune_groups(cgp_ctx *c, int batch, int NT, hipStream_t s) {
+  int G = 2;
+  cgp_ctx::GroupTune *tune = nullptr;
+  hipEvent_t tune_ev0 = nullptr, tune_ev1 = nullptr;
+  constexpr int kWarm = 2, kRun = 4, kTuneDecide = kWarm + 2 * kRun, kRetune = 256;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  const bool capturing = hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+  if (capturing) (void)hipGetLastError();
+  cgp_ctx::GroupTune *t = nullptr, *lru = &c->tune[0];
+  for (auto &e : c->tune) {
+    if (e.state >= 0 && e.stream == s && e.batch == batch && e.NT == NT) t = &e;
+    if (e.used < lru->used) lru = &e;
+  }
+  if (!t && !capturing) {
+    t = lru;
+    t->stream = s;
+    t->batch = batch;
+    t->NT = NT;
+    t->state = 0;
+    t->groups = 2;
+    for (auto &e : t->e)
+      if (!e && hipEventCreate(&e) != hipSuccess) {   // no events: keep the two groups, never measure
+        (void)hipGetLastError();
+        t->state = kTuneDecide + 1;
+      }
+    for (auto &e : t->mon)
+      if (!e && hipEventCreate(&e) != hipSuccess) (void)hipGetLastError();   // (no monitor then)
+    t->mon_pending = false;
+    t->slow = 0;
+    t->retune = 24;
+  }
+  if (capturing) {
+    G = t && t->state > kTuneDecide ? t->groups : 2;
+    t = nullptr;
+  }
+  if (t) {
+    t->used = ++c->tune_clock;
+    // (the first decisions are re-checked early: a context's first calls run while the part is still coming out of idle -- both forms
+    // then measure alike, 4.70 / 4.72 ms per four calls where warm they are 4.5 / 2.9 -- and the decision is a coin toss)
+    if (t->state > kTuneDecide + t->retune) {
+      t->state = kWarm;
+      t->retune = std::min(2 * t->retune, kRetune);
+    }
+    if (t->state == kTuneDecide) {
+      float m2 = 0.f, m1 = 0.f;
+      const hipError_t qe = hipEventQuery(t->e[3]);
+      if (qe == hipSuccess && hipEventElapsedTime(&m2, t->e[0], t->e[1]) == hipSuccess &&
+          hipEventElapsedTime(&m1, t->e[2], t->e[3]) == hipSuccess) {
+        t->ms[0] = m2;
+        t->ms[1] = m1;
+        if (m2 > 4.f * m1 || m1 > 4.f * m2) t->state = kWarm - 1;   // host gaps, not schedules: measure again
+        else t->groups = m2 <= m1 ? 2 : 1;
+        ++t->state;
+        static const bool trace = getenv("CGP_TUNE_TRACE") != nullptr;   // development aid: what was measured and decided
+        if (trace) fprintf(stderr, "cgp tune: ctx %p stream %p fits %d NT %d: two groups %.3f ms, one group %.3f ms per %d calls -> %s\n", (void *)c, (void *)s,
+                           batch, NT, m2, m1, kRun, t->state == kWarm ? "measure again" : (t->groups == 2 ? "two groups" : "one group"));
+      } else {
+        (void)hipGetLastError();   // not ready (or a failed query): nothing sticks, two groups for this call, ask again
+        if (qe != hipErrorNotReady) t->state = kTuneDecide + 1;
+      }
+    }
+    if (t->state == kTuneDecide) {
+      G = 2;
+    } else if (t->state > kTuneDecide) {
+      G = t->groups;
+      ++t->state;
+      // The stream -> hardware-queue mapping the decision rests on can change under a long-lived caller (other contexts and
+      // streams come and go): one call in a while is bracketed by two events that a LATER call reads without blocking; three
+      // such calls in a row at more than 1.3 x what the chosen form measured send the entry back to measuring.
+      if (t->mon[0] && t->mon[1]) {
+        if (t->mon_pending) {
+          const hipError_t qm = hipEventQuery(t->mon[1]);
+          if (qm == hipSuccess) {
+            float ms1 = 0.f;
+            const float base = t->ms[t->groups == 2 ? 0 : 1] / (float)kRun;
+            if (hipEventElapsedTime(&ms1, t->mon[0], t->mon[1]) == hipSuccess && base > 0.f) t->slow = ms1 > 1.3f * base ? t->slow + 1 : 0;
+            t->mon_pending = false;
+            if (t->slow >= 3) {
+              t->slow = 0;
+              t->state = kWarm;
+              static const bool trace2 = getenv("CGP_TUNE_TRACE") != nullptr;
+              if (trace2) fprintf(stderr, "cgp tune: ctx %p stream %p: three monitored calls above 1.3 x %.3f ms (last %.3f): measuring again\n", (void *)c, (void *)s, base, ms1);
+            }
+          } else (void)hipGetLastError();
+        } else if ((t->state & 7) == 0) {
+          tune_ev0 = t->mon[0];
+          tune_ev1 = t->mon[1];
+          t->mon_pending = true;
+        }
+      }
+    } else {
+      G = t->state < kWarm + kRun ? 2 : 1;
+      tune = t;
+      if (t->state == kWarm) tune_ev0 = t->e[0];
+      if (t->state == kWarm + kRun - 1) tune_ev1 = t->e[1];
+      if (t->state == kWarm + kRun) tune_ev0 = t->e[2];
+      if (t->state == kTuneDecide - 1) tune_ev1 = t->e[3];
+    }
+  }
+  return TuneStep{G, tune_ev0, tune_ev1, tune};
+}
+
 int ensure_fitted(cgp_ctx *c);   // below, with the short-window paths
 bool small_batch_predict_ok(const cgp_ctx *c, int batch, int N, int d, int M);
 int tick_table_entries_batch(int kid, int d, int batch, const double *X, int N, const double *Xs, int M);
@@ -211,27 +334,27 @@ int node_callback_small(cgp_ctx *c, const double *time_array, const double *slip
 bool grow_pinned(void *&p, size_t &cap, size_t bytes);
 bool grow_device(void *&p, size_t &cap, size_t bytes);
 void window_free(cgp_ctx *c, bool joint_only);   // cgp_window_host.hpp
-// cgp_joint_host.hpp.  What a joint call adds to a batch of fits: the contraction of the fits' V rows into their covariance slots.
-struct MultiCall;   // cgp_multi_host.hpp: the targets of a multi-target call
-struct PgradCall;   // cgp_pgrad_host.hpp: the arrays of a predictive-gradient call
-struct JointHook {
-  double *dcov;   // output form (batch, M, M) on the device; null: the scratch form for the factorisation
-  const MultiCall *multi = nullptr;   // a multi-target call instead: solve + contraction of the fits' P targets (dcov unused)
-  const PgradCall *pgrad = nullptr;   // a predictive-gradient call instead: backward solve + contraction (dcov unused)
+// What a batch entry point with more than mean / variance to compute (joint, multi-target, predictive-gradient calls) enqueues on s
+// for the `nfit` fits whose panels are slabs slab, slab + 1, ... into the slots slot, slot + 1, ... of its own arrays, while the
+// fits' V rows are still in the panel.  Each entry point builds its own, next to the arrays (fit_predict_batch_host calls it):
+// a function pointer and the closure it is called with, which the entry point keeps alive (nothing allocated, nothing exported).
+struct PostFit {
+  int (*fn)(const void *closure, int slab, int slot, int nfit, hipStream_t s);
+  const void *closure;
+  int operator()(int slab, int slot, int nfit, hipStream_t s) const { return fn(closure, slab, slot, nfit, s); }
 };
-void joint_free(cgp_ctx *c);
-int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, const double *dXs,
-                     const double *dtheta, const double *dvar, const int *dinfo, hipStream_t s);
-void multi_free(cgp_ctx *c);
-void multi_grad_free(cgp_ctx *c);   // cgp_multi_grad_host.hpp
-void pgrad_free(cgp_ctx *c);        // cgp_pgrad_host.hpp
-int pgrad_launch(cgp_ctx *c, const PgradCall &pc, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s);
-int multi_hook_launch(cgp_ctx *c, const MultiCall &mc, int N, int M, int slab, int slot, int nfit, hipStream_t s);
-// what the hook of a batch call enqueues for the fits in slabs slab ... into the slots slot ... of the call's arrays
-inline int post_fit_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s);
+template <typename F> PostFit post_fit(const F &f) {
+  return PostFit{[](const void *p, int slab, int slot, int nfit, hipStream_t s) { return (*static_cast<const F *>(p))(slab, slot, nfit, s); }, &f};
+}
 
 inline int ntheta(int kid, int d) { return k_ntheta(kid, d); }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// A one-dimensional grid of `work` workgroups dealt to the XCDs in turn: rounded up to a multiple of WF_XCDS
+inline int xcd_grid(long long work, unsigned &grid) {
+  if (work > (1ll << 30)) return CGP_EINVAL;
+  grid = (unsigned)(cdiv((int)work, WF_XCDS) * WF_XCDS);
+  return CGP_OK;
+}
 
 bool hip_ok(cgp_ctx *c, hipError_t e, const char *what) {
   if (e == hipSuccess) return true;
@@ -242,6 +365,32 @@ bool hip_ok(cgp_ctx *c, hipError_t e, const char *what) {
   do {                                                       \
     if (!hip_ok((ctx), (expr), #expr)) return CGP_EHIP;      \
   } while (0)
+
+void scratch_free(Scratch &r) {
+  if (r.buf) (void)hipFree(r.buf);
+  if (r.stage) (void)hipFree(r.stage);
+  r = Scratch{};
+}
+// after the call's own dtype / count checks: is there a reservation, and does it hold `batch` fits x `dim`
+int scratch_check(const Scratch &r, int batch, int dim) {
+  if (r.max_dim < 1) return CGP_ESTATE;
+  if (batch > r.max_batch || dim > r.max_dim) return CGP_ECAPACITY;
+  return CGP_OK;
+}
+// after the caller's own range checks: the old reservation goes, `bytes` of scratch come
+int scratch_reserve(cgp_ctx *c, Scratch &r, int max_batch, int max_dim, size_t bytes) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());   // an earlier call may still use the scratch that goes
+  scratch_free(r);
+  if (hipMalloc(&r.buf, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    r.buf = nullptr;
+    return CGP_ENOMEM;
+  }
+  r.max_batch = max_batch;
+  r.max_dim = max_dim;
+  return CGP_OK;
+}
 
 hipEvent_t get_event(cgp_ctx *c) {
   if (!c->pool.empty()) {
@@ -688,6 +837,31 @@ inline double refine_flops(const FitArgs &a, int nfits, int steps, bool solve) {
   return nfits * (ent * (3.0 * a.d + 20.0) + (solve ? (steps + 0.5) * 2.0 * a.N * a.N : 0.0));
 }
 
+// How every schedule of a call ends: decided once, at the head of run_schedule
+struct Epilogue {
+  bool in_rows, want_alpha;
+  int rsteps;   // refinement steps (0: none), with a solve for alpha_0 or on the alpha the fit call left, alpha of every fit or of the marked
+  bool rsolve, ralpha_all;
+};
+// The launches that end the schedule of the `nfits` fits from fit g0 of the call (a: their view), on L's stream and each bracketed
+// by L: k_finalize with TM test points per workgroup, k_alpha when the caller wants alpha, the fp32 refinement
+template <typename T, int TM>
+void launch_epilogue(cgp_ctx *c, Launcher &L, const FitArgs &a, const Epilogue &e, int nfits, int g0) {
+  L.begin(3, nfits * (4.0 * a.M * a.N + 2.0 * a.N));
+  hipLaunchKernelGGL((k_finalize<T, TM>), dim3(cdiv(a.M, TM) + 1, nfits), dim3(256), 0, L.s, a, e.in_rows ? 1 : 0);
+  L.end();
+  if (e.want_alpha) {
+    L.begin(4, nfits * (double)a.N * a.N);
+    hipLaunchKernelGGL(k_alpha<T>, dim3(nfits), dim3(256), alpha_lds_bytes(a.NT), L.s, a);
+    L.end();
+  }
+  if (e.rsteps > 0) {
+    L.begin(4, refine_flops(a, nfits, e.rsteps, e.rsolve));
+    launch_refine(c, a, nfits, g0, L.s, e.rsteps, e.rsolve, e.ralpha_all);
+    L.end();
+  }
+}
+
 // Enqueue the whole schedule for `batch` fits.  The batch is cut into up to c->nstreams contiguous
 // groups, one worker stream each, forked from / joined to the caller's stream `s` with events; the
 // launches are issued step-interleaved so every stream always has work queued.
@@ -706,6 +880,7 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
   const bool ralpha_all = rsolve && want_alpha;
   if (rsolve) want_alpha = false;   // alpha_0 comes from k_refine_solve (double precision, dref_a): no k_alpha launch
   if constexpr (sizeof(T) == 4) a.rflag = rsteps > 0 && refine_gated(c, a) ? c->dref_flag : nullptr;
+  const Epilogue ep{in_rows, want_alpha, rsteps, rsolve, ralpha_all};
   const int upd_lds = upd_lds_bytes<T>();
   const int tile_lds = potf2_lds_bytes<T>();
   const bool auto_groups = c->nstreams == 0;
@@ -726,126 +901,16 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
   // Since round 5 the engine takes that split by itself (cgp_set_streams(0), the default): every caller of a 56 ... 96-fit fp32
   // call -- cgp_sweep_*, a plain C host -- gets the 0.90 ms, not only a caller that knew to ask; cgp_set_streams(1) keeps one group.
   if (latency || (mid && sizeof(T) == 8)) G = 1;
-  cgp_ctx::GroupTune *tune = nullptr;   // non-null: this call belongs to the tuning runs
-  hipEvent_t tune_ev0 = nullptr, tune_ev1 = nullptr;   // events to record on the caller's stream before / after this call
+  TuneStep tune;
   if (mid && sizeof(T) == 4 && (G > 1 || auto_groups)) {
     G = batch >= 56 && batch / 2 > lat_fits<T>(a.NT) ? 2 : 1;
-    // Whether the two groups really run side by side depends on how the runtime mapped the caller's stream and the worker
-    // stream onto its few hardware queues -- the process's history, which nothing reports: the same 64-fit call took 0.89 ms
-    // on the legacy stream and 1.28 ms (the two groups in order: worse than one group's 0.98) on a fresh torch stream or on a
-    // context created later in the process (tools/sweep_probe.py, stream_probe.py; a probe with spin kernels did not predict
-    // it, both groups on the context's own streams was no better, and a single timed call does not show it: it is a
-    // steady-state effect of calls issued back to back).  So the default does not assume: per caller stream, after two
-    // warm-up calls, four eligible calls run as two groups and four as one, each run bracketed by events on the caller's
-    // stream, and from then on the faster form is used.  Results are bitwise the same either way.
-    // Every kRetune calls the two runs are repeated (a caller that first synchronises after every call and later issues calls
-    // back to back sees the other behaviour: sweep_probe.py's 1.24 ms): 8 calls in 264, half of them at the slower setting.
-    // The measurement never blocks the caller and never touches a stream that is being captured: the decision is read with
-    // hipEventQuery (until the last timed call has finished the call keeps two groups and asks again next time), an entry is
-    // keyed by (stream, fits, block steps) -- a caller that mixes shapes on one stream gets one decision per shape --, a pair
-    // of spans that differ by more than 4 x is the caller's own host gaps, not the schedules (discarded, measured again), and
-    // while the stream is capturing (cgp_set_streams documents fixing the form for graphs; this keeps the default safe) the
-    // call takes the form already decided, or two groups, without recording or reading any timing event.
-    constexpr int kWarm = 2, kRun = 4, kTuneDecide = kWarm + 2 * kRun, kRetune = 256;
-    if (G == 2 && auto_groups && in_rows && !c->prof) {
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      const bool capturing = hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
-      if (capturing) (void)hipGetLastError();
-      cgp_ctx::GroupTune *t = nullptr, *lru = &c->tune[0];
-      for (auto &e : c->tune) {
-        if (e.state >= 0 && e.stream == s && e.batch == batch && e.NT == a.NT) t = &e;
-        if (e.used < lru->used) lru = &e;
-      }
-      if (!t && !capturing) {
-        t = lru;
-        t->stream = s;
-        t->batch = batch;
-        t->NT = a.NT;
-        t->state = 0;
-        t->groups = 2;
-        for (auto &e : t->e)
-          if (!e && hipEventCreate(&e) != hipSuccess) {   // no events: keep the two groups, never measure
-            (void)hipGetLastError();
-            t->state = kTuneDecide + 1;
-          }
-        for (auto &e : t->mon)
-          if (!e && hipEventCreate(&e) != hipSuccess) (void)hipGetLastError();   // (no monitor then)
-        t->mon_pending = false;
-        t->slow = 0;
-        t->retune = 24;
-      }
-      if (capturing) {
-        G = t && t->state > kTuneDecide ? t->groups : 2;
-        t = nullptr;
-      }
-      if (t) {
-        t->used = ++c->tune_clock;
-        // (the first decisions are re-checked early: a context's first calls run while the part is still coming out of idle -- both forms
-      // then measure alike, 4.70 / 4.72 ms per four calls where warm they are 4.5 / 2.9 -- and the decision is a coin toss)
-      if (t->state > kTuneDecide + t->retune) {
-        t->state = kWarm;
-        t->retune = std::min(2 * t->retune, kRetune);
-      }
-        if (t->state == kTuneDecide) {
-          float m2 = 0.f, m1 = 0.f;
-          const hipError_t qe = hipEventQuery(t->e[3]);
-          if (qe == hipSuccess && hipEventElapsedTime(&m2, t->e[0], t->e[1]) == hipSuccess &&
-              hipEventElapsedTime(&m1, t->e[2], t->e[3]) == hipSuccess) {
-            t->ms[0] = m2;
-            t->ms[1] = m1;
-            if (m2 > 4.f * m1 || m1 > 4.f * m2) t->state = kWarm - 1;   // host gaps, not schedules: measure again
-            else t->groups = m2 <= m1 ? 2 : 1;
-            ++t->state;
-            static const bool trace = getenv("CGP_TUNE_TRACE") != nullptr;   // development aid: what was measured and decided
-            if (trace) fprintf(stderr, "cgp tune: ctx %p stream %p fits %d NT %d: two groups %.3f ms, one group %.3f ms per %d calls -> %s\n", (void *)c, (void *)s,
-                               batch, a.NT, m2, m1, kRun, t->state == kWarm ? "measure again" : (t->groups == 2 ? "two groups" : "one group"));
-          } else {
-            (void)hipGetLastError();   // not ready (or a failed query): nothing sticks, two groups for this call, ask again
-            if (qe != hipErrorNotReady) t->state = kTuneDecide + 1;
-          }
-        }
-        if (t->state == kTuneDecide) {
-          G = 2;
-        } else if (t->state > kTuneDecide) {
-          G = t->groups;
-          ++t->state;
-          // The stream -> hardware-queue mapping the decision rests on can change under a long-lived caller (other contexts and
-          // streams come and go): one call in a while is bracketed by two events that a LATER call reads without blocking; three
-          // such calls in a row at more than 1.3 x what the chosen form measured send the entry back to measuring.
-          if (t->mon[0] && t->mon[1]) {
-            if (t->mon_pending) {
-              const hipError_t qm = hipEventQuery(t->mon[1]);
-              if (qm == hipSuccess) {
-                float ms1 = 0.f;
-                const float base = t->ms[t->groups == 2 ? 0 : 1] / (float)kRun;
-                if (hipEventElapsedTime(&ms1, t->mon[0], t->mon[1]) == hipSuccess && base > 0.f) t->slow = ms1 > 1.3f * base ? t->slow + 1 : 0;
-                t->mon_pending = false;
-                if (t->slow >= 3) {
-                  t->slow = 0;
-                  t->state = kWarm;
-                  static const bool trace2 = getenv("CGP_TUNE_TRACE") != nullptr;
-                  if (trace2) fprintf(stderr, "cgp tune: ctx %p stream %p: three monitored calls above 1.3 x %.3f ms (last %.3f): measuring again\n", (void *)c, (void *)s, base, ms1);
-                }
-              } else (void)hipGetLastError();
-            } else if ((t->state & 7) == 0) {
-              tune_ev0 = t->mon[0];
-              tune_ev1 = t->mon[1];
-              t->mon_pending = true;
-            }
-          }
-        } else {
-          G = t->state < kWarm + kRun ? 2 : 1;
-          tune = t;
-          if (t->state == kWarm) tune_ev0 = t->e[0];
-          if (t->state == kWarm + kRun - 1) tune_ev1 = t->e[1];
-          if (t->state == kWarm + kRun) tune_ev0 = t->e[2];
-          if (t->state == kTuneDecide - 1) tune_ev1 = t->e[3];
-        }
-      }
+    if (G == 2 && auto_groups && in_rows && !c->prof) {   // the default does not assume that two groups run side by side: it measures
+      tune = tune_groups(c, batch, a.NT, s);
+      G = tune.groups;
     }
   }
   if (c->prof || !in_rows) G = 1;  // per-kernel timing wants isolated launches
-  if (tune_ev0) HIP_TRY(c, hipEventRecord(tune_ev0, s));
+  if (tune.ev0) HIP_TRY(c, hipEventRecord(tune.ev0, s));
   const bool fused64 = sw.fused_diag || batch < FUSED64_BELOW;
   const bool split_diag = sw.split_diag || !in_rows || (sizeof(T) == 8 && !fused64);
   // Mid-size calls: the extra rows (test points and y: M + 1 of them against N - 128 (k + 1) matrix rows, i.e. most of
@@ -912,9 +977,7 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
     launch_diag<T>(ga[0], batch, 0, sw.fat_diag, s, true);   // diagonal tile 0: nothing to run beside it yet
     int rc = run_sched<T>(c, ga[0], batch, s);
     if (rc != CGP_OK) return rc;
-    hipLaunchKernelGGL((k_finalize<T, 64>), dim3(cdiv(a.M, 64) + 1, batch), dim3(256), 0, s, ga[0], 1);
-    if (want_alpha) hipLaunchKernelGGL(k_alpha<T>, dim3(batch), dim3(256), alpha_lds_bytes(a.NT), s, ga[0]);
-    if (rsteps > 0) launch_refine(c, ga[0], batch, 0, s, rsteps, rsolve, ralpha_all);
+    launch_epilogue<T, 64>(c, L[0], ga[0], ep, batch, 0);
     HIP_TRY(c, hipGetLastError());
     return CGP_OK;
   }
@@ -957,9 +1020,8 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
       }
     }
     HIP_TRY(c, hipStreamWaitEvent(sA, ev(3 * (NT - 1) + 2), 0));
-    hipLaunchKernelGGL((k_finalize<T, 64>), dim3(cdiv(a.M, 64) + 1, B), dim3(256), 0, sA, ga[0], 1);
-    if (want_alpha) hipLaunchKernelGGL(k_alpha<T>, dim3(B), dim3(256), (a.NT * TS + TS) * sizeof(double), sA, ga[0]);
-    if (rsteps > 0) launch_refine(c, ga[0], B, 0, sA, rsteps, rsolve, ralpha_all);
+    Launcher LA{c, sA};
+    launch_epilogue<T, 64>(c, LA, ga[0], ep, B, 0);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_join[0], sA));
     HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join[0], 0));
@@ -992,19 +1054,7 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
         L[0].end();
       }
     }
-    L[0].begin(3, batch * (4.0 * a.M * a.N + 2.0 * a.N));
-    hipLaunchKernelGGL((k_finalize<T, 8>), dim3(cdiv(a.M, 8) + 1, batch), dim3(256), 0, s, ga[0], in_rows ? 1 : 0);
-    L[0].end();
-    if (want_alpha) {
-      L[0].begin(4, batch * (double)a.N * a.N);
-      hipLaunchKernelGGL(k_alpha<T>, dim3(batch), dim3(256), alpha_lds_bytes(a.NT), s, ga[0]);
-      L[0].end();
-    }
-    if (rsteps > 0) {
-      L[0].begin(4, refine_flops(a, batch, rsteps, rsolve));
-      launch_refine(c, ga[0], batch, 0, s, rsteps, rsolve, ralpha_all);
-      L[0].end();
-    }
+    launch_epilogue<T, 8>(c, L[0], ga[0], ep, batch, 0);
     HIP_TRY(c, hipGetLastError());
     return CGP_OK;
   }
@@ -1072,21 +1122,7 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
     HIP_TRY(c, hipEventRecord(c->ev_join[0], sE));
     HIP_TRY(c, hipStreamWaitEvent(gs[0], c->ev_join[0], 0));
   }
-  for (int g = 0, g0 = 0; g < G; g0 += gb[g], ++g) {
-    L[g].begin(3, gb[g] * (4.0 * a.M * a.N + 2.0 * a.N));
-    hipLaunchKernelGGL((k_finalize<T, 64>), dim3(cdiv(a.M, 64) + 1, gb[g]), dim3(256), 0, gs[g], ga[g], in_rows ? 1 : 0);
-    L[g].end();
-    if (want_alpha) {
-      L[g].begin(4, gb[g] * (double)a.N * a.N);
-      hipLaunchKernelGGL(k_alpha<T>, dim3(gb[g]), dim3(256), alpha_lds_bytes(a.NT), gs[g], ga[g]);
-      L[g].end();
-    }
-    if (rsteps > 0) {
-      L[g].begin(4, refine_flops(a, gb[g], rsteps, rsolve));
-      launch_refine(c, ga[g], gb[g], g0, gs[g], rsteps, rsolve, ralpha_all);
-      L[g].end();
-    }
-  }
+  for (int g = 0, g0 = 0; g < G; g0 += gb[g], ++g) launch_epilogue<T, 64>(c, L[g], ga[g], ep, gb[g], g0);
   HIP_TRY(c, hipGetLastError());
   for (int g = 0; g < G; ++g) {
     if (gs[g] == s) continue;   // ran on the caller's stream itself
@@ -1094,8 +1130,8 @@ int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha
     HIP_TRY(c, hipEventRecord(ej, gs[g]));
     HIP_TRY(c, hipStreamWaitEvent(s, ej, 0));
   }
-  if (tune_ev1) HIP_TRY(c, hipEventRecord(tune_ev1, s));
-  if (tune) ++tune->state;
+  if (tune.ev1) HIP_TRY(c, hipEventRecord(tune.ev1, s));
+  if (tune.entry) ++tune.entry->state;
   return CGP_OK;
 }
 
@@ -1134,6 +1170,23 @@ FitArgs base_args(cgp_ctx *c, int N, int d, int M, int kid, int include_noise) {
   a.dbg = dbg_env;  // timing ablations: results are wrong on purpose, cgp_build_flags() reports the build
 #endif
   return a;
+}
+// the nine arrays of a call (every pointer: its first fit), in the device dtype where void
+inline void set_call_arrays(FitArgs &a, const void *X, const void *y, const void *Xs, const double *theta, const double *jitter, void *mean,
+                            void *var, double *logml, int *info) {
+  a.X = X;
+  a.Xs = Xs;
+  a.y = y;
+  a.theta = theta;
+  a.jitter = jitter;
+  a.mean = mean;
+  a.var = var;
+  a.logml = logml;
+  a.info = info;
+}
+// ... of a call on the context's own copies (the single fit of cgp_fit, slot 0)
+inline void set_ctx_arrays(cgp_ctx *c, FitArgs &a) {
+  set_call_arrays(a, c->dX, c->dy, c->dXs, c->dtheta, c->djitter, c->dmean, c->dvar, c->dlogml, c->dinfo);
 }
 
 int check_shape(const cgp_ctx *c, int batch, int N, int d, int M, int kid) {
@@ -1460,10 +1513,7 @@ void cgp_destroy(cgp_ctx *c) {
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
   window_free(c, false);
-  joint_free(c);
-  multi_free(c);
-  multi_grad_free(c);
-  pgrad_free(c);
+  for (Scratch *r : {&c->fj, &c->mz, &c->ma, &c->pg}) scratch_free(*r);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -1592,15 +1642,7 @@ static int fit_predict_device(cgp_ctx *c, int batch, int N, int d, int M, int ki
   if (!dX || !dy || !dtheta || !dlogml || !dinfo || (M > 0 && (!dXs || !dmean || !dvar))) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   FitArgs a = base_args(c, N, d, M, kid, include_noise);
-  a.X = dX;
-  a.Xs = dXs;
-  a.y = dy;
-  a.theta = dtheta;
-  a.jitter = djitter;
-  a.mean = dmean;
-  a.var = dvar;
-  a.logml = dlogml;
-  a.info = dinfo;
+  set_call_arrays(a, dX, dy, dXs, dtheta, djitter, dmean, dvar, dlogml, dinfo);
   c->have_fit = false;
   c->lazy_fit = false;
   if (!tiled_only && !k_is_matern(kid) && small_batch_predict_ok(c, batch, N, d, M)) {   // short windows: fit + predictions of the whole batch in ONE launch, factors in LDS
@@ -1621,15 +1663,17 @@ int cgp_fit_predict_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int
                             false);
 }
 
-// jh: a joint call (cgp_joint_host.hpp, fp64) or a multi-target call (cgp_multi_host.hpp).  Tiled schedules for every shape, and
-// every fit's V rows are contracted (post_fit_launch: into its covariance slot, or with its P solved targets) while they are still in the panel: the whole batch before the ladder's first retry, a retried fit -- which runs
-// as a call of one fit, in slab 0 -- right after its retry.  mean / var may be NULL then (the device copies stay in the context).
+// post: what a joint, multi-target or predictive-gradient call (cgp_joint_host.hpp, cgp_multi_host.hpp, cgp_pgrad_host.hpp; fp64)
+// does with every fit's V rows while they are still in the panel: for the whole batch before the ladder's first retry, for a
+// retried fit -- which runs as a call of one fit, in slab 0 -- right after its retry.  Such a call reads the factor panel, so it
+// keeps the tiled schedules for every shape, and its mean / var may be NULL (the device copies stay in the context).
 static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, int kid, const double *X, const double *y,
                                   const double *Xs, const double *theta, int theta_stride, int include_noise,
-                                  double *mean, double *var, double *logml, int *info, const JointHook *jh) {
+                                  double *mean, double *var, double *logml, int *info, const PostFit *post) {
+  const bool reads_panel = post != nullptr;
   int rc = check_shape(c, batch, N, d, M, kid);
   if (rc != CGP_OK) return rc;
-  if (!X || !y || !theta || (M > 0 && (!Xs || (!jh && (!mean || !var))))) return CGP_EINVAL;
+  if (!X || !y || !theta || (M > 0 && (!Xs || (!reads_panel && (!mean || !var))))) return CGP_EINVAL;
   const int nth = ntheta(kid, d);
   if (theta_stride < nth) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1717,14 +1761,14 @@ static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, in
   }
   // (the scan that establishes "tick counts" is 1.5 ns per input on the host: 0.3 ms for 256 windows with their 599 test points,
   // more than the launch it would shorten by a tenth -- ensembles beyond 20 k inputs take the direct evaluation)
-  const int tick_tab = !jh && small_batch_predict_ok(c, batch, N, d, M) && (size_t)batch * (N + M) <= 20000
+  const int tick_tab = !reads_panel && small_batch_predict_ok(c, batch, N, d, M) && (size_t)batch * (N + M) <= 20000
                            ? tick_table_entries_batch(kid, d, batch, X, N, Xs, M) : 0;
   c->pending_tab = tick_tab;
   rc = fit_predict_device(c, batch, N, d, M, kid, c->dX, c->dy, c->dXs, c->dtheta, c->djitter,
-                          include_noise, c->dmean, c->dvar, c->dlogml, c->dinfo, CGP_STREAM_CTX, jh != nullptr);
+                          include_noise, c->dmean, c->dvar, c->dlogml, c->dinfo, CGP_STREAM_CTX, /*tiled_only=*/reads_panel);
   c->pending_tab = 0;
   if (rc != CGP_OK) return rc;
-  if (jh && (rc = post_fit_launch(c, *jh, N, d, M, kid, 0, 0, batch, s)) != CGP_OK) return rc;
+  if (post && (rc = (*post)(0, 0, batch, s)) != CGP_OK) return rc;
   char *hout = static_cast<char *>(c->pin_out);
   double *hl = reinterpret_cast<double *>(hout + out_elems * esz);
   int *hinfo = reinterpret_cast<int *>(hl + B);
@@ -1752,8 +1796,8 @@ static int fit_predict_batch_host(cgp_ctx *c, int batch, int N, int d, int M, in
         c, 1, N, d, M, kid, (char *)c->dX + (size_t)b * d * N * esz, (char *)c->dy + (size_t)b * N * esz,
         (char *)c->dXs + (size_t)b * d * M * esz, c->dtheta + (size_t)b * CGP_MAX_THETA, c->djitter + b,
         include_noise, (char *)c->dmean + (size_t)b * M * esz, (char *)c->dvar + (size_t)b * M * esz,
-        c->dlogml + b, c->dinfo + b, CGP_STREAM_CTX, jh != nullptr);
-    if (r == CGP_OK && jh) r = post_fit_launch(c, *jh, N, d, M, kid, 0, b, 1, s);
+        c->dlogml + b, c->dinfo + b, CGP_STREAM_CTX, /*tiled_only=*/reads_panel);
+    if (r == CGP_OK && post) r = (*post)(0, b, 1, s);
     return r;
   });
   if (rc != CGP_OK) return rc;
@@ -1824,15 +1868,7 @@ static int predict_enqueue(cgp_ctx *c, const double *Xs, int M, int include_nois
   pack_soa(Xs, M, c->fd, c->dtype, hxs, 0);
   HIP_TRY(c, hipMemcpyAsync(c->dXs, hxs.data(), hxs.size(), hipMemcpyHostToDevice, s));
   FitArgs a = base_args(c, c->fN, c->fd, M, c->fkernel, include_noise);
-  a.X = c->dX;
-  a.Xs = c->dXs;
-  a.y = c->dy;
-  a.theta = c->dtheta;
-  a.jitter = c->djitter;
-  a.mean = c->dmean;
-  a.var = c->dvar;
-  a.logml = c->dlogml;
-  a.info = c->dinfo;
+  set_ctx_arrays(c, a);
   return run(c, a, 1, false, false, s);
 }
 
@@ -1860,15 +1896,7 @@ int cgp_get_alpha(cgp_ctx *c, double *alpha) {
   // z is the y row of the factor panel; it sits at extra row index M of the LAST run.  Re-run the
   // y row alone (M = 0) so its position is known, then back-substitute.
   FitArgs a = base_args(c, c->fN, c->fd, 0, c->fkernel, 0);
-  a.X = c->dX;
-  a.Xs = c->dXs;
-  a.y = c->dy;
-  a.theta = c->dtheta;
-  a.jitter = c->djitter;
-  a.mean = c->dmean;
-  a.var = c->dvar;
-  a.logml = c->dlogml;
-  a.info = c->dinfo;
+  set_ctx_arrays(c, a);
   int rc = run(c, a, 1, false, true, s);
   if (rc != CGP_OK) return rc;
   if (c->dtype == CGP_F32 && c->refined) {   // the refined alpha is kept in double precision (cgp_refine.hpp)
@@ -2307,15 +2335,7 @@ int ensure_fitted(cgp_ctx *c) {
     HIP_TRY(c, hipMemcpyAsync(c->dtheta, th, sizeof th, hipMemcpyHostToDevice, s));   // pageable source: staged before the call returns
   }
   FitArgs a = base_args(c, c->fN, c->fd, 0, c->fkernel, 0);
-  a.X = c->dX;
-  a.Xs = c->dXs;
-  a.y = c->dy;
-  a.theta = c->dtheta;
-  a.jitter = c->djitter;
-  a.mean = c->dmean;
-  a.var = c->dvar;
-  a.logml = c->dlogml;
-  a.info = c->dinfo;
+  set_ctx_arrays(c, a);
   double jit = c->fjitter;
   int info = 0;
   // GPy's jitchol: one attempt without jitter, then five rungs mean(diag) 1e-6 10^r.  The short-window kernel may already

@@ -7,21 +7,25 @@
 
 namespace {
 
-void joint_free(cgp_ctx *c) {   // (declared in cgp_engine.hip for cgp_destroy)
-  for (void *&b : c->fjbuf) {
-    if (b) (void)hipFree(b);
-    b = nullptr;
-  }
-  if (c->fj_dev) (void)hipFree(c->fj_dev);
-  c->fj_dev = nullptr;
-  c->fj_dev_cap = 0;
-  c->fj_max_batch = c->fj_max_m = 0;
+// The arrays of a joint call on the device (all pointers: the call's first fit)
+struct JointCall {
+  const double *dXs, *dtheta, *dvar;
+  const int *dinfo;   // or null: a single fit known to be good
+  double *dcov;       // output form (batch, M, M); null: the scratch form for the factorisation
+};
+
+// the reservation: the matrices [max_batch][(mt * 16)^2], then the factorisations' failure words [max_batch]
+inline size_t joint_mat_doubles(int max_batch, int max_m) {
+  const size_t mpad = (size_t)cdiv(max_m, WPB) * WPB;
+  return (size_t)max_batch * mpad * mpad;
+}
+inline int *joint_fail_words(const cgp_ctx *c) {
+  return reinterpret_cast<int *>(static_cast<double *>(c->fj.buf) + joint_mat_doubles(c->fj.max_batch, c->fj.max_dim));
 }
 
 // The contraction of `nfit` fits whose panels are slabs slab, slab + 1, ... into the slots slot, slot + 1, ... of the call's
-// arrays (dXs, dtheta, dvar, dinfo: the call's first fit).  After run() has returned: a worker stream is joined by then.
-int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, const double *dXs,
-                     const double *dtheta, const double *dvar, const int *dinfo, hipStream_t s) {
+// arrays.  After run() has returned: a worker stream is joined by then.
+int joint_cov_launch(cgp_ctx *c, const JointCall &jc, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s) {
   JointFitArgs j{};
   const unsigned grid = joint_cov_grid(M, nfit, j.mt, j.nsup, j.npair, j.per_fit);
   if (grid == 0) return CGP_EINVAL;
@@ -30,17 +34,22 @@ int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int ki
   j.lw_stride = c->lw_stride;
   j.row0 = (size_t)cdiv(N, TS) * TS;
   j.ld = c->ld;
-  j.theta = dtheta + (size_t)slot * CGP_MAX_THETA;
-  j.Xs = dXs + (size_t)slot * d * M;
-  j.var = dvar + (size_t)slot * M;
-  j.info = dinfo ? dinfo + slot : nullptr;
-  j.cov = h.dcov ? h.dcov + (size_t)slot * M * M : nullptr;
-  j.C = static_cast<double *>(c->fjbuf[0]) + (size_t)slot * mpad * mpad;
+  j.theta = jc.dtheta + (size_t)slot * CGP_MAX_THETA;
+  j.Xs = jc.dXs + (size_t)slot * d * M;
+  j.var = jc.dvar + (size_t)slot * M;
+  j.info = jc.dinfo ? jc.dinfo + slot : nullptr;
+  j.cov = jc.dcov ? jc.dcov + (size_t)slot * M * M : nullptr;
+  j.C = static_cast<double *>(c->fj.buf) + (size_t)slot * mpad * mpad;
   j.N = N; j.d = d; j.M = M; j.kernel_id = kid; j.nfit = nfit;
-  if (h.dcov) hipLaunchKernelGGL(k_joint_cov<false>, dim3(grid), dim3(WJ_THREADS), 0, s, j);
+  if (jc.dcov) hipLaunchKernelGGL(k_joint_cov<false>, dim3(grid), dim3(WJ_THREADS), 0, s, j);
   else hipLaunchKernelGGL(k_joint_cov<true>, dim3(grid), dim3(WJ_THREADS), 0, s, j);
   if (!hip_ok(c, hipGetLastError(), "joint covariance launch")) return CGP_EHIP;
   return CGP_OK;
+}
+
+// a call whose test points, theta and variance are the context's own copies (the host entry points)
+inline JointCall joint_ctx_call(const cgp_ctx *c, const int *dinfo, double *dcov) {
+  return JointCall{static_cast<const double *>(c->dXs), c->dtheta, static_cast<const double *>(c->dvar), dinfo, dcov};
 }
 
 // C C^T = scratch matrix + jitter I in place, then out = mean + C xi, for the fits in slots [0, nfit): the windows' kernels through
@@ -48,8 +57,8 @@ int joint_cov_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int ki
 int joint_paths_launch(cgp_ctx *c, int nfit, int M, int S, const double *dmean, const double *dvar, const double *dxi, double jitter_rel,
                        double *dout, int *dsinfo, hipStream_t s) {
   JointArgs j{};
-  j.C = static_cast<double *>(c->fjbuf[0]);
-  j.jinfo = static_cast<int *>(c->fjbuf[1]);
+  j.C = static_cast<double *>(c->fj.buf);
+  j.jinfo = joint_fail_words(c);
   j.mean = dmean; j.var = dvar; j.xi = dxi; j.out = dout; j.info = dsinfo;
   j.jitter_rel = jitter_rel;
   j.M = M; j.S = S; j.nwin = nfit;
@@ -63,9 +72,7 @@ int joint_paths_launch(cgp_ctx *c, int nfit, int M, int S, const double *dmean, 
 // the checks every joint call starts with: dtype, reservation, the reservation's capacity
 int joint_check(const cgp_ctx *c, int batch, int M) {
   if (!c || c->dtype != CGP_F64 || M < 1) return CGP_EINVAL;
-  if (c->fj_max_m < 1) return CGP_ESTATE;
-  if (batch > c->fj_max_batch || M > c->fj_max_m) return CGP_ECAPACITY;
-  return CGP_OK;
+  return scratch_check(c->fj, batch, M);
 }
 
 inline int first_flagged_fit(const int *info, size_t n) {
@@ -79,21 +86,7 @@ inline int first_flagged_fit(const int *info, size_t n) {
 extern "C" int cgp_joint_reserve(cgp_ctx *c, int max_batch, int max_m) {
   if (!c || c->dtype != CGP_F64) return CGP_EINVAL;
   if (max_batch < 1 || max_batch > c->max_batch || max_m < 1 || max_m > std::min(c->max_m, 1024)) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipDeviceSynchronize());   // an earlier joint call may still read the buffers that go
-  joint_free(c);
-  const size_t mpad = (size_t)cdiv(max_m, WPB) * WPB;
-  const size_t sizes[2] = {(size_t)max_batch * mpad * mpad * sizeof(double), (size_t)max_batch * sizeof(int)};
-  for (int i = 0; i < 2; ++i)
-    if (hipMalloc(&c->fjbuf[i], sizes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      c->fjbuf[i] = nullptr;
-      joint_free(c);
-      return CGP_ENOMEM;
-    }
-  c->fj_max_batch = max_batch;
-  c->fj_max_m = max_m;
-  return CGP_OK;
+  return scratch_reserve(c, c->fj, max_batch, max_m, joint_mat_doubles(max_batch, max_m) * sizeof(double) + (size_t)max_batch * sizeof(int));
 }
 
 extern "C" int cgp_fit_predict_cov_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int kid, const double *dX, const double *dy,
@@ -105,7 +98,7 @@ extern "C" int cgp_fit_predict_cov_batch_device(cgp_ctx *c, int batch, int N, in
   double *dvar = static_cast<double *>(c->dvar);   // the fit's variance, the diagonal of cov: the context's own buffer
   rc = fit_predict_device(c, batch, N, d, M, kid, dX, dy, dXs, dtheta, djitter, include_noise, dmean, dvar, dlogml, dinfo, hip_stream, true);
   if (rc != CGP_OK) return rc;
-  return joint_cov_launch(c, JointHook{dcov}, N, d, M, kid, 0, 0, batch, dXs, dtheta, dvar, dinfo, pick_stream(c, hip_stream));
+  return joint_cov_launch(c, JointCall{dXs, dtheta, dvar, dinfo, dcov}, N, d, M, kid, 0, 0, batch, pick_stream(c, hip_stream));
 }
 
 extern "C" int cgp_fit_sample_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int kid, const double *dX, const double *dy,
@@ -119,7 +112,7 @@ extern "C" int cgp_fit_sample_batch_device(cgp_ctx *c, int batch, int N, int d, 
   rc = fit_predict_device(c, batch, N, d, M, kid, dX, dy, dXs, dtheta, djitter, include_noise, dmean, dvar, dlogml, dinfo, hip_stream, true);
   if (rc != CGP_OK) return rc;
   hipStream_t s = pick_stream(c, hip_stream);
-  rc = joint_cov_launch(c, JointHook{nullptr}, N, d, M, kid, 0, 0, batch, dXs, dtheta, dvar, dinfo, s);
+  rc = joint_cov_launch(c, JointCall{dXs, dtheta, dvar, dinfo, nullptr}, N, d, M, kid, 0, 0, batch, s);
   if (rc != CGP_OK) return rc;
   return joint_paths_launch(c, batch, M, S, dmean, dvar, dxi, jitter_rel, dout, dsinfo, s);
 }
@@ -131,10 +124,12 @@ extern "C" int cgp_fit_predict_cov_batch(cgp_ctx *c, int batch, int N, int d, in
   if (rc != CGP_OK) return rc;
   if (!mean || !cov) return CGP_EINVAL;
   // the output form goes to the reservation, (M, M) per fit, and from there to the caller
-  const JointHook jh{static_cast<double *>(c->fjbuf[0])};
-  rc = fit_predict_batch_host(c, batch, N, d, M, kid, X, y, Xs, theta, theta_stride, include_noise, mean, nullptr, logml, info, &jh);
+  const JointCall jc = joint_ctx_call(c, c->dinfo, static_cast<double *>(c->fj.buf));
+  const auto hook = [&](int slab, int slot, int nfit, hipStream_t s) { return joint_cov_launch(c, jc, N, d, M, kid, slab, slot, nfit, s); };
+  const PostFit post = post_fit(hook);
+  rc = fit_predict_batch_host(c, batch, N, d, M, kid, X, y, Xs, theta, theta_stride, include_noise, mean, nullptr, logml, info, &post);
   if (rc < 0) return rc;
-  HIP_TRY(c, hipMemcpyAsync(cov, jh.dcov, (size_t)batch * M * M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(cov, jc.dcov, (size_t)batch * M * M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return rc;
 }
@@ -144,8 +139,8 @@ namespace {
 // the two host sampling calls share.  Returns 0 or the 1-based index of the first fit whose paths are NaN.
 int joint_sample_host(cgp_ctx *c, int nfit, int M, int S, const double *xi, double jitter_rel, double *out, int *sinfo) {
   const size_t np = (size_t)nfit * S * M;
-  if (!grow_device(c->fj_dev, c->fj_dev_cap, 2 * np * sizeof(double))) return CGP_ENOMEM;
-  double *dxi = static_cast<double *>(c->fj_dev), *dout = dxi + np;
+  if (!grow_device(c->fj.stage, c->fj.stage_cap, 2 * np * sizeof(double))) return CGP_ENOMEM;
+  double *dxi = static_cast<double *>(c->fj.stage), *dout = dxi + np;
   hipStream_t s = c->stream;
   HIP_TRY(c, hipMemcpyAsync(dxi, xi, np * sizeof(double), hipMemcpyHostToDevice, s));
   int rc = joint_paths_launch(c, nfit, M, S, static_cast<const double *>(c->dmean), static_cast<const double *>(c->dvar), dxi, jitter_rel,
@@ -153,7 +148,7 @@ int joint_sample_host(cgp_ctx *c, int nfit, int M, int S, const double *xi, doub
   if (rc != CGP_OK) return rc;
   std::vector<int> hi(nfit);
   HIP_TRY(c, hipMemcpyAsync(out, dout, np * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(hi.data(), c->fjbuf[1], (size_t)nfit * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(hi.data(), joint_fail_words(c), (size_t)nfit * sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   if (sinfo) memcpy(sinfo, hi.data(), (size_t)nfit * sizeof(int));
   return first_flagged_fit(hi.data(), nfit);
@@ -166,8 +161,10 @@ extern "C" int cgp_fit_sample_batch(cgp_ctx *c, int batch, int N, int d, int M, 
   int rc = joint_check(c, batch, M);
   if (rc != CGP_OK) return rc;
   if (S < 1 || !xi || !out || !(jitter_rel >= 0.0)) return CGP_EINVAL;
-  const JointHook jh{nullptr};
-  rc = fit_predict_batch_host(c, batch, N, d, M, kid, X, y, Xs, theta, theta_stride, include_noise, nullptr, nullptr, logml, info, &jh);
+  const JointCall jc = joint_ctx_call(c, c->dinfo, nullptr);
+  const auto hook = [&](int slab, int slot, int nfit, hipStream_t s) { return joint_cov_launch(c, jc, N, d, M, kid, slab, slot, nfit, s); };
+  const PostFit post = post_fit(hook);
+  rc = fit_predict_batch_host(c, batch, N, d, M, kid, X, y, Xs, theta, theta_stride, include_noise, nullptr, nullptr, logml, info, &post);
   if (rc < 0) return rc;
   return joint_sample_host(c, batch, M, S, xi, jitter_rel, out, sinfo);
 }
@@ -179,12 +176,10 @@ extern "C" int cgp_predict_cov(cgp_ctx *c, const double *Xs, int M, int include_
   if (!Xs || !mean || !cov) return CGP_EINVAL;
   if ((rc = predict_enqueue(c, Xs, M, include_noise)) != CGP_OK) return rc;
   hipStream_t s = c->stream;
-  const JointHook jh{static_cast<double *>(c->fjbuf[0])};
-  rc = joint_cov_launch(c, jh, c->fN, c->fd, M, c->fkernel, 0, 0, 1, static_cast<const double *>(c->dXs), c->dtheta,
-                        static_cast<const double *>(c->dvar), nullptr, s);
-  if (rc != CGP_OK) return rc;
+  const JointCall jc = joint_ctx_call(c, nullptr, static_cast<double *>(c->fj.buf));
+  if ((rc = joint_cov_launch(c, jc, c->fN, c->fd, M, c->fkernel, 0, 0, 1, s)) != CGP_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(mean, c->dmean, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(cov, jh.dcov, (size_t)M * M * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(cov, jc.dcov, (size_t)M * M * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return CGP_OK;
 }
@@ -195,8 +190,6 @@ extern "C" int cgp_sample(cgp_ctx *c, const double *Xs, int M, int S, const doub
   if (rc != CGP_OK) return rc;
   if (S < 1 || !Xs || !xi || !out || !(jitter_rel >= 0.0)) return CGP_EINVAL;
   if ((rc = predict_enqueue(c, Xs, M, include_noise)) != CGP_OK) return rc;
-  rc = joint_cov_launch(c, JointHook{nullptr}, c->fN, c->fd, M, c->fkernel, 0, 0, 1, static_cast<const double *>(c->dXs), c->dtheta,
-                        static_cast<const double *>(c->dvar), nullptr, c->stream);
-  if (rc != CGP_OK) return rc;
+  if ((rc = joint_cov_launch(c, joint_ctx_call(c, nullptr, nullptr), c->fN, c->fd, M, c->fkernel, 0, 0, 1, c->stream)) != CGP_OK) return rc;
   return joint_sample_host(c, 1, M, S, xi, jitter_rel, out, info);
 }

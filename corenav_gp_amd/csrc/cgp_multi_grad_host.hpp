@@ -6,15 +6,6 @@
 
 namespace {
 
-void multi_grad_free(cgp_ctx *c) {   // (declared in cgp_engine.hip for cgp_destroy)
-  if (c->ma) (void)hipFree(c->ma);
-  c->ma = nullptr;
-  c->ma_max_batch = c->ma_max_p = 0;
-  if (c->ma_dev) (void)hipFree(c->ma_dev);
-  c->ma_dev = nullptr;
-  c->ma_dev_cap = 0;
-}
-
 inline size_t multi_grad_a_doubles(const cgp_ctx *c, int max_batch, int max_p) {
   return (size_t)max_batch * c->NTmax * TS * ((size_t)cdiv(max_p, KT) * KT);
 }
@@ -22,9 +13,9 @@ inline size_t multi_grad_a_doubles(const cgp_ctx *c, int max_batch, int max_p) {
 // the checks every call of this section starts with: dtype, P, both reservations, their capacity
 int multi_grad_check(const cgp_ctx *c, int batch, int P) {
   if (!c || c->dtype != CGP_F64 || P < 1) return CGP_EINVAL;
-  if (c->mz_max_p < 1 || c->ma_max_p < 1) return CGP_ESTATE;
-  if (batch > c->mz_max_batch || P > c->mz_max_p || batch > c->ma_max_batch || P > c->ma_max_p) return CGP_ECAPACITY;
-  return CGP_OK;
+  const int rz = scratch_check(c->mz, batch, P), ra = scratch_check(c->ma, batch, P);
+  if (rz == CGP_ESTATE || ra == CGP_ESTATE) return CGP_ESTATE;   // a missing reservation before a small one
+  return rz != CGP_OK ? rz : ra;
 }
 
 // One evaluation of `nfit` fits: slabs 0 .. nfit - 1 of the context, slots slot .. of the call's arrays (every pointer: the
@@ -34,7 +25,7 @@ int multi_grad_enqueue(cgp_ctx *c, int slot, int nfit, int N, int d, int P, int 
                        const double *dtheta, const double *djitter, double *dnll, double *dgrad, int grad_stride, double *dlogml,
                        int *dinfo, hipStream_t s) {
   double *dy0 = static_cast<double *>(c->dy);
-  if (!dlogml) dlogml = static_cast<double *>(c->ma) + multi_grad_a_doubles(c, c->ma_max_batch, c->ma_max_p);   // the reservation's own (batch, P)
+  if (!dlogml) dlogml = static_cast<double *>(c->ma.buf) + multi_grad_a_doubles(c, c->ma.max_batch, c->ma.max_dim);   // the reservation's own (batch, P)
   MultiArgs ma = multi_args(c, N, 0, P, 0, slot, nfit, dY, dy0, nullptr, nullptr, dlogml, dinfo);
   int rc = multi_pack_launch(c, ma, s);
   if (rc != CGP_OK) return rc;
@@ -46,13 +37,7 @@ int multi_grad_enqueue(cgp_ctx *c, int slot, int nfit, int N, int d, int P, int 
   a.info = dinfo + slot;
   rc = run(c, a, nfit, true, true, s);
   if (rc != CGP_OK) return rc;
-  const bool h64 = multi_rows64(c, nfit, P);
-  ma.stiles = cdiv(P, h64 ? HR : TS);
-  const long long nsolve = (long long)nfit * ma.stiles;
-  if (nsolve > (1ll << 30)) return CGP_EINVAL;
-  const unsigned gs = (unsigned)(cdiv((int)nsolve, WF_XCDS) * WF_XCDS);
-  if (h64) hipLaunchKernelGGL(k_multi_solve<true>, dim3(gs), dim3(256), multi_lds_bytes(), s, ma);
-  else hipLaunchKernelGGL(k_multi_solve<false>, dim3(gs), dim3(256), multi_lds_bytes(), s, ma);
+  if ((rc = multi_solve_launch(c, ma, s)) != CGP_OK) return rc;
   hipLaunchKernelGGL(k_multi_logml, dim3(nfit), dim3(ML_THREADS), 0, s, ma);
   MultiGradArgs g{};
   g.Zw = ma.Zw;
@@ -62,7 +47,7 @@ int multi_grad_enqueue(cgp_ctx *c, int slot, int nfit, int N, int d, int P, int 
   g.P16 = cdiv(P, KT) * KT;
   g.lda = a.NT * TS;
   g.a_stride = (size_t)g.lda * g.P16;
-  g.Aw = static_cast<double *>(c->ma);
+  g.Aw = static_cast<double *>(c->ma.buf);
   g.logml = ma.logml;
   g.nll = dnll + slot;
   g.grad = dgrad + (size_t)slot * grad_stride;
@@ -86,8 +71,8 @@ struct MultiGradStage {
 };
 int multi_grad_stage(cgp_ctx *c, int batch, int N, int P, MultiGradStage &st) {
   const size_t B = batch, nY = B * P * N;
-  if (!grow_device(c->ma_dev, c->ma_dev_cap, (nY + B + B * CGP_MAX_THETA + B * P) * sizeof(double))) return CGP_ENOMEM;
-  st.dY = static_cast<double *>(c->ma_dev);
+  if (!grow_device(c->ma.stage, c->ma.stage_cap, (nY + B + B * CGP_MAX_THETA + B * P) * sizeof(double))) return CGP_ENOMEM;
+  st.dY = static_cast<double *>(c->ma.stage);
   st.dnll = st.dY + nY;
   st.dgrad = st.dnll + B;
   st.dlogml = st.dgrad + B * CGP_MAX_THETA;
@@ -127,23 +112,13 @@ int multi_grad_eval_host(cgp_ctx *c, int batch, int N, int d, int P, int kid, co
 extern "C" int cgp_multi_grad_reserve(cgp_ctx *c, int max_batch, int max_p) {
   if (!c || c->dtype != CGP_F64) return CGP_EINVAL;
   if (max_batch < 1 || max_batch > c->max_batch || max_p < 1 || max_p > MULTI_MAX_P) return CGP_EINVAL;
-  if (max_batch > c->mz_max_batch || max_p > c->mz_max_p) return CGP_ESTATE;   // cgp_multi_reserve first, and one that covers this
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipDeviceSynchronize());   // an earlier call may still use the scratch that goes
-  multi_grad_free(c);
+  if (max_batch > c->mz.max_batch || max_p > c->mz.max_dim) return CGP_ESTATE;   // cgp_multi_reserve first, and one that covers this
+  HIP_TRY(c, hipSetDevice(c->device));   // (the attribute goes to the current device's function)
   for (const void *fn : {reinterpret_cast<const void *>(&k_multi_alpha), reinterpret_cast<const void *>(&k_multi_grad<0>),
                          reinterpret_cast<const void *>(&k_multi_grad<1>), reinterpret_cast<const void *>(&k_multi_grad<2>)})
     HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, upd_lds_bytes<double>()));
   // A of every fit, then (max_batch, max_p) logml for the calls that pass none
-  const size_t bytes = (multi_grad_a_doubles(c, max_batch, max_p) + (size_t)max_batch * max_p) * sizeof(double);
-  if (hipMalloc(&c->ma, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    c->ma = nullptr;
-    return CGP_ENOMEM;
-  }
-  c->ma_max_batch = max_batch;
-  c->ma_max_p = max_p;
-  return CGP_OK;
+  return scratch_reserve(c, c->ma, max_batch, max_p, (multi_grad_a_doubles(c, max_batch, max_p) + (size_t)max_batch * max_p) * sizeof(double));
 }
 
 extern "C" int cgp_multi_nll_grad_batch_device(cgp_ctx *c, int batch, int N, int d, int P, int kid, const double *dX, const double *dY,

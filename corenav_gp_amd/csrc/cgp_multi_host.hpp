@@ -7,23 +7,6 @@ namespace {
 
 constexpr int MULTI_MAX_P = 4096;   // corenav_gp.h states it
 
-// The targets of a multi-target call, on the device: what fit_predict_batch_host's hook needs beside the call's own arrays.
-struct MultiCall {
-  int P;
-  const double *dY;   // (batch, P, N)
-  double *dmean;      // (batch, P, M)
-  double *dlogml;     // (batch, P)
-};
-
-void multi_free(cgp_ctx *c) {   // (declared in cgp_engine.hip for cgp_destroy)
-  if (c->mz) (void)hipFree(c->mz);
-  c->mz = nullptr;
-  c->mz_max_batch = c->mz_max_p = 0;
-  if (c->mz_dev) (void)hipFree(c->mz_dev);
-  c->mz_dev = nullptr;
-  c->mz_dev_cap = 0;
-}
-
 constexpr int multi_lds_bytes() { return std::max(upd_lds_bytes<double>(), WIMG * (int)sizeof(double)); }
 
 // Tile height of the solve, from (fits, P) ONLY -- never from N or M, so a column's bits can be followed from the call's size.  Half
@@ -48,7 +31,7 @@ MultiArgs multi_args(cgp_ctx *c, int N, int M, int P, int slab, int slot, int nf
   a.ld = c->ld;
   a.Winv = static_cast<const double *>(c->Winv) + (size_t)slab * c->winv_stride;
   a.winv_stride = c->winv_stride;
-  a.Zw = static_cast<double *>(c->mz) + (size_t)slot * a.z_stride;
+  a.Zw = static_cast<double *>(c->mz.buf) + (size_t)slot * a.z_stride;
   a.Y = dY + (size_t)slot * P * N;
   a.y0 = dy0 ? dy0 + (size_t)slot * N : nullptr;
   a.mean = dmean ? dmean + (size_t)slot * P * M : nullptr;
@@ -72,43 +55,31 @@ int multi_pack_launch(cgp_ctx *c, const MultiArgs &a, hipStream_t s) {
   return CGP_OK;
 }
 
-// after the fits: Z = L^-1 Y in place, mean = V^T Z, logml; three launches
-int multi_post_launch(cgp_ctx *c, MultiArgs a, hipStream_t s) {
+// Z = L^-1 Y in place: the tile height chosen (a.stiles follows it: the later launches of the call read it), one launch
+int multi_solve_launch(cgp_ctx *c, MultiArgs &a, hipStream_t s) {
   const bool h64 = multi_rows64(c, a.nfit, a.P);
   a.stiles = cdiv(a.P, h64 ? HR : TS);
-  const long long nsolve = (long long)a.nfit * a.stiles, nmean = (long long)a.nfit * a.per_fit;
-  if (nsolve > (1ll << 30) || nmean > (1ll << 30)) return CGP_EINVAL;
-  const unsigned gs = (unsigned)(cdiv((int)nsolve, WF_XCDS) * WF_XCDS), gm = (unsigned)(cdiv((int)nmean, WF_XCDS) * WF_XCDS);
+  unsigned gs = 0;
+  if (xcd_grid((long long)a.nfit * a.stiles, gs) != CGP_OK) return CGP_EINVAL;
   if (h64) hipLaunchKernelGGL(k_multi_solve<true>, dim3(gs), dim3(256), multi_lds_bytes(), s, a);
   else hipLaunchKernelGGL(k_multi_solve<false>, dim3(gs), dim3(256), multi_lds_bytes(), s, a);
+  return CGP_OK;
+}
+
+// after the fits: the solve, mean = V^T Z, logml; three launches
+int multi_post_launch(cgp_ctx *c, MultiArgs a, hipStream_t s) {
+  unsigned gm = 0;
+  if (xcd_grid((long long)a.nfit * a.per_fit, gm) != CGP_OK || multi_solve_launch(c, a, s) != CGP_OK) return CGP_EINVAL;
   hipLaunchKernelGGL(k_multi_mean, dim3(gm), dim3(WJ_THREADS), 0, s, a);
   hipLaunchKernelGGL(k_multi_logml, dim3(a.nfit), dim3(ML_THREADS), 0, s, a);
   if (!hip_ok(c, hipGetLastError(), "multi-target solve / mean launches")) return CGP_EHIP;
   return CGP_OK;
 }
 
-// fit_predict_batch_host's hook: the fits' targets are packed again (a retried fit's right-hand sides were solved in place
-// against the factor that failed), solved and contracted
-int multi_hook_launch(cgp_ctx *c, const MultiCall &mc, int N, int M, int slab, int slot, int nfit, hipStream_t s) {
-  const MultiArgs a = multi_args(c, N, M, mc.P, slab, slot, nfit, mc.dY, nullptr, mc.dmean, static_cast<double *>(c->dvar), mc.dlogml,
-                                 c->dinfo);
-  const int rc = multi_pack_launch(c, a, s);
-  return rc != CGP_OK ? rc : multi_post_launch(c, a, s);
-}
-
-inline int post_fit_launch(cgp_ctx *c, const JointHook &h, int N, int d, int M, int kid, int slab, int slot, int nfit, hipStream_t s) {
-  if (h.multi) return multi_hook_launch(c, *h.multi, N, M, slab, slot, nfit, s);
-  if (h.pgrad) return pgrad_launch(c, *h.pgrad, N, d, M, kid, slab, slot, nfit, s);
-  return joint_cov_launch(c, h, N, d, M, kid, slab, slot, nfit, static_cast<const double *>(c->dXs), c->dtheta,
-                          static_cast<const double *>(c->dvar), c->dinfo, s);
-}
-
 // the checks every multi-target call starts with: dtype, counts, reservation, the reservation's capacity
 int multi_check(const cgp_ctx *c, int batch, int M, int P) {
   if (!c || c->dtype != CGP_F64 || M < 1 || P < 1) return CGP_EINVAL;
-  if (c->mz_max_p < 1) return CGP_ESTATE;
-  if (batch > c->mz_max_batch || P > c->mz_max_p) return CGP_ECAPACITY;
-  return CGP_OK;
+  return scratch_check(c->mz, batch, P);
 }
 
 }  // namespace
@@ -116,20 +87,10 @@ int multi_check(const cgp_ctx *c, int batch, int M, int P) {
 extern "C" int cgp_multi_reserve(cgp_ctx *c, int max_batch, int max_p) {
   if (!c || c->dtype != CGP_F64) return CGP_EINVAL;
   if (max_batch < 1 || max_batch > c->max_batch || max_p < 1 || max_p > MULTI_MAX_P) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipDeviceSynchronize());   // an earlier call may still use the scratch that goes
-  multi_free(c);
+  HIP_TRY(c, hipSetDevice(c->device));   // (the attribute goes to the current device's function)
   for (const void *fn : {reinterpret_cast<const void *>(&k_multi_solve<true>), reinterpret_cast<const void *>(&k_multi_solve<false>)})
     HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, multi_lds_bytes()));
-  const size_t bytes = (size_t)max_batch * c->NTmax * TS * ((size_t)cdiv(max_p, TS) * TS) * sizeof(double);
-  if (hipMalloc(&c->mz, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    c->mz = nullptr;
-    return CGP_ENOMEM;
-  }
-  c->mz_max_batch = max_batch;
-  c->mz_max_p = max_p;
-  return CGP_OK;
+  return scratch_reserve(c, c->mz, max_batch, max_p, (size_t)max_batch * c->NTmax * TS * ((size_t)cdiv(max_p, TS) * TS) * sizeof(double));
 }
 
 extern "C" int cgp_multi_set_form(cgp_ctx *c, int rows) {
@@ -168,16 +129,22 @@ extern "C" int cgp_fit_predict_multi_batch(cgp_ctx *c, int batch, int N, int d, 
   if (theta_stride < ntheta(kid, d)) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t B = batch, nY = B * P * N, nmean = B * P * M, nl = B * P;
-  if (!grow_device(c->mz_dev, c->mz_dev_cap, (nY + nmean + nl) * sizeof(double))) return CGP_ENOMEM;
-  double *dY = static_cast<double *>(c->mz_dev), *dmean = dY + nY, *dlogml = dmean + nmean;
+  if (!grow_device(c->mz.stage, c->mz.stage_cap, (nY + nmean + nl) * sizeof(double))) return CGP_ENOMEM;
+  double *dY = static_cast<double *>(c->mz.stage), *dmean = dY + nY, *dlogml = dmean + nmean;
   HIP_TRY(c, hipMemcpyAsync(dY, Y, nY * sizeof(double), hipMemcpyHostToDevice, c->stream));
   std::vector<double> y0(B * N);   // the fit schedule's y: each fit's column 0
   for (size_t b = 0; b < B; ++b) memcpy(&y0[b * N], Y + b * P * N, (size_t)N * sizeof(double));
   std::vector<int> hinfo(B);
-  const MultiCall mc{P, dY, dmean, dlogml};
-  const JointHook jh{nullptr, &mc};
+  // after the fits: their targets are packed again (a retried fit's right-hand sides were solved in place against the factor that
+  // failed), solved and contracted
+  const auto hook = [&](int slab, int slot, int nfit, hipStream_t s) {
+    const MultiArgs a = multi_args(c, N, M, P, slab, slot, nfit, dY, nullptr, dmean, static_cast<double *>(c->dvar), dlogml, c->dinfo);
+    const int r = multi_pack_launch(c, a, s);
+    return r != CGP_OK ? r : multi_post_launch(c, a, s);
+  };
+  const PostFit post = post_fit(hook);
   rc = fit_predict_batch_host(c, batch, N, d, M, kid, X, y0.data(), Xs, theta, theta_stride, include_noise, nullptr, var, nullptr,
-                              hinfo.data(), &jh);
+                              hinfo.data(), &post);
   if (rc < 0) return rc;
   HIP_TRY(c, hipMemcpyAsync(mean, dmean, nmean * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   std::vector<double> hl(logml ? nl : 0);

@@ -1,28 +1,18 @@
 // cgp_pgrad_host.hpp -- host side of the predictive gradients after batch / single fits (kernels: cgp_pgrad.hpp).  Not a
 // translation unit of its own: cgp_engine.hip includes it after the fit entry points it builds on (fit_predict_device,
-// fit_predict_batch_host, predict_enqueue) and after cgp_joint_host.hpp / cgp_multi_host.hpp, whose post_fit_launch hands the fits
-// of a host call to pgrad_launch.  fp64 contexts only: every entry point answers CGP_EINVAL in a CGP_F32 context before anything
-// is enqueued.
+// fit_predict_batch_host, predict_enqueue); it uses nothing of the other features' host headers.  fp64 contexts only: every entry
+// point answers CGP_EINVAL in a CGP_F32 context before anything is enqueued.
 #pragma once
 
 namespace {
 
-// The arrays of a predictive-gradient call on the device (all pointers: the call's first fit): what fit_predict_batch_host's hook
-// needs beside the factor panel.
+// The arrays of a predictive-gradient call on the device (all pointers: the call's first fit): what pgrad_launch needs beside the
+// factor panel.
 struct PgradCall {
   const double *dX, *dXs, *dtheta;
   const int *dinfo;          // or null: a single fit known to be good
   double *ddmean, *ddvar;    // (batch, M, d); either may be null
 };
-
-void pgrad_free(cgp_ctx *c) {   // (declared in cgp_engine.hip for cgp_destroy)
-  if (c->pgbuf) (void)hipFree(c->pgbuf);
-  c->pgbuf = nullptr;
-  c->pg_max_batch = c->pg_max_m = 0;
-  if (c->pg_dev) (void)hipFree(c->pg_dev);
-  c->pg_dev = nullptr;
-  c->pg_dev_cap = 0;
-}
 
 // Backward solve and contraction of `nfit` fits whose panels are slabs slab, slab + 1, ... into the slots slot, slot + 1, ... of
 // the call's arrays and of the scratch.  After run() has returned: a worker stream is joined by then.
@@ -37,7 +27,7 @@ int pgrad_launch(cgp_ctx *c, const PgradCall &pc, int N, int d, int M, int kid, 
   a.ld = c->ld;
   a.Winv = static_cast<const double *>(c->Winv) + (size_t)slab * c->winv_stride;
   a.winv_stride = c->winv_stride;
-  a.Bw = static_cast<double *>(c->pgbuf) + (size_t)slot * a.b_stride;
+  a.Bw = static_cast<double *>(c->pg.buf) + (size_t)slot * a.b_stride;
   a.X = pc.dX + (size_t)slot * d * N;
   a.Xs = pc.dXs + (size_t)slot * d * M;
   a.theta = pc.dtheta + (size_t)slot * CGP_MAX_THETA;
@@ -46,9 +36,8 @@ int pgrad_launch(cgp_ctx *c, const PgradCall &pc, int N, int d, int M, int kid, 
   a.dvar = pc.ddvar ? pc.ddvar + (size_t)slot * M * d : nullptr;
   a.row0 = (size_t)a.NT * TS;
   a.N = N; a.d = d; a.M = M; a.nfit = nfit;
-  const long long nsolve = (long long)nfit * a.stiles;
-  if (nsolve > (1ll << 30) || nfit > 65535) return CGP_EINVAL;
-  const unsigned gs = (unsigned)(cdiv((int)nsolve, WF_XCDS) * WF_XCDS);
+  unsigned gs = 0;
+  if (nfit > 65535 || xcd_grid((long long)nfit * a.stiles, gs) != CGP_OK) return CGP_EINVAL;
   hipLaunchKernelGGL(k_pgrad_solve, dim3(gs), dim3(256), 0, s, a);
   const dim3 gc(cdiv(M, 64), nfit);
   if (kid == K_RBF_BROWNIAN) hipLaunchKernelGGL(k_pgrad_contract<PGK_BROWN>, gc, dim3(256), 0, s, a, kid);
@@ -62,9 +51,7 @@ int pgrad_launch(cgp_ctx *c, const PgradCall &pc, int N, int d, int M, int kid, 
 // the checks every predictive-gradient call starts with: dtype, reservation, the reservation's capacity
 int pgrad_check(const cgp_ctx *c, int batch, int M) {
   if (!c || c->dtype != CGP_F64 || M < 1) return CGP_EINVAL;
-  if (c->pg_max_m < 1) return CGP_ESTATE;
-  if (batch > c->pg_max_batch || M > c->pg_max_m) return CGP_ECAPACITY;
-  return CGP_OK;
+  return scratch_check(c->pg, batch, M);
 }
 
 }  // namespace
@@ -72,18 +59,7 @@ int pgrad_check(const cgp_ctx *c, int batch, int M) {
 extern "C" int cgp_pgrad_reserve(cgp_ctx *c, int max_batch, int max_m) {
   if (!c || c->dtype != CGP_F64) return CGP_EINVAL;
   if (max_batch < 1 || max_batch > c->max_batch || max_m < 1 || max_m > c->max_m) return CGP_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipDeviceSynchronize());   // an earlier call may still use the scratch that goes
-  pgrad_free(c);
-  const size_t bytes = (size_t)max_batch * c->NTmax * TS * ((size_t)cdiv(max_m + 1, TS) * TS) * sizeof(double);
-  if (hipMalloc(&c->pgbuf, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    c->pgbuf = nullptr;
-    return CGP_ENOMEM;
-  }
-  c->pg_max_batch = max_batch;
-  c->pg_max_m = max_m;
-  return CGP_OK;
+  return scratch_reserve(c, c->pg, max_batch, max_m, (size_t)max_batch * c->NTmax * TS * ((size_t)cdiv(max_m + 1, TS) * TS) * sizeof(double));
 }
 
 extern "C" int cgp_fit_predict_grad_batch_device(cgp_ctx *c, int batch, int N, int d, int M, int kid, const double *dX, const double *dy,
@@ -107,12 +83,13 @@ extern "C" int cgp_fit_predict_grad_batch(cgp_ctx *c, int batch, int N, int d, i
   if ((rc = check_shape(c, batch, N, d, M, kid)) != CGP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t ng = (size_t)batch * M * d;
-  if (!grow_device(c->pg_dev, c->pg_dev_cap, 2 * ng * sizeof(double))) return CGP_ENOMEM;
-  double *ddmean = static_cast<double *>(c->pg_dev), *ddvar = ddmean + ng;
+  if (!grow_device(c->pg.stage, c->pg.stage_cap, 2 * ng * sizeof(double))) return CGP_ENOMEM;
+  double *ddmean = static_cast<double *>(c->pg.stage), *ddvar = ddmean + ng;
   const PgradCall pc{static_cast<const double *>(c->dX), static_cast<const double *>(c->dXs), c->dtheta, c->dinfo, dmean ? ddmean : nullptr,
                      dvar ? ddvar : nullptr};
-  const JointHook jh{nullptr, nullptr, &pc};
-  rc = fit_predict_batch_host(c, batch, N, d, M, kid, X, y, Xs, theta, theta_stride, include_noise, mean, var, logml, info, &jh);
+  const auto hook = [&](int slab, int slot, int nfit, hipStream_t s) { return pgrad_launch(c, pc, N, d, M, kid, slab, slot, nfit, s); };
+  const PostFit post = post_fit(hook);
+  rc = fit_predict_batch_host(c, batch, N, d, M, kid, X, y, Xs, theta, theta_stride, include_noise, mean, var, logml, info, &post);
   if (rc < 0) return rc;
   if (dmean) HIP_TRY(c, hipMemcpyAsync(dmean, ddmean, ng * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (dvar) HIP_TRY(c, hipMemcpyAsync(dvar, ddvar, ng * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -128,8 +105,8 @@ extern "C" int cgp_predict_gradients(cgp_ctx *c, const double *Xs, int M, double
   if ((rc = predict_enqueue(c, Xs, M, 0)) != CGP_OK) return rc;
   hipStream_t s = c->stream;
   const size_t ng = (size_t)M * c->fd;
-  if (!grow_device(c->pg_dev, c->pg_dev_cap, 2 * ng * sizeof(double))) return CGP_ENOMEM;
-  double *ddmean = static_cast<double *>(c->pg_dev), *ddvar = ddmean + ng;
+  if (!grow_device(c->pg.stage, c->pg.stage_cap, 2 * ng * sizeof(double))) return CGP_ENOMEM;
+  double *ddmean = static_cast<double *>(c->pg.stage), *ddvar = ddmean + ng;
   const PgradCall pc{static_cast<const double *>(c->dX), static_cast<const double *>(c->dXs), c->dtheta, nullptr, dmean ? ddmean : nullptr,
                      dvar ? ddvar : nullptr};
   if ((rc = pgrad_launch(c, pc, c->fN, c->fd, M, c->fkernel, 0, 0, 1, s)) != CGP_OK) return rc;

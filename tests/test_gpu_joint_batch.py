@@ -447,6 +447,9 @@ def test_argument_and_state_errors(engine):
 
     assert cov() == ESTATE and smp() == ESTATE and covd() == ESTATE and smpd() == ESTATE        # no reservation
     assert lib.cgp_predict_cov(ctx.h, p, 4, 1, p, p) == ESTATE and lib.cgp_sample(ctx.h, p, 4, 1, p, 0, 1e-6, p, ip) == ESTATE
+    # the order of the answers: no context and M = 0 before the missing reservation ...
+    calls = (cov, smp, covd, smpd)
+    assert all(f(h=None) == EINVAL and f(shape=(1, 9, 1, 0, 2)) == EINVAL for f in calls) and lib.cgp_joint_reserve(None, 1, 4) == EINVAL
     for mb, mm in ((0, 4), (3, 4), (1, 0), (1, 9)):
         assert lib.cgp_joint_reserve(ctx.h, mb, mm) == EINVAL
     assert lib.cgp_joint_reserve(ctx.h, 1, 4) == 0
@@ -454,6 +457,9 @@ def test_argument_and_state_errors(engine):
     big_m, big_b = (1, 8, 1, 5, 2), (2, 8, 1, 4, 2)
     for s in (big_m, big_b):
         assert cov(shape=s) == ECAPACITY and smp(shape=s) == ECAPACITY and covd(shape=s) == ECAPACITY and smpd(shape=s) == ECAPACITY
+    for s in ((2, 9, 1, 1, 2), (1, 9, 1, 5, 2)):                                                 # ... the capacity before the arrays
+        assert cov(shape=s, c=None) == ECAPACITY and smp(shape=s, S=0) == ECAPACITY
+        assert covd(shape=s, c=None) == ECAPACITY and smpd(shape=s, out=None) == ECAPACITY
     m0 = (1, 8, 1, 0, 2)
     assert cov(shape=m0) == EINVAL and smp(shape=m0) == EINVAL and covd(shape=m0) == EINVAL and smpd(shape=m0) == EINVAL
     assert cov(xs=None) == EINVAL and cov(mean=None) == EINVAL and cov(c=None) == EINVAL and covd(c=None) == EINVAL

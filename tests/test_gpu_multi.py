@@ -286,12 +286,18 @@ def test_argument_and_state_errors(engine):
         return lib.cgp_fit_predict_multi_batch_device(h, *shape, a, y, a, a, None, 1, mean, var, logml, info, None)
 
     assert host() == ESTATE and dev() == ESTATE                                   # no reservation
+    # the order of the answers: no context, M = 0 and P = 0 before the missing reservation ...
+    for f in (host, dev):
+        assert f(h=None) == EINVAL and f(shape=(1, 9, 1, 0, 1, 2)) == EINVAL and f(shape=(1, 9, 1, 1, 0, 2)) == EINVAL
+    assert lib.cgp_multi_reserve(None, 1, 2) == EINVAL
     for mb, mp in ((0, 2), (3, 2), (1, 0), (1, 4097)):
         assert lib.cgp_multi_reserve(ctx.h, mb, mp) == EINVAL
     assert host() == ESTATE
     assert lib.cgp_multi_reserve(ctx.h, 1, 2) == 0
     for s in ((1, 8, 1, 4, 3, 2), (2, 8, 1, 4, 2, 2)):                            # P, batch beyond the reservation
         assert host(shape=s) == ECAPACITY and dev(shape=s) == ECAPACITY
+    for s in ((2, 9, 1, 1, 1, 2), (1, 9, 1, 1, 3, 2), (2, 9, 1, 1, 1, 5)):        # ... the capacity before the arrays and the kernel id
+        assert host(shape=s, x=None) == ECAPACITY and host(shape=s, mean=None) == ECAPACITY and dev(shape=s, y=None) == ECAPACITY
     for s in ((1, 8, 1, 4, 0, 2), (1, 8, 1, 0, 2, 2)):                            # P = 0, M = 0
         assert host(shape=s) == EINVAL and dev(shape=s) == EINVAL
     assert host(x=None) == EINVAL and host(y=None) == EINVAL and host(xs=None) == EINVAL and host(th=None) == EINVAL

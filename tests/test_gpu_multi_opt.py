@@ -340,9 +340,12 @@ def test_argument_and_state_errors(engine):
 
     calls = (host, dev, opt)
     assert all(f() == ESTATE for f in calls)                                      # no reservation at all
+    # the order of the answers: no context and P = 0 before the missing reservation ...
+    assert all(f(h=None) == EINVAL and f(shape=(1, 9, 1, 0, 2)) == EINVAL for f in calls) and lib.cgp_multi_grad_reserve(None, 1, 2) == EINVAL
     assert lib.cgp_multi_grad_reserve(ctx.h, 1, 2) == ESTATE                      # needs cgp_multi_reserve first
     assert lib.cgp_multi_reserve(ctx.h, 1, 2) == 0
     assert all(f() == ESTATE for f in calls)                                      # ... and the A scratch
+    assert all(f(shape=(2, 9, 1, 1, 2)) == ESTATE for f in calls)                 # ... a missing reservation before a small one
     for mb, mp in ((0, 2), (3, 2), (1, 0), (1, 4097)):
         assert lib.cgp_multi_grad_reserve(ctx.h, mb, mp) == EINVAL
     assert lib.cgp_multi_grad_reserve(ctx.h, 2, 2) == ESTATE and lib.cgp_multi_grad_reserve(ctx.h, 1, 3) == ESTATE   # not covered
@@ -350,6 +353,8 @@ def test_argument_and_state_errors(engine):
     assert lib.cgp_multi_grad_reserve(ctx.h, 1, 2) == 0
     for s in ((1, 8, 1, 3, 2), (2, 8, 1, 2, 2)):                                  # P, batch beyond the reservation
         assert all(f(shape=s) == ECAPACITY for f in calls)
+    for s in ((2, 9, 1, 1, 2), (1, 9, 1, 3, 2), (2, 9, 1, 1, 5)):                 # ... the capacity before the arrays and the kernel id
+        assert all(f(shape=s, x=None) == ECAPACITY for f in calls)
     assert all(f(shape=(1, 8, 1, 0, 2)) == EINVAL for f in calls)                 # P = 0
     assert all(f(shape=(1, 8, 1, 2, 5)) == EINVAL for f in calls)                 # kernel id
     assert all(f(shape=(1, 17, 1, 2, 2)) == ECAPACITY for f in calls)             # N beyond the context

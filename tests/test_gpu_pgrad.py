@@ -314,6 +314,9 @@ def test_argument_and_state_errors(engine):
         return lib.cgp_predict_gradients(h, p, M, p, p, dm, dv)
 
     assert host() == ESTATE and dev() == ESTATE and single() == ESTATE        # no reservation
+    # the order of the answers: no context and M = 0 before the missing reservation ...
+    assert host(h=None) == EINVAL and dev(h=None) == EINVAL and single(h=None) == EINVAL and lib.cgp_pgrad_reserve(None, 1, 4) == EINVAL
+    assert host(shape=(1, 9, 1, 0, 2)) == EINVAL and dev(shape=(1, 9, 1, 0, 2)) == EINVAL and single(M=0) == EINVAL
     for mb, mm in ((0, 4), (3, 4), (1, 0), (1, 9)):
         assert lib.cgp_pgrad_reserve(ctx.h, mb, mm) == EINVAL
     assert lib.cgp_pgrad_reserve(ctx.h, 1, 4) == 0
@@ -321,6 +324,10 @@ def test_argument_and_state_errors(engine):
     for s in ((1, 8, 1, 5, 2), (2, 8, 1, 4, 2)):
         assert host(shape=s) == ECAPACITY and dev(shape=s) == ECAPACITY
     assert single(M=5) == ECAPACITY
+    for s in ((2, 9, 1, 1, 2), (1, 9, 1, 5, 2)):                               # ... the capacity before the arrays
+        assert host(shape=s, dm=None, dv=None) == ECAPACITY and host(shape=s, mean=None) == ECAPACITY
+        assert dev(shape=s, dm=None, dv=None) == ECAPACITY
+    assert single(M=5, dm=None, dv=None) == ECAPACITY
     m0 = (1, 8, 1, 0, 2)
     assert host(shape=m0) == EINVAL and dev(shape=m0) == EINVAL and single(M=0) == EINVAL
     assert host(dm=None, dv=None) == EINVAL and dev(dm=None, dv=None) == EINVAL and single(dm=None, dv=None) == EINVAL

@@ -12,6 +12,9 @@ in ulps, non-zero exit when any call differs.  Shapes are the smallest that reac
                M = 1, 17 (two tiles of one super-tile), 65 (an off-diagonal super-tile pair), 130 (three super-tiles, ragged);
                every kernel id; CGP_SMALL=off so that every N takes the tiled schedules; a device-form call of three fits whose
                middle one is indefinite
+  hooked calls the multi-target calls (N = 130, M = 17, P = 1 / 17 / 129, the solve's tile height free, 64 and 128) and the
+               predictive-gradient calls (N = 130, M = 1 / 65 / 130), host and device form, and cgp_predict_gradients: three
+               fits, one retried on the ladder's first rung (the host form runs its post-fit hook again) and one indefinite
   windows      capacity 33 and 64, d = 1 and 3, kernel ids 0, 2, 4: empty, after N / 2 ticks, after N + 5 ticks, and with one
                window failed by a theta of negative noise (a push feeds every window of the context, so no window can stay
                empty beside filled ones: the empty state is all three windows before the first push, which takes the same
@@ -84,6 +87,79 @@ def batch_calls(engine, out):
     res = [t.cpu().numpy() for t in (dm, dc, dp, dl, di, ds)]
     assert res[4][1] != 0 and res[4][0] == 0 and res[4][2] == 0 and np.all(np.isnan(res[1][1])) and np.all(np.isnan(res[2][1])), res[4]
     out["device form B3 N130 M65, fit 1 indefinite"] = flat(*res)
+    ctx.close()
+
+
+def hooked_calls(engine, out):
+    """The multi-target and predictive-gradient calls (the batch entry points with a post-fit hook besides the joint ones), host
+    and device form, on three fits of N = 130: fit 0 factors, fit 1 needs exactly the ladder's first rung (the host form retries
+    it once and runs the hook again for it alone), fit 2 stays indefinite on every rung.  tests/failure_oracle.py builds them."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import failure_oracle as fo
+    B, N, d, kid = 3, 130, 3, 1
+    shift = 3e-7
+    assert fo.rung_of(shift)[0] == 0
+    wins = [fo.lattice_window(kid, N, d, None, seed=1), fo.rung_window(kid, N, d, 70, seed=2, shift=shift)[:3],
+            fo.lattice_window(kid, N, d, 100, seed=3)]
+    X, y, theta = (np.stack([w[i] for w in wins]) for i in range(3))
+    th10 = np.zeros((B, 10))
+    th10[:, :theta.shape[1]] = theta
+
+    def dev(*arrays):
+        return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+    def zeros(shape, dtype=torch.float64):
+        return torch.zeros(shape, dtype=dtype, device="cuda")
+
+    def ladder_ok(info):   # host form: only the hopeless fit is left flagged
+        assert info[0] == 0 and info[1] == 0 and info[2] == 101, info
+
+    def noladder_ok(info):   # device form: no ladder, the jitter as given (none)
+        assert info[0] == 0 and info[1] != 0 and info[2] == 101, info
+
+    # multi-target: M = 17, P = 1 / 17 / 129, the engine's choice of the solve's tile height and both forced ones
+    M = 17
+    Xs = X[:, :M] + 0.25
+    ctx = engine.Context(max_n=N, max_m=N, max_d=d, max_batch=B)
+    assert ctx.multi_reserve(B, 129) == 0 and ctx.pgrad_reserve(B, N) == 0
+    for P in (1, 17, 129):
+        Y = np.stack([[fo._targets(N, 100 * b + p) for p in range(P)] for b in range(B)])
+        Y[:, 0] = y
+        dX, dY, dXs, dth = dev(X.transpose(0, 2, 1), Y, Xs.transpose(0, 2, 1), th10)
+        for form in (0, 64, 128):
+            assert ctx.multi_set_form(form) == 0
+            res = ctx.fit_predict_multi_batch(X, Y, Xs, theta, kid)
+            ladder_ok(res[4])
+            out[f"fit_predict_multi_batch P{P} form{form}"] = flat(*res)
+            dm, dv, dl, di = zeros((B, P, M)), zeros((B, M)), zeros((B, P)), zeros(B, torch.int32)
+            assert ctx.fit_predict_multi_batch_device(B, N, d, M, P, kid, dX.data_ptr(), dY.data_ptr(), dXs.data_ptr(), dth.data_ptr(), 0,
+                                                      True, dm.data_ptr(), dv.data_ptr(), dl.data_ptr(), di.data_ptr()) == 0
+            torch.cuda.synchronize()
+            res = [t.cpu().numpy() for t in (dm, dv, dl, di)]
+            noladder_ok(res[3])
+            out[f"fit_predict_multi_batch_device P{P} form{form}"] = flat(*res)
+    assert ctx.multi_set_form(0) == 0
+
+    # predictive gradients: M = 1 / 65 / 130
+    for M in (1, 65, 130):
+        Xs = X[:, :M] + 0.25
+        res = ctx.fit_predict_grad_batch(X, y, Xs, theta, kid)
+        ladder_ok(res[4])
+        out[f"fit_predict_grad_batch M{M}"] = flat(*res)
+        dX, dy, dXs, dth = dev(X.transpose(0, 2, 1), y, Xs.transpose(0, 2, 1), th10)
+        dm, dv, dl, di, dgm, dgv = zeros((B, M)), zeros((B, M)), zeros(B), zeros(B, torch.int32), zeros((B, M, d)), zeros((B, M, d))
+        assert ctx.fit_predict_grad_batch_device(B, N, d, M, kid, dX.data_ptr(), dy.data_ptr(), dXs.data_ptr(), dth.data_ptr(), 0, True,
+                                                 dm.data_ptr(), dv.data_ptr(), dl.data_ptr(), di.data_ptr(), dgm.data_ptr(),
+                                                 dgv.data_ptr()) == 0
+        torch.cuda.synchronize()
+        res = [t.cpu().numpy() for t in (dm, dv, dl, di, dgm, dgv)]
+        noladder_ok(res[3])
+        out[f"fit_predict_grad_batch_device M{M}"] = flat(*res)
+        for b in range(B):   # after a single fit: the ladder is cgp_fit's, the hopeless window leaves nothing to differentiate
+            rc, logml = ctx.fit(X[b], y[b], kid, theta[b])
+            assert (rc != 0) == (b == 2), (b, rc)
+            out[f"predict_gradients M{M} fit {b}"] = flat(rc, logml, *(ctx.predict_gradients(Xs[b]) if rc == 0 else ()))
     ctx.close()
 
 
@@ -163,6 +239,7 @@ def run(out_path):
     engine.load()
     out = {}
     batch_calls(engine, out)
+    hooked_calls(engine, out)
     window_calls(engine, out)
     np.savez(out_path, **out)
     print(f"{len(out)} calls saved to {out_path} (library {engine.LIB_PATH})")
