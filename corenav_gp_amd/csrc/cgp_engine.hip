@@ -9,6 +9,7 @@
 #include "cgp_window_adapt.hpp"
 #include "cgp_window_loo.hpp"
 #include "cgp_window_joint.hpp"
+#include "cgp_window_pgrad.hpp"
 #include "cgp_joint.hpp"
 #include "cgp_multi.hpp"
 #include "cgp_multi_grad.hpp"

@@ -30,6 +30,8 @@
 // Workgroups are numbered so that the chunks of a window run on the same XCD at the same time (blockIdx.x round-robins over
 // the eight XCDs): a window's factor is then fetched from HBM once and served to its other chunks by that XCD's L2.
 // Read-only on the windows: L, z, xw, yw and state are not written.
+// The kernel has two more forms of the same block step: KEEP also stores V for the joint forecast (cgp_window_joint.hpp), GRAD
+// goes on from V to the predictive gradients (cgp_window_pgrad.hpp: B = L^-T V in place, then the contraction with dk/dx*).
 #pragma once
 #include "cgp_window.hpp"
 
@@ -52,6 +54,9 @@ struct ForecastArgs {
   // KEEP form only (cgp_window_joint.hpp): V is also stored, [nwin][mt][NB * 16][16] (test-point tile, row, column of the tile)
   double *vkeep;
   int mt;                     // test-point tiles of 16 the store is sized for: ceil(M / 16)
+  // GRAD form only (cgp_window_pgrad.hpp): mean / var may each be null there
+  const double *alpha;        // [nwin][NB * 16] k_window_alpha's alpha = L^-T z
+  double *gdmean, *gdvar;     // [nwin][M][d] d mean / d x*, d var / d x*; either may be null
 };
 
 // Inverse of every 16 x 16 diagonal block of the windows' factors (blocks counted from the window's origin).  Rows past the
@@ -92,7 +97,16 @@ __global__ __launch_bounds__(64) void k_window_diag_inv(ForecastArgs p) {
 // NCT column tiles per workgroup (the waves of a tile split the sum over J WF_WAVES / NCT ways); VW = columns of a tile in use
 // KEEP: every finished V(I) block is also stored for the joint forecast (cgp_window_joint.hpp); the forms cgp_window_predict
 // launches are the KEEP = false ones
-template <int NCT, int VW, bool KEEP = false, bool MAT = false>   // MAT: the windows hold a Matern kernel (an instantiation of its own)
+// GRAD: the gradient form (cgp_window_pgrad.hpp, cgp_window_predict_gradients): the same solve, then the tail declared below
+// goes on from the chunk's finished V in LDS; p.mean / p.var may each be null.  The forms cgp_window_predict and the joint
+// forecast launch are the GRAD = false ones; the block step is written once for all of them.
+template <int NCT, int VW, bool MAT>
+__device__ __forceinline__ void window_grad_tail(const ForecastArgs &p, double *V, double *red, const double *L, const double *xw,
+                                                 const double *dinv, const double *pr, const double (&xq)[MAXD], int w, int col,
+                                                 bool colok, int n, int nb, double (&a)[WF_PREF][4]);
+__device__ __forceinline__ void window_grad_prior(const ForecastArgs &p, size_t oi, bool bad, double x0, const double *pr);
+
+template <int NCT, int VW, bool KEEP = false, bool MAT = false, bool GRAD = false>   // MAT: the windows hold a Matern kernel (an instantiation of its own)
 __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs p) {
   static_assert((NCT == 1 || NCT == 2) && (VW == 16 || VW == 8), "forms of the forecast kernel");
   constexpr int SPLIT = WF_WAVES / NCT, MC = NCT * VW;
@@ -125,8 +139,9 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
   if (bad != 0 || n <= 0) {   // a failed window answers NaN, an empty one with the prior
     if (jq == 0 && lq == 0 && colok) {
       const size_t oi = (size_t)w * M + col;
-      p.mean[oi] = bad != 0 ? __builtin_nan("") : 0.0;
-      p.var[oi] = bad != 0 ? __builtin_nan("") : kss + noise;
+      if (!GRAD || p.mean) p.mean[oi] = bad != 0 ? __builtin_nan("") : 0.0;
+      if (!GRAD || p.var) p.var[oi] = bad != 0 ? __builtin_nan("") : kss + noise;
+      if constexpr (GRAD) window_grad_prior(p, oi, bad != 0, xq[0], pr);
     }
     return;
   }
@@ -263,10 +278,11 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
       const size_t oi = (size_t)w * M + col;
       double pv = kss - sv2;
       pv = pv < 1e-15 ? 1e-15 : pv;
-      p.mean[oi] = svz;
-      p.var[oi] = pv + noise;
+      if (!GRAD || p.mean) p.mean[oi] = svz;
+      if (!GRAD || p.var) p.var[oi] = pv + noise;
     }
   }
+  if constexpr (GRAD) window_grad_tail<NCT, VW, MAT>(p, V, red, L, xw, dinv, pr, xq, w, col, colok, n, nb, a);
 }
 
 }  // namespace cgp

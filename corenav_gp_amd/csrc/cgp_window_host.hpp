@@ -1,5 +1,5 @@
 // cgp_window_host.hpp -- host layer of the sliding windows: the cgp_window_* entry points of include/corenav_gp.h.  The kernels
-// are in cgp_window.hpp (push), cgp_window_forecast.hpp, cgp_window_adapt.hpp and cgp_window_joint.hpp.  Not a translation unit
+// are in cgp_window.hpp (push), cgp_window_forecast.hpp, cgp_window_pgrad.hpp, cgp_window_adapt.hpp and cgp_window_joint.hpp.  Not a translation unit
 // of its own: cgp_engine.hip includes it after cgp_ctx and the helpers it uses (hip_ok / HIP_TRY, grow_pinned, grow_device,
 // pick_stream, cdiv, ntheta).
 #pragma once
@@ -135,6 +135,18 @@ inline ForecastForm forecast_form(int N, bool keep, bool matern) {
   return f;
 }
 
+// the gradient form of the forecast (cgp_window_pgrad.hpp): the forecast's forms (KEEP = false), chunk widths and LDS
+template <bool MAT> ForecastForm pgrad_win_form_of(int N) {
+  if (N <= kWinClassMaxN[0]) return {k_window_forecast<2, 16, false, MAT, true>, 32};
+  if (N <= kWinClassMaxN[1]) return {k_window_forecast<1, 16, false, MAT, true>, 16};
+  return {k_window_forecast<1, 8, false, MAT, true>, 8};
+}
+inline ForecastForm pgrad_win_form(int N, bool matern) {
+  ForecastForm f = matern ? pgrad_win_form_of<true>(N) : pgrad_win_form_of<false>(N);
+  f.lds = forecast_form(N, false, matern).lds;
+  return f;
+}
+
 // A kernel's view of the resident windows: the fields that do not depend on the call.
 ForecastArgs forecast_args(cgp_ctx *c) {
   const WindowArgs &wa = c->win;
@@ -238,6 +250,8 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
   for (int n : kWinClassMaxN)
     for (bool keep : {false, true})
       if (!lds_limit(forecast_form(n, keep, mat).kernel, kWinForecastLdsMax)) return CGP_EHIP;
+  for (int n : kWinClassMaxN)
+    if (!lds_limit(pgrad_win_form(n, mat).kernel, kWinForecastLdsMax)) return CGP_EHIP;
   // the old windows are gone from here on: a failure below must leave the context without windows,
   // not with stale pointers (cgp_window_push checks nwin)
   c->nwin = 0;
@@ -447,6 +461,61 @@ extern "C" int cgp_window_predict(cgp_ctx *c, int M, const double *xs, int inclu
   if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
   memcpy(mean, h + nx, ny * 8);
   memcpy(var, h + nx + ny, ny * 8);
+  return first_failing_tick(hst + 2, W, 4);
+}
+
+// ---- predictive gradients from the windows as they stand (cgp_window_pgrad.hpp) --------------------------------------
+// The forecast's launches with the gradient's alpha between them: diagonal inverses, alpha = L^-T z (cgp_window_nll_grad's
+// second launch, into its scratch), then the gradient form of the forecast kernel.
+extern "C" int cgp_window_predict_gradients_device(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean_out,
+                                                   double *dvar_out, double *ddmean, double *ddvar, void *hip_stream) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (M < 1 || !dxs || (!ddmean && !ddvar)) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  ForecastArgs a = forecast_args(c);
+  a.xs = dxs; a.mean = dmean_out; a.var = dvar_out;
+  a.M = M; a.include_noise = include_noise;
+  const AdaptArgs ad = adapt_args(c);
+  a.alpha = ad.alpha; a.gdmean = ddmean; a.gdvar = ddvar;
+  const ForecastForm form = pgrad_win_form(a.N, k_is_matern(a.kernel_id));   // by N alone, as the forecast's
+  a.nchunk = cdiv(M, form.mc);
+  const long long total = (long long)c->nwin * a.nchunk;
+  if (total > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
+  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
+  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, ad);
+  hipLaunchKernelGGL(form.kernel, dim3(grid), dim3(WF_THREADS), form.lds, ws, a);
+  if (!hip_ok(c, hipGetLastError(), "window gradient forecast launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_predict_gradients(cgp_ctx *c, int M, const double *xs, int include_noise, double *mean, double *var,
+                                            double *dmean, double *dvar) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (M < 1 || !xs || (!dmean && !dvar)) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // staged as cgp_window_predict: one pinned block [xs | mean var | dmean dvar | state] and its device twin
+  const size_t W = c->nwin, nx = W * M * c->win.d, ny = W * M;
+  const size_t ndbl = 3 * nx + 2 * ny, bytes = ndbl * 8 + W * 4 * sizeof(int);
+  double *h, *d;
+  if (!window_stage(c, bytes, ndbl * 8, h, d)) return CGP_ENOMEM;
+  int *hst = reinterpret_cast<int *>(h + ndbl);
+  memcpy(h, xs, nx * 8);
+  hipStream_t s = c->stream;
+  const bool inplace = bytes <= kWinZeroCopyBytes;
+  if (!inplace) HIP_TRY(c, hipMemcpyAsync(d, h, nx * 8, hipMemcpyHostToDevice, s));
+  double *io = inplace ? h : d;
+  const size_t om = nx, ov = nx + ny, odm = nx + 2 * ny, odv = 2 * nx + 2 * ny;
+  int rc = cgp_window_predict_gradients_device(c, M, io, include_noise, mean ? io + om : nullptr, var ? io + ov : nullptr,
+                                               dmean ? io + odm : nullptr, dvar ? io + odv : nullptr, s);
+  if (rc != CGP_OK) return rc;
+  if (!inplace) HIP_TRY(c, hipMemcpyAsync(h + nx, d + nx, (2 * ny + 2 * nx) * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
+  if (mean) memcpy(mean, h + om, ny * 8);
+  if (var) memcpy(var, h + ov, ny * 8);
+  if (dmean) memcpy(dmean, h + odm, nx * 8);
+  if (dvar) memcpy(dvar, h + odv, nx * 8);
   return first_failing_tick(hst + 2, W, 4);
 }
 

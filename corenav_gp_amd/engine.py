@@ -112,6 +112,8 @@ _SIGS = {
     "cgp_window_state": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _ip]),
     "cgp_window_predict": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp]),
     "cgp_window_predict_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    "cgp_window_predict_gradients": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
+    "cgp_window_predict_gradients_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cgp_window_joint_reserve": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_window_predict_cov": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp]),
     "cgp_window_predict_cov_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
@@ -629,6 +631,35 @@ class Context:
     def window_predict_device(self, M, dxs, include_noise, dmean, dvar, stream=0):
         return self._chk(self.lib.cgp_window_predict_device(self.h, M, dxs, int(include_noise), dmean, dvar,
                                                             ctypes.c_void_p(stream)))
+
+    def window_predict_gradients(self, xs, include_noise=True, check=True, want=("dmean", "dvar"), moments=("mean", "var")):
+        """m.predictive_gradients(Xnew) from the windows as they stand: xs (nwin, M, d) (or (M, d) for one window) ->
+        (mean, var, dmean, dvar): mean / var (nwin, M) as window_predict returns them, dmean / dvar (nwin, M, d) the
+        derivatives of the mean and of the unclipped latent variance with respect to the test inputs.  `want` names the
+        gradients and `moments` the moments to compute (the others come back as None; at least one gradient).  A window that
+        failed in an earlier push raises CgpError (check=False: returns (mean, var, dmean, dvar, code), that window's outputs
+        NaN)."""
+        nwin, d = self._win
+        xs = _d(xs).reshape(nwin, -1, d)
+        M = xs.shape[1]
+        mean = np.empty((nwin, M)) if "mean" in moments else None
+        var = np.empty((nwin, M)) if "var" in moments else None
+        dmean = np.empty((nwin, M, d)) if "dmean" in want else None
+        dvar = np.empty((nwin, M, d)) if "dvar" in want else None
+        opt = lambda a: _p(a) if a is not None else None
+        rc = self._chk(self.lib.cgp_window_predict_gradients(self.h, M, _p(xs), int(include_noise), opt(mean), opt(var),
+                                                             opt(dmean), opt(dvar)))
+        if not check:
+            return mean, var, dmean, dvar, rc
+        if rc > 0:
+            raise CgpError(rc)
+        return mean, var, dmean, dvar
+
+    def window_predict_gradients_device(self, M, dxs, include_noise, dmean, dvar, ddmean, ddvar, stream=0):
+        """Device pointers (ints; 0 / None = not wanted, for dmean / dvar -- the moments -- and for one of ddmean / ddvar)."""
+        return self._chk(self.lib.cgp_window_predict_gradients_device(self.h, M, dxs, int(include_noise), dmean or None,
+                                                                      dvar or None, ddmean or None, ddvar or None,
+                                                                      ctypes.c_void_p(stream)))
 
     def window_joint_reserve(self, max_m):
         """Scratch for joint forecasts (window_predict_cov / window_sample) of up to max_m test points per window; once

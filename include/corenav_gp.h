@@ -98,7 +98,8 @@ const char *cgp_last_error(const cgp_ctx *ctx);
  * and for cgp_window_joint_reserve, cgp_window_predict_cov, cgp_window_predict_cov_device, cgp_window_sample and
  * cgp_window_sample_device (the joint forecast: full posterior covariance and sample paths).  Revision 3 libraries built after the
  * Matern kernels were added accept CGP_KERNEL_MATERN32_ARD and CGP_KERNEL_MATERN52_ARD in fp64 contexts (values added only: an
- * earlier library answers CGP_EINVAL for them; probe with cgp_fit on a two-sample window). */
+ * earlier library answers CGP_EINVAL for them; probe with cgp_fit on a two-sample window).  cgp_window_predict_gradients and
+ * cgp_window_predict_gradients_device (predictive gradients from the resident windows): revision 3, symbols added only. */
 #define CGP_ABI_VERSION 3
 int cgp_abi_version(void);
 /* How the library was built: 0 for the shipped library.  CGP_BUILD_ABLATION (-DCGP_ABLATION): env
@@ -642,6 +643,37 @@ int cgp_window_predict(cgp_ctx *ctx, int M, const double *xs, int include_noise,
  * synchronisation (capturable into a hipGraph).  It cannot see a failed window: its NaN outputs and cgp_window_state do. */
 int cgp_window_predict_device(cgp_ctx *ctx, int M, const double *dxs, int include_noise, double *dmean, double *dvar,
                               void *hip_stream);
+/* Predictive gradients from the windows as they stand after the last push (m.predictive_gradients(Xnew) on a window that is
+ * maintained instead of refitted): xs (nwin, M, d) as for cgp_window_predict, mean / var (nwin, M), each may be NULL,
+ * dmean / dvar (nwin, M, d) row-major, either may be NULL, not both (CGP_EINVAL).  Formulas, kernel derivatives (all five
+ * kernel ids), the id-2 tie convention and sign(0) = 0 are those of the "predictive gradients" section above, with
+ * alpha = L^-T z and B = L^-T L^-1 K(X, xs) on the window's n samples:
+ *   dmean[m][q] =                     sum_i dk(x*_m, x_i)/dx*_q alpha_i
+ *   dvar [m][q] = dk(x*_m, x*_m)/dx*_q - 2 sum_i dk(x*_m, x_i)/dx*_q B[i][m]
+ * -- the gradient of the UNCLIPPED latent variance; include_noise only affects var.  mean / var, where passed, are bitwise
+ * what cgp_window_predict returns for the same arguments (the forward pass is the same code).  Always fp64, whatever the
+ * context's dtype; 2 n^2 M flops per window on the fp64 matrix cores (the forecast's forward substitution and its mirror
+ * image).  The windows are not modified (L, z, the samples and the state words are not written, the slabs' strict upper
+ * triangle is neither read nor written): a push after the call gives bitwise what it gives without it.  An empty window
+ * answers with the prior: mean 0, var k(xs_j, xs_j) (+ sigma_n^2), dmean 0, dvar = d k(x*, x*) / dx* (zero for ids 0, 1, 3, 4;
+ * sigma_r^2 sigma_b^2 sign(x*) for id 2); a window still filling works; a window that lost positive definiteness gets NaN in
+ * all of its outputs, the others are unaffected.  A window's outputs depend on its own state and on N (which selects the
+ * kernel form) only, never on its slot, on nwin or on its neighbours; no atomics, every sum runs in a fixed order; the host
+ * and the device form are bitwise equal.  No reservation call is needed.  Uses the scratch of the diagonal blocks' inverses
+ * (shared with cgp_window_predict) and the alpha scratch of cgp_window_nll_grad: it is not to run concurrently with
+ * cgp_window_predict, cgp_window_nll_grad, cgp_window_loo or the joint forecast on other streams of the same context.
+ * Returns CGP_ESTATE without windows, CGP_EINVAL for M < 1, a NULL xs or both gradients NULL, else 0 or, like
+ * cgp_window_predict, the 1-based tick at which a window failed.  Blocks until the outputs are in the caller's arrays. */
+int cgp_window_predict_gradients(cgp_ctx *ctx, int M, const double *xs, int include_noise,
+                                 double *mean, double *var, double *dmean, double *dvar);
+/* Device-resident variant: device pointers with the same NULL rules (dmean_out / dvar_out are the (nwin, M) mean and
+ * variance, ddmean / ddvar the (nwin, M, d) gradients); three launches enqueued on hip_stream (NULL = legacy default stream,
+ * CGP_STREAM_CTX = the context's own), without allocation or synchronisation (capturable into a hipGraph).  Nothing outside
+ * the documented extents is written, every documented element of a passed array is written, element alignment suffices.
+ * It cannot see a failed window: its NaN outputs and cgp_window_state do. */
+int cgp_window_predict_gradients_device(cgp_ctx *ctx, int M, const double *dxs, int include_noise,
+                                        double *dmean_out, double *dvar_out, double *ddmean, double *ddvar,
+                                        void *hip_stream);
 
 /* ---- hyper-parameters of the resident windows, replaced and re-estimated in place ----------------
  * The reference re-estimates its hyper-parameters on every window (gp_slip_node.py:36, m.optimize()); cgp_window_init fixes
