@@ -10,6 +10,7 @@
 #include "cgp_window_loo.hpp"
 #include "cgp_window_joint.hpp"
 #include "cgp_window_pgrad.hpp"
+#include "cgp_window_multi.hpp"
 #include "cgp_joint.hpp"
 #include "cgp_multi.hpp"
 #include "cgp_multi_grad.hpp"
@@ -142,6 +143,11 @@ struct cgp_ctx {
   // mean | variance [2][nwin][max_m], failure words [nwin]
   void *jointbuf[4] = {nullptr};
   int joint_max_m = 0;
+  // multi-target windows (cgp_window_multi_reserve): the target store [nwin][P][N], its tick counts [nwin] (ints), the Z scratch
+  // [nwin][ceil(P / 16)][NB * 16][16], and column 0 of a push gathered for the push kernels [nwin][win_multi_ticks]
+  void *wmbuf[4] = {nullptr};
+  int win_multi_p = 0;          // the reservation's P; 0 = none
+  size_t win_multi_ticks = 0;   // ticks per push the gather block holds
   // joint forecast after batch / single fits (cgp_joint_reserve): the posterior covariance or its factor [max_batch][(mt * 16)^2],
   // then the factorisations' failure words [max_batch]; staging of the host sampling calls [xi | out]
   Scratch fj;

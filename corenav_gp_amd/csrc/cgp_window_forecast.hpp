@@ -32,6 +32,8 @@
 // Read-only on the windows: L, z, xw, yw and state are not written.
 // The kernel has two more forms of the same block step: KEEP also stores V for the joint forecast (cgp_window_joint.hpp), GRAD
 // goes on from V to the predictive gradients (cgp_window_pgrad.hpp: B = L^-T V in place, then the contraction with dk/dx*).
+// The multi-target windows (cgp_window_multi.hpp) add two: WM_Z solves Z = L^-1 Y for the P target columns (the start tile comes
+// from the target store instead of K*), WM_MEAN is the forecast whose P mean rows are contracted from V and Z after the loop.
 #pragma once
 #include "cgp_window.hpp"
 
@@ -57,7 +59,14 @@ struct ForecastArgs {
   // GRAD form only (cgp_window_pgrad.hpp): mean / var may each be null there
   const double *alpha;        // [nwin][NB * 16] k_window_alpha's alpha = L^-T z
   double *gdmean, *gdvar;     // [nwin][M][d] d mean / d x*, d var / d x*; either may be null
+  // multi-target forms only (cgp_window_multi.hpp); in the WM_Z form M = P and the "test points" are the target columns
+  const double *ystore;       // [nwin][P][N] the targets of the last N ticks, tick t at index t mod N
+  const int *ycount;          // [nwin] ticks stored so far, mod N
+  double *zs;                 // [nwin][pt][NB * 16][16] Z = L^-1 Y in the B-operand order (target tile, row, column of the tile)
+  double *mlogml;             // [nwin][P] or null (WM_Z)
+  int P, pt;                  // targets, target tiles of 16: ceil(P / 16); WM_MEAN: mean is [nwin][P][M]
 };
+enum { WM_NONE = 0, WM_Z = 1, WM_MEAN = 2 };   // forms of k_window_forecast for the multi-target windows
 
 // Inverse of every 16 x 16 diagonal block of the windows' factors (blocks counted from the window's origin).  Rows past the
 // window are identity rows.  One 16-lane row per block, four blocks per workgroup.
@@ -105,8 +114,17 @@ __device__ __forceinline__ void window_grad_tail(const ForecastArgs &p, double *
                                                  const double *dinv, const double *pr, const double (&xq)[MAXD], int w, int col,
                                                  bool colok, int n, int nb, double (&a)[WF_PREF][4]);
 __device__ __forceinline__ void window_grad_prior(const ForecastArgs &p, size_t oi, bool bad, double x0, const double *pr);
+// MULTI: the two multi-target forms (cgp_window_multi.hpp): the pieces below are theirs, the block step is the kernel's own.
+// WM_Z has no test points: lane l15 of a tile is a target column, the start tile is read from the target store, every finished
+// block goes to the Z scratch, and the tail writes logml[p].  WM_MEAN leaves the mean to its tail; var is the kernel's own.
+template <int MULTI> __device__ __forceinline__ void window_multi_prior(const ForecastArgs &p, int w, int col, bool bad, double prior_var);
+__device__ __forceinline__ double window_multi_target(const ForecastArgs &p, int w, int col, int n, int row);
+__device__ __forceinline__ void window_multi_z_tail(const ForecastArgs &p, double *red, const double *L, int w, int col, bool writer,
+                                                    int n, double sv2);
+template <int NCT, int VW>
+__device__ __forceinline__ void window_multi_mean_tail(const ForecastArgs &p, const double *V, double *red, int w, int ch, int n, int nb);
 
-template <int NCT, int VW, bool KEEP = false, bool MAT = false, bool GRAD = false>   // MAT: the windows hold a Matern kernel (an instantiation of its own)
+template <int NCT, int VW, bool KEEP = false, bool MAT = false, bool GRAD = false, int MULTI = WM_NONE>   // MAT: the windows hold a Matern kernel (an instantiation of its own)
 __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs p) {
   static_assert((NCT == 1 || NCT == 2) && (VW == 16 || VW == 8), "forms of the forecast kernel");
   constexpr int SPLIT = WF_WAVES / NCT, MC = NCT * VW;
@@ -134,14 +152,18 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
   const bool colok = l15 < VW && col < M;
   double xq[MAXD];
 #pragma unroll
-  for (int q = 0; q < MAXD; ++q) xq[q] = (colok && q < d) ? p.xs[((size_t)w * M + col) * d + q] : 0.0;
+  for (int q = 0; q < MAXD; ++q) xq[q] = (MULTI != WM_Z && colok && q < d) ? p.xs[((size_t)w * M + col) * d + q] : 0.0;
   const double kss = (kid == K_RBF_BROWNIAN) ? pr[9] * pr[10] * fabs(xq[0]) : pr[9];
   if (bad != 0 || n <= 0) {   // a failed window answers NaN, an empty one with the prior
     if (jq == 0 && lq == 0 && colok) {
-      const size_t oi = (size_t)w * M + col;
-      if (!GRAD || p.mean) p.mean[oi] = bad != 0 ? __builtin_nan("") : 0.0;
-      if (!GRAD || p.var) p.var[oi] = bad != 0 ? __builtin_nan("") : kss + noise;
-      if constexpr (GRAD) window_grad_prior(p, oi, bad != 0, xq[0], pr);
+      if constexpr (MULTI != WM_NONE) {
+        window_multi_prior<MULTI>(p, w, col, bad != 0, kss + noise);
+      } else {
+        const size_t oi = (size_t)w * M + col;
+        if (!GRAD || p.mean) p.mean[oi] = bad != 0 ? __builtin_nan("") : 0.0;
+        if (!GRAD || p.var) p.var[oi] = bad != 0 ? __builtin_nan("") : kss + noise;
+        if constexpr (GRAD) window_grad_prior(p, oi, bad != 0, xq[0], pr);
+      }
     }
     return;
   }
@@ -176,6 +198,14 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
   for (int q = 0; q < MAXD; ++q) prr[q] = q < d ? pr[q] : 0.0;
   const double amp = pr[9], ampb = pr[10];
   auto load_x = [&](int I) {
+    if constexpr (MULTI == WM_Z) {   // the start tile itself: rows lq + 4 r of target column `col`
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = I * WPB + lq + 4 * r;
+        xr[r][0] = (colok && row < n) ? window_multi_target(p, w, col, n, row) : 0.0;
+      }
+      return;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = I * WPB + lq + 4 * r;
@@ -215,7 +245,10 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
     double di[4] = {0.0, 0.0, 0.0, 0.0};
     if (kwave) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] = I * WPB + lq + 4 * r < n ? cov(xr[r]) : 0.0;
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (MULTI == WM_Z) acc[r] = xr[r][0];
+        else acc[r] = I * WPB + lq + 4 * r < n ? cov(xr[r]) : 0.0;
+      }
     }
     if (jq == 0) {   // the tile's solver wave requests the diagonal block's inverse (used after the barrier)
 #pragma unroll
@@ -262,8 +295,14 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
           if ((VW == 16 || l15 < VW) && (gc >> 4) < p.mt)
             p.vkeep[(((size_t)w * p.mt + (gc >> 4)) * nrow + row) * WPB + (gc & 15)] = v[r];
         }
-        const double zr = row < n ? z[row] : 0.0;
-        svz = __builtin_fma(v[r], zr, svz);
+        if constexpr (MULTI == WM_Z) {   // the KEEP store's order, into the Z scratch
+          const int gc = ch * MC + ct * VW + l15;
+          if ((VW == 16 || l15 < VW) && (gc >> 4) < p.pt) p.zs[(((size_t)w * p.pt + (gc >> 4)) * nrow + row) * WPB + (gc & 15)] = v[r];
+        }
+        if constexpr (MULTI == WM_NONE) {
+          const double zr = row < n ? z[row] : 0.0;
+          svz = __builtin_fma(v[r], zr, svz);
+        }
         sv2 = __builtin_fma(v[r], v[r], sv2);
       }
     }
@@ -278,11 +317,13 @@ __global__ __launch_bounds__(WF_THREADS, 1) void k_window_forecast(ForecastArgs 
       const size_t oi = (size_t)w * M + col;
       double pv = kss - sv2;
       pv = pv < 1e-15 ? 1e-15 : pv;
-      if (!GRAD || p.mean) p.mean[oi] = svz;
-      if (!GRAD || p.var) p.var[oi] = pv + noise;
+      if (MULTI == WM_NONE && (!GRAD || p.mean)) p.mean[oi] = svz;
+      if (MULTI != WM_Z && (!GRAD || p.var)) p.var[oi] = pv + noise;
     }
   }
   if constexpr (GRAD) window_grad_tail<NCT, VW, MAT>(p, V, red, L, xw, dinv, pr, xq, w, col, colok, n, nb, a);
+  if constexpr (MULTI == WM_Z) window_multi_z_tail(p, red, L, w, col, jq == 0 && lq == 0 && colok, n, sv2);
+  if constexpr (MULTI == WM_MEAN) window_multi_mean_tail<NCT, VW>(p, V, red, w, ch, n, nb);
 }
 
 }  // namespace cgp

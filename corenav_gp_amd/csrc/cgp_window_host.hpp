@@ -1,5 +1,5 @@
 // cgp_window_host.hpp -- host layer of the sliding windows: the cgp_window_* entry points of include/corenav_gp.h.  The kernels
-// are in cgp_window.hpp (push), cgp_window_forecast.hpp, cgp_window_pgrad.hpp, cgp_window_adapt.hpp and cgp_window_joint.hpp.  Not a translation unit
+// are in cgp_window.hpp (push), cgp_window_forecast.hpp, cgp_window_pgrad.hpp, cgp_window_multi.hpp, cgp_window_adapt.hpp and cgp_window_joint.hpp.  Not a translation unit
 // of its own: cgp_engine.hip includes it after cgp_ctx and the helpers it uses (hip_ok / HIP_TRY, grow_pinned, grow_device,
 // pick_stream, cdiv, ntheta).
 #pragma once
@@ -147,6 +147,26 @@ inline ForecastForm pgrad_win_form(int N, bool matern) {
   return f;
 }
 
+// the multi-target forms (cgp_window_multi.hpp): the forecast's forms (KEEP = false), chunk widths and LDS.  z = true: Z = L^-1 Y
+// (k_window_multi_z: no covariance is evaluated, one instantiation serves every kernel id); else the forecast with P mean rows
+template <bool MAT> ForecastForm multi_win_form_of(int N) {
+  if (N <= kWinClassMaxN[0]) return {k_window_forecast<2, 16, false, MAT, false, WM_MEAN>, 32};
+  if (N <= kWinClassMaxN[1]) return {k_window_forecast<1, 16, false, MAT, false, WM_MEAN>, 16};
+  return {k_window_forecast<1, 8, false, MAT, false, WM_MEAN>, 8};
+}
+inline ForecastForm multi_win_form(int N, bool z, bool matern) {
+  ForecastForm f;
+  if (z) {
+    if (N <= kWinClassMaxN[0]) f = {k_window_multi_z<2, 16>, 32};
+    else if (N <= kWinClassMaxN[1]) f = {k_window_multi_z<1, 16>, 16};
+    else f = {k_window_multi_z<1, 8>, 8};
+  } else {
+    f = matern ? multi_win_form_of<true>(N) : multi_win_form_of<false>(N);
+  }
+  f.lds = forecast_form(N, false, matern).lds;
+  return f;
+}
+
 // A kernel's view of the resident windows: the fields that do not depend on the call.
 ForecastArgs forecast_args(cgp_ctx *c) {
   const WindowArgs &wa = c->win;
@@ -224,7 +244,12 @@ void window_free(cgp_ctx *c, bool joint_only) {   // (declared in cgp_engine.hip
       b = nullptr;
     }
   };
-  if (!joint_only) release(c->winbuf);
+  if (!joint_only) {   // the multi-target reservation was sized for these windows and their (empty) state
+    release(c->winbuf);
+    release(c->wmbuf);
+    c->win_multi_p = 0;
+    c->win_multi_ticks = 0;
+  }
   release(c->jointbuf);
   c->joint_max_m = 0;
 }
@@ -314,7 +339,7 @@ int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, in
 }
 extern "C" int cgp_window_push_device(cgp_ctx *c, int T, const double *dxs, const double *dys, int include_noise,
                                       double *dpm, double *dpv, double *dl, void *hip_stream) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (!c || c->nwin < 1 || c->win_multi_p > 0) return CGP_ESTATE;   // (a single-target push would leave the other columns behind)
   if (T < 1 || !dxs || !dys || !dpm || !dpv || !dl) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   return window_push_impl(c, T, dxs, dys, include_noise, dpm, dpv, dl, nullptr, pick_stream(c, hip_stream));
@@ -362,7 +387,7 @@ int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, in
 
 extern "C" int cgp_window_push(cgp_ctx *c, int T, const double *xs, const double *ys, int include_noise, double *pm,
                                double *pv, double *logml) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (!c || c->nwin < 1 || c->win_multi_p > 0) return CGP_ESTATE;
   if (T < 1 || !xs || !ys || !pm || !pv || !logml) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   // The per-tick host entry (configs[3] is "streamed per IMU tick": T = 1 is the common call): no allocation and no
@@ -516,6 +541,180 @@ extern "C" int cgp_window_predict_gradients(cgp_ctx *c, int M, const double *xs,
   if (var) memcpy(var, h + ov, ny * 8);
   if (dmean) memcpy(dmean, h + odm, nx * 8);
   if (dvar) memcpy(dvar, h + odv, nx * 8);
+  return first_failing_tick(hst + 2, W, 4);
+}
+
+// ---- multi-target windows: P target columns share the resident factor (cgp_window_multi.hpp) --------------------------
+namespace {
+// the checks the four multi-target calls start with, before anything is enqueued
+int window_multi_check(const cgp_ctx *c, int P, bool args_ok) {
+  if (!c) return CGP_ESTATE;
+  if (c->dtype != CGP_F64) return CGP_EINVAL;
+  if (c->nwin < 1 || c->win_multi_p < 1) return CGP_ESTATE;
+  if (P != c->win_multi_p || !args_ok) return CGP_EINVAL;
+  return CGP_OK;
+}
+}  // namespace
+
+extern "C" int cgp_window_multi_reserve(cgp_ctx *c, int P) {
+  if (!c) return CGP_ESTATE;
+  if (c->dtype != CGP_F64) return CGP_EINVAL;
+  if (c->nwin < 1) return CGP_ESTATE;
+  if (P < 1 || P > WM_MAX_P) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());   // earlier pushes have landed; an earlier reservation's buffers are idle
+  const size_t W = c->nwin;
+  {   // every window still empty: the store starts at tick 0 with the windows
+    std::vector<int> st(W * 4);
+    HIP_TRY(c, hipMemcpy(st.data(), c->win.state, st.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t w = 0; w < W; ++w)
+      if (st[w * 4 + 1] != 0 || st[w * 4 + 3] != 0) return CGP_ESTATE;
+  }
+  // every instantiation a multi-target launch can pick gets its LDS limit, here only (the _device entry points make no attribute call)
+  const int N = c->win.N;
+  const bool mat = k_is_matern(c->win.kernel_id);
+  for (int n : kWinClassMaxN)
+    for (bool z : {false, true})
+      if (hipFuncSetAttribute(reinterpret_cast<const void *>(multi_win_form(n, z, mat).kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              kWinForecastLdsMax) != hipSuccess)
+        return CGP_EHIP;
+  auto drop = [&]() {
+    for (void *&b : c->wmbuf) {
+      if (b) (void)hipFree(b);
+      b = nullptr;
+    }
+    c->win_multi_p = 0;
+    c->win_multi_ticks = 0;
+  };
+  drop();
+  const size_t pt = cdiv(P, WPB), nrow = (size_t)cdiv(N, WPB) * WPB, ticks = std::max(N, 256);
+  const size_t sizes[4] = {W * P * N * 8, W * sizeof(int), W * pt * nrow * WPB * 8, W * ticks * 8};
+  for (int i = 0; i < 4; ++i)
+    if (hipMalloc(&c->wmbuf[i], sizes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      c->wmbuf[i] = nullptr;
+      drop();
+      return CGP_ENOMEM;
+    }
+  // (the Z scratch starts as zeros: the columns past P of the last target tile are never written and stay so)
+  if (!hip_ok(c, hipMemset(c->wmbuf[0], 0, sizes[0]), "window target store memset") ||
+      !hip_ok(c, hipMemset(c->wmbuf[1], 0, sizes[1]), "window target count memset") ||
+      !hip_ok(c, hipMemset(c->wmbuf[2], 0, sizes[2]), "window Z scratch memset") ||
+      !hip_ok(c, hipDeviceSynchronize(), "window multi reserve synchronise")) {   // (cgp_window_init on why: the fills are ordered on the legacy stream only)
+    drop();
+    return CGP_EHIP;
+  }
+  c->win_multi_p = P;
+  c->win_multi_ticks = ticks;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_push_multi_device(cgp_ctx *c, int T, int P, const double *dxs, const double *dYs, int include_noise,
+                                            double *dpm, double *dpv, double *dl, void *hip_stream) {
+  int rc = window_multi_check(c, P, T >= 1 && dxs && dYs && dpm && dpv && dl);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  if ((size_t)T > c->win_multi_ticks) {   // a push longer than any before it: the gather block grows (an allocation; the free waits for the device)
+    void *nb = nullptr;
+    if (hipMalloc(&nb, (size_t)c->nwin * T * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      return CGP_ENOMEM;
+    }
+    (void)hipFree(c->wmbuf[3]);
+    c->wmbuf[3] = nb;
+    c->win_multi_ticks = T;
+  }
+  TargetStoreArgs s{};
+  s.Ys = dYs;
+  s.ystore = static_cast<double *>(c->wmbuf[0]);
+  s.ycount = static_cast<int *>(c->wmbuf[1]);
+  s.y0 = static_cast<double *>(c->wmbuf[3]);
+  s.N = c->win.N; s.P = P; s.T = T;
+  hipLaunchKernelGGL(k_window_targets_store, dim3(c->nwin), dim3(256), 0, ws, s);
+  return window_push_impl(c, T, dxs, s.y0, include_noise, dpm, dpv, dl, nullptr, ws);
+}
+
+extern "C" int cgp_window_push_multi(cgp_ctx *c, int T, int P, const double *xs, const double *Ys, int include_noise, double *pm,
+                                     double *pv, double *logml) {
+  int rc = window_multi_check(c, P, T >= 1 && xs && Ys && pm && pv && logml);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // staged like a large cgp_window_push: one pinned block [xs | Ys | pm pv logml | state] and its device twin, one H2D, two D2H
+  const size_t W = c->nwin, nx = W * T * c->win.d, ny = W * T, nY = ny * P;
+  const size_t ndbl = nx + nY + 3 * ny, bytes = ndbl * 8 + W * 4 * sizeof(int);
+  double *h, *d;
+  if (!window_stage(c, bytes, ndbl * 8, h, d)) return CGP_ENOMEM;
+  int *hst = reinterpret_cast<int *>(h + ndbl);
+  memcpy(h, xs, nx * 8);
+  memcpy(h + nx, Ys, nY * 8);
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(d, h, (nx + nY) * 8, hipMemcpyHostToDevice, s));
+  const size_t oo = nx + nY;
+  rc = cgp_window_push_multi_device(c, T, P, d, d + nx, include_noise, d + oo, d + oo + ny, d + oo + 2 * ny, s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h + oo, d + oo, 3 * ny * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
+  memcpy(pm, h + oo, ny * 8);
+  memcpy(pv, h + oo + ny, ny * 8);
+  memcpy(logml, h + oo + 2 * ny, ny * 8);
+  return first_failing_tick(hst + 2, W, 4);
+}
+
+// Three launches: the diagonal blocks' inverses, Z = L^-1 Y of the P columns into the scratch (with logml), the forecast whose
+// epilogue contracts V with Z.  Sized by the capacity N; origin, size and tick count are read on the device.
+extern "C" int cgp_window_predict_multi_device(cgp_ctx *c, int M, int P, const double *dxs, int include_noise, double *dmean,
+                                               double *dvar, double *dlogml, void *hip_stream) {
+  int rc = window_multi_check(c, P, M >= 1 && dxs && dmean && dvar);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  ForecastArgs a = forecast_args(c);
+  a.include_noise = include_noise;
+  a.ystore = static_cast<const double *>(c->wmbuf[0]);
+  a.ycount = static_cast<const int *>(c->wmbuf[1]);
+  a.zs = static_cast<double *>(c->wmbuf[2]);
+  a.P = P;
+  a.pt = cdiv(P, WPB);
+  const bool matern = k_is_matern(a.kernel_id);
+  const ForecastForm zf = multi_win_form(a.N, true, matern), mf = multi_win_form(a.N, false, matern);   // by N alone, as the forecast's
+  ForecastArgs za = a;   // the targets take the test points' place
+  za.M = P;
+  za.nchunk = cdiv(P, zf.mc);
+  za.mlogml = dlogml;
+  a.xs = dxs; a.mean = dmean; a.var = dvar;
+  a.M = M;
+  a.nchunk = cdiv(M, mf.mc);
+  const long long total = (long long)c->nwin * a.nchunk, ztotal = (long long)c->nwin * za.nchunk;
+  if (total > (1ll << 30) || ztotal > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
+  hipLaunchKernelGGL(zf.kernel, dim3((unsigned)(cdiv((int)ztotal, WF_XCDS) * WF_XCDS)), dim3(WF_THREADS), zf.lds, ws, za);
+  hipLaunchKernelGGL(mf.kernel, dim3((unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS)), dim3(WF_THREADS), mf.lds, ws, a);
+  if (!hip_ok(c, hipGetLastError(), "window multi-target forecast launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_predict_multi(cgp_ctx *c, int M, int P, const double *xs, int include_noise, double *mean, double *var,
+                                        double *logml) {
+  int rc = window_multi_check(c, P, M >= 1 && xs && mean && var);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one pinned block [xs | mean | var | logml | state] and its device twin: one H2D, one D2H of the outputs, the state words
+  const size_t W = c->nwin, nx = W * M * c->win.d, nm = W * P * M, nv = W * M, nl = W * P;
+  const size_t ndbl = nx + nm + nv + nl, bytes = ndbl * 8 + W * 4 * sizeof(int);
+  double *h, *d;
+  if (!window_stage(c, bytes, ndbl * 8, h, d)) return CGP_ENOMEM;
+  int *hst = reinterpret_cast<int *>(h + ndbl);
+  memcpy(h, xs, nx * 8);
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(d, h, nx * 8, hipMemcpyHostToDevice, s));
+  rc = cgp_window_predict_multi_device(c, M, P, d, include_noise, d + nx, d + nx + nm, logml ? d + nx + nm + nv : nullptr, s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h + nx, d + nx, (nm + nv + (logml ? nl : 0)) * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
+  memcpy(mean, h + nx, nm * 8);
+  memcpy(var, h + nx + nm, nv * 8);
+  if (logml) memcpy(logml, h + nx + nm + nv, nl * 8);
   return first_failing_tick(hst + 2, W, 4);
 }
 

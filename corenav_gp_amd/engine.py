@@ -114,6 +114,11 @@ _SIGS = {
     "cgp_window_predict_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "cgp_window_predict_gradients": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
     "cgp_window_predict_gradients_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "cgp_window_multi_reserve": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "cgp_window_push_multi": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
+    "cgp_window_push_multi_device": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "cgp_window_predict_multi": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp]),
+    "cgp_window_predict_multi_device": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "cgp_window_joint_reserve": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_window_predict_cov": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp]),
     "cgp_window_predict_cov_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
@@ -592,6 +597,7 @@ class Context:
         self._win = (nwin, d)
         self._win_nth = ntheta(kernel_id, d)
         self._win_n = N
+        self._win_p = 0   # (a multi-target reservation goes with the windows it was made for)
         self._chk(self.lib.cgp_window_init(self.h, nwin, N, d, kernel_id, _p(theta), theta.shape[1]))
 
     def window_push(self, xs, ys, include_noise=True, check=True):
@@ -660,6 +666,55 @@ class Context:
         return self._chk(self.lib.cgp_window_predict_gradients_device(self.h, M, dxs, int(include_noise), dmean or None,
                                                                       dvar or None, ddmean or None, ddvar or None,
                                                                       ctypes.c_void_p(stream)))
+
+    def window_multi_reserve(self, P):
+        """Multi-target windows: target store and Z scratch for P target columns per tick (1 <= P <= 64); once after
+        window_init, while the windows are empty.  From here on the windows are fed with window_push_multi."""
+        rc = self._chk(self.lib.cgp_window_multi_reserve(self.h, int(P)))
+        self._win_p = int(P)
+        return rc
+
+    def window_push_multi(self, xs, Ys, include_noise=True, check=True):
+        """xs (nwin, T, d), Ys (nwin, T, P) -> column 0's one-step-ahead mean, variance and logML per tick, each (nwin, T):
+        bitwise window_push's for that column.  Failure reporting as window_push."""
+        nwin, d = self._win
+        P = self._win_p
+        xs, Ys = _d(xs).reshape(nwin, -1, d), _d(Ys).reshape(nwin, -1, P)
+        T = Ys.shape[1]
+        pm, pv, lm = np.empty((nwin, T)), np.empty((nwin, T)), np.empty((nwin, T))
+        rc = self._chk(self.lib.cgp_window_push_multi(self.h, T, P, _p(xs), _p(Ys), int(include_noise), _p(pm), _p(pv), _p(lm)))
+        if not check:
+            return pm, pv, lm, rc
+        if rc > 0:
+            raise CgpError(rc)
+        return pm, pv, lm
+
+    def window_push_multi_device(self, T, P, dxs, dYs, include_noise, dpm, dpv, dlm, stream=0):
+        return self._chk(self.lib.cgp_window_push_multi_device(self.h, T, P, dxs, dYs, int(include_noise), dpm, dpv, dlm,
+                                                               ctypes.c_void_p(stream)))
+
+    def window_predict_multi(self, xs, include_noise=True, check=True, want_logml=True):
+        """Forecast of all P target columns from the windows as they stand: xs (nwin, M, d) -> mean (nwin, P, M), var
+        (nwin, M) (shared by the columns), logml (nwin, P) (None with want_logml=False).  A failed window raises CgpError
+        (check=False: returns (mean, var, logml, code), that window's outputs NaN)."""
+        nwin, d = self._win
+        P = self._win_p
+        xs = _d(xs).reshape(nwin, -1, d)
+        M = xs.shape[1]
+        mean, var = np.empty((nwin, P, M)), np.empty((nwin, M))
+        logml = np.empty((nwin, P)) if want_logml else None
+        rc = self._chk(self.lib.cgp_window_predict_multi(self.h, M, P, _p(xs), int(include_noise), _p(mean), _p(var),
+                                                         _p(logml) if want_logml else None))
+        if not check:
+            return mean, var, logml, rc
+        if rc > 0:
+            raise CgpError(rc)
+        return mean, var, logml
+
+    def window_predict_multi_device(self, M, P, dxs, include_noise, dmean, dvar, dlogml, stream=0):
+        """Device pointers (ints; dlogml 0 / None = not wanted)."""
+        return self._chk(self.lib.cgp_window_predict_multi_device(self.h, M, P, dxs, int(include_noise), dmean, dvar,
+                                                                  dlogml or None, ctypes.c_void_p(stream)))
 
     def window_joint_reserve(self, max_m):
         """Scratch for joint forecasts (window_predict_cov / window_sample) of up to max_m test points per window; once

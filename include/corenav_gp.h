@@ -99,7 +99,9 @@ const char *cgp_last_error(const cgp_ctx *ctx);
  * cgp_window_sample_device (the joint forecast: full posterior covariance and sample paths).  Revision 3 libraries built after the
  * Matern kernels were added accept CGP_KERNEL_MATERN32_ARD and CGP_KERNEL_MATERN52_ARD in fp64 contexts (values added only: an
  * earlier library answers CGP_EINVAL for them; probe with cgp_fit on a two-sample window).  cgp_window_predict_gradients and
- * cgp_window_predict_gradients_device (predictive gradients from the resident windows): revision 3, symbols added only. */
+ * cgp_window_predict_gradients_device (predictive gradients from the resident windows): revision 3, symbols added only.
+ * cgp_window_multi_reserve, cgp_window_push_multi, cgp_window_push_multi_device, cgp_window_predict_multi and
+ * cgp_window_predict_multi_device (multi-target sliding windows): revision 3, symbols added only. */
 #define CGP_ABI_VERSION 3
 int cgp_abi_version(void);
 /* How the library was built: 0 for the shipped library.  CGP_BUILD_ABLATION (-DCGP_ABLATION): env
@@ -430,8 +432,8 @@ int cgp_predict_gradients(cgp_ctx *ctx, const double *Xs, int M, double *mean, d
  * a lone fit of N = 2048, M = 599, replicating X through cgp_fit_predict_batch_device is as fast or faster (measured: P = 8 0.79 x,
  * P = 16 1.23 x, P = 512 17 x the replicate route; 64 fits x P = 8: 5.2 x; DESIGN.md section 9d has the table).
  *
- * Not provided: multi-target leave-one-out or joint covariance, multi-target sliding windows, and a cgp_sweep_* form.  (The
- * hyper-parameters of a multi-target model: the next section.) */
+ * Not provided: multi-target leave-one-out or joint covariance, and a cgp_sweep_* form.  (The hyper-parameters of a
+ * multi-target model: the next section; multi-target sliding windows: the section after cgp_window_predict_gradients.) */
 int cgp_multi_reserve(cgp_ctx *ctx, int max_batch, int max_p);
 /* cgp_fit_predict_multi_batch: blocks; GPy's jitter ladder per fit exactly as cgp_fit_predict_batch runs it (a failed fit is
  * retried as a call of one fit; its targets are solved and contracted right after its retry, the whole batch's before the first
@@ -674,6 +676,74 @@ int cgp_window_predict_gradients(cgp_ctx *ctx, int M, const double *xs, int incl
 int cgp_window_predict_gradients_device(cgp_ctx *ctx, int M, const double *dxs, int include_noise,
                                         double *dmean_out, double *dvar_out, double *ddmean, double *ddvar,
                                         void *hip_stream);
+
+/* ---- multi-target sliding windows: P target columns share a window's resident factor -----------------
+ * The window form of the multi-target fits above: every tick brings P targets on the same inputs (the four wheels' slip and
+ * whatever else is sampled on the same time axis), and a forecast answers with P mean rows, ONE variance and P log marginal
+ * likelihoods from the ONE resident factor -- instead of P copies of every window, P rank-1 updates per tick and P forecast
+ * solves.  Formulas (those of the multi-target section), on the window's n samples, Y (n x P) its targets:
+ *   Z = L^-1 Y          V = L^-1 K(X, xs)
+ *   mean[p, m] = sum_i V[i, m] Z[i, p]
+ *   var[m]     = max(k(xs_m, xs_m) - sum_i V[i, m]^2, 1e-15) (+ sigma_n^2 when include_noise)
+ *   logml[p]   = -1/2 sum_i Z[i, p]^2 - sum_i log L_ii - n/2 log 2 pi        (sum_i log L_ii read from the diagonal in a fixed order)
+ * CGP_F64 contexts only: every entry point of this section returns CGP_EINVAL in a CGP_F32 context before anything is enqueued.
+ * All five kernel ids.
+ *
+ * How it is kept.  Column 0 goes through the push kernels exactly as cgp_window_push feeds them: the per-tick outputs of a
+ * multi-target push (one-step-ahead mean / variance, logML) describe COLUMN 0 ONLY and are bitwise what cgp_window_push gives for
+ * that column.  All P columns (column 0 included) are also written to a per-window target store, a circular buffer of the last N
+ * ticks; Z is formed from it and the factor AS IT STANDS whenever a forecast asks.  So after cgp_window_set_theta or
+ * cgp_window_optimize the next multi-target forecast is right for every column with no further call, and a failed window that
+ * cgp_window_set_theta revives answers for every column, the samples pushed while it was failed included.
+ *
+ * cgp_window_multi_reserve: once after cgp_window_init, while every window is still empty (CGP_ESTATE otherwise, and without
+ * windows): the target store, nwin x P x N doubles, the scratch for Z, nwin x ceil(P / 16) x (N rounded up to 16) x 16 doubles,
+ * and a block for column 0 of a push.  1 <= P <= 64, else CGP_EINVAL.  CGP_ENOMEM leaves no reservation; calling it again (windows
+ * still empty) replaces the reservation; cgp_window_init and cgp_destroy drop it.  Blocks (it synchronises the device).
+ * While a reservation exists cgp_window_push and cgp_window_push_device return CGP_ESTATE: a single-target push would leave the
+ * other columns behind.
+ *
+ * cgp_window_push_multi: xs (nwin, T, d), Ys (nwin, T, P) -- a tick's P targets contiguous -- outputs (nwin, T) for column 0.  P
+ * must equal the reservation's (CGP_EINVAL).  Return value and failure semantics are cgp_window_push's.  Blocks.
+ *
+ * cgp_window_predict_multi: xs (nwin, M, d), mean (nwin, P, M), var (nwin, M) (shared by the P targets), logml (nwin, P) or NULL.
+ * An empty window answers with the prior: mean 0, var k(xs_m, xs_m) (+ sigma_n^2), logml 0.  A window that lost positive
+ * definiteness has NaN in all P mean rows, in var and in its P logml entries; its neighbours are unaffected.  Read-only on the
+ * windows (L, z, the samples and the state words are not written): a push after a forecast is bitwise the push without it, and
+ * two forecasts in a row are identical (the scratch carries no state).  Returns CGP_ESTATE without windows or without a
+ * reservation, CGP_EINVAL for a P that is not the reservation's, M < 1 or a NULL required pointer, else 0 or, like
+ * cgp_window_predict, the 1-based tick at which a window failed.  Blocks.
+ *
+ * Determinism.  var is bitwise cgp_window_predict's var for the same arguments (the same code, the same arithmetic).  A column's
+ * mean row and logml are a function of its own targets, of the window and of N (which selects the kernel form): never of its
+ * position p, of P, of the other columns, of the window's slot or of its neighbours.  Permuting the columns permutes the outputs
+ * bitwise.  No atomics; every sum runs in a fixed order over the window's real n samples.  Column 0's mean row agrees with
+ * cgp_window_predict's mean to rounding, not bitwise: the resident z is updated incrementally, Z is a fresh solve.
+ *
+ * The other window calls on a multi-target context -- cgp_window_predict, cgp_window_predict_gradients, cgp_window_predict_cov,
+ * cgp_window_sample, cgp_window_loo, cgp_window_nll_grad and cgp_window_optimize -- keep working and speak of COLUMN 0.
+ * Not provided: a multi-target window optimiser (the summed objective of the P columns), multi-target joint forecast /
+ * leave-one-out / predictive gradients, and one-step-ahead outputs for the columns >= 1.
+ * Cost of a forecast: the forecast's n^2 M flops, n^2 P for Z and 2 n M P for the mean rows, per window, on the fp64 matrix
+ * cores.  Shares the scratch of the diagonal blocks' inverses with cgp_window_predict: not to run concurrently with the other
+ * window forecasts on other streams of the same context. */
+int cgp_window_multi_reserve(cgp_ctx *ctx, int P);
+int cgp_window_push_multi(cgp_ctx *ctx, int T, int P, const double *xs, const double *Ys, int include_noise,
+                          double *pred_mean, double *pred_var, double *logml);
+/* Device-resident variant: device pointers, enqueued on hip_stream (NULL = legacy default stream, CGP_STREAM_CTX = the context's
+ * own) without synchronising: one small launch that stores the targets, then cgp_window_push_device's launches.  The block that
+ * holds column 0 is sized for pushes of up to max(N, 256) ticks; a longer push than any before it grows it first (an allocation,
+ * not capturable).  The extent contract at cgp_fit_predict_batch_device applies. */
+int cgp_window_push_multi_device(cgp_ctx *ctx, int T, int P, const double *dxs, const double *dYs, int include_noise,
+                                 double *dpred_mean, double *dpred_var, double *dlogml, void *hip_stream);
+int cgp_window_predict_multi(cgp_ctx *ctx, int M, int P, const double *xs, int include_noise,
+                             double *mean, double *var, double *logml);
+/* Device-resident variant: device pointers (dlogml may be NULL); three launches enqueued on hip_stream, without allocation,
+ * attribute call or synchronisation (capturable into a hipGraph, like cgp_window_predict_device).  Nothing outside the documented
+ * extents is written, every documented element is written, element alignment suffices.  It cannot see a failed window: its NaN
+ * outputs and cgp_window_state do. */
+int cgp_window_predict_multi_device(cgp_ctx *ctx, int M, int P, const double *dxs, int include_noise,
+                                    double *dmean, double *dvar, double *dlogml, void *hip_stream);
 
 /* ---- hyper-parameters of the resident windows, replaced and re-estimated in place ----------------
  * The reference re-estimates its hyper-parameters on every window (gp_slip_node.py:36, m.optimize()); cgp_window_init fixes
