@@ -11,6 +11,7 @@
 #include "cgp_window_joint.hpp"
 #include "cgp_window_pgrad.hpp"
 #include "cgp_window_multi.hpp"
+#include "cgp_window_multi_grad.hpp"
 #include "cgp_joint.hpp"
 #include "cgp_multi.hpp"
 #include "cgp_multi_grad.hpp"
@@ -148,6 +149,9 @@ struct cgp_ctx {
   void *wmbuf[4] = {nullptr};
   int win_multi_p = 0;          // the reservation's P; 0 = none
   size_t win_multi_ticks = 0;   // ticks per push the gather block holds
+  // multi-target window objective (cgp_window_multi_grad_reserve): the A scratch [nwin][ceil(P / 16)][NB * 16][16] and the
+  // per-column values [nwin][P] a call without a logml buffer writes; both null = no reservation
+  void *wgbuf[2] = {nullptr};
   // joint forecast after batch / single fits (cgp_joint_reserve): the posterior covariance or its factor [max_batch][(mt * 16)^2],
   // then the factorisations' failure words [max_batch]; staging of the host sampling calls [xi | out]
   Scratch fj;

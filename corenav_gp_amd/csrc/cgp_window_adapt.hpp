@@ -61,6 +61,11 @@ struct AdaptArgs {
   double *nll, *grad;         // outputs: [nwin], [nwin][grad_stride]
   int grad_stride;
   int N, CAP, d, kernel_id, nwin, NB;
+  // multi-target objective (cgp_window_multi_grad.hpp)
+  const double *zs;           // [nwin][pt][NB * 16][16] k_window_multi_z's Z = L^-1 Y
+  double *am;                 // [nwin][pt][NB * 16][16] A = L^-T Z, the same tile order
+  const double *mlogml;       // [nwin][P] k_window_multi_z's per-column values
+  int P, pt;                  // targets, target tiles of 16
 };
 
 typedef double d4 __attribute__((ext_vector_type(4)));   // one lane's share of a 16 x 16 fp64 MFMA tile

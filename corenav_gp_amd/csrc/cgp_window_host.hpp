@@ -1,5 +1,5 @@
 // cgp_window_host.hpp -- host layer of the sliding windows: the cgp_window_* entry points of include/corenav_gp.h.  The kernels
-// are in cgp_window.hpp (push), cgp_window_forecast.hpp, cgp_window_pgrad.hpp, cgp_window_multi.hpp, cgp_window_adapt.hpp and cgp_window_joint.hpp.  Not a translation unit
+// are in cgp_window.hpp (push), cgp_window_forecast.hpp, cgp_window_pgrad.hpp, cgp_window_multi.hpp, cgp_window_multi_grad.hpp, cgp_window_adapt.hpp and cgp_window_joint.hpp.  Not a translation unit
 // of its own: cgp_engine.hip includes it after cgp_ctx and the helpers it uses (hip_ok / HIP_TRY, grow_pinned, grow_device,
 // pick_stream, cdiv, ntheta).
 #pragma once
@@ -201,6 +201,11 @@ AdaptArgs adapt_args(cgp_ctx *c) {
   a.alpha = sc;
   a.gpart = sc + (size_t)c->nwin * a.NB * WPB;
   a.nllv = a.gpart + (size_t)c->nwin * a.NB * GRAD_N;
+  // the multi-target objective (null / 0 without its reservations)
+  a.zs = static_cast<const double *>(c->wmbuf[2]);
+  a.am = static_cast<double *>(c->wgbuf[0]);
+  a.P = c->win_multi_p;
+  a.pt = cdiv(c->win_multi_p, WPB);
   return a;
 }
 
@@ -247,6 +252,7 @@ void window_free(cgp_ctx *c, bool joint_only) {   // (declared in cgp_engine.hip
   if (!joint_only) {   // the multi-target reservation was sized for these windows and their (empty) state
     release(c->winbuf);
     release(c->wmbuf);
+    release(c->wgbuf);   // (the objective's scratch was sized for the reservation's P)
     c->win_multi_p = 0;
     c->win_multi_ticks = 0;
   }
@@ -580,6 +586,10 @@ extern "C" int cgp_window_multi_reserve(cgp_ctx *c, int P) {
         return CGP_EHIP;
   auto drop = [&]() {
     for (void *&b : c->wmbuf) {
+      if (b) (void)hipFree(b);
+      b = nullptr;
+    }
+    for (void *&b : c->wgbuf) {   // cgp_window_multi_grad_reserve's scratch was sized for the reservation that goes
       if (b) (void)hipFree(b);
       b = nullptr;
     }
@@ -1010,9 +1020,12 @@ extern "C" int cgp_window_loo(cgp_ctx *c, double *loo_mean, double *loo_var, dou
 
 // m.optimize() on the resident windows: the batched L-BFGS driver of cgp_optimize_batch (one batched evaluation per round, every
 // window its own stepper and line search) with set_theta + nll_grad on the windows themselves as the evaluation.
-extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
-                                   double *logml_out, int *n_evals) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
+// The loop is written once: `eval(dnll, dgrad, grad_stride, stream)` enqueues the evaluation of every window where it stands --
+// cgp_window_nll_grad_device (cgp_window_optimize) or the summed objective of the P columns (cgp_window_optimize_multi).
+namespace {
+template <class Eval>
+int window_optimize_impl(cgp_ctx *c, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
+                         double *logml_out, int *n_evals, Eval &&eval) {
   const int nth = ntheta(c->win.kernel_id, c->win.d);
   if (theta_out && theta_stride < nth) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1045,7 +1058,7 @@ extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned cha
     for (size_t w = 0; w < W; ++w) hsel[w] = active[w] ? 1 : 0;
     int rc = set_theta();
     if (rc != CGP_OK) return rc;
-    rc = cgp_window_nll_grad_device(c, d + o_nll, d + o_grad, nth, s);
+    rc = eval(d + o_nll, d + o_grad, nth, s);
     if (rc != CGP_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(hnll, d + o_nll, (2 * W + nt + ni) * 8, hipMemcpyDeviceToHost, s));   // nll | grad | logml | info
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -1076,4 +1089,121 @@ extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned cha
     if (n_evals) n_evals[w] = res.evals[w];
   }
   return CGP_OK;
+}
+}  // namespace
+
+extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
+                                   double *logml_out, int *n_evals) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  return window_optimize_impl(c, max_evals, select, theta_out, theta_stride, logml_out, n_evals,
+                              [&](double *dnll, double *dgrad, int stride, hipStream_t s) {
+                                return cgp_window_nll_grad_device(c, dnll, dgrad, stride, s);
+                              });
+}
+
+// ---- multi-target windows: value, gradient and optimiser of the P columns' summed logML (cgp_window_multi_grad.hpp) ----
+namespace {
+// the checks the multi-target objective's calls start with, before anything is enqueued
+int window_multi_grad_check(const cgp_ctx *c, int P, bool args_ok) {
+  if (!c) return CGP_ESTATE;
+  if (c->dtype != CGP_F64) return CGP_EINVAL;
+  if (c->nwin < 1 || c->win_multi_p < 1 || !c->wgbuf[0] || !c->wgbuf[1]) return CGP_ESTATE;
+  if (P != c->win_multi_p || !args_ok) return CGP_EINVAL;
+  return CGP_OK;
+}
+}  // namespace
+
+extern "C" int cgp_window_multi_grad_reserve(cgp_ctx *c) {
+  if (!c) return CGP_ESTATE;
+  if (c->dtype != CGP_F64) return CGP_EINVAL;
+  if (c->nwin < 1 || c->win_multi_p < 1) return CGP_ESTATE;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());   // an earlier reservation's buffers are idle
+  auto drop = [&]() {
+    for (void *&b : c->wgbuf) {
+      if (b) (void)hipFree(b);
+      b = nullptr;
+    }
+  };
+  drop();
+  const size_t W = c->nwin, P = c->win_multi_p, pt = cdiv(c->win_multi_p, WPB), nrow = (size_t)cdiv(c->win.N, WPB) * WPB;
+  const size_t sizes[2] = {W * pt * nrow * WPB * 8, W * P * 8};
+  for (int i = 0; i < 2; ++i)
+    if (hipMalloc(&c->wgbuf[i], sizes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      c->wgbuf[i] = nullptr;
+      drop();
+      return CGP_ENOMEM;
+    }
+  if (!hip_ok(c, hipMemset(c->wgbuf[0], 0, sizes[0]), "window A scratch memset") ||
+      !hip_ok(c, hipMemset(c->wgbuf[1], 0, sizes[1]), "window column values memset") ||
+      !hip_ok(c, hipDeviceSynchronize(), "window multi grad reserve synchronise")) {   // (cgp_window_init on why)
+    drop();
+    return CGP_EHIP;
+  }
+  return CGP_OK;
+}
+
+// Five launches: the diagonal blocks' inverses, Z = L^-1 Y with the columns' logml (cgp_window_predict_multi's second launch), A =
+// L^-T Z, the contraction with dK/dtheta, the finish.  Sized by the capacity N; origin, size and tick count are read on the device.
+extern "C" int cgp_window_multi_nll_grad_device(cgp_ctx *c, int P, double *dnll, double *dgrad, int grad_stride, double *dlogml,
+                                                void *hip_stream) {
+  int rc = window_multi_grad_check(c, P, c && dnll && dgrad && grad_stride >= ntheta(c->win.kernel_id, c->win.d));
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  AdaptArgs a = adapt_args(c);
+  a.nll = dnll; a.grad = dgrad; a.grad_stride = grad_stride;
+  double *lm = dlogml ? dlogml : static_cast<double *>(c->wgbuf[1]);   // the value is read from it by the finish
+  a.mlogml = lm;
+  ForecastArgs za = forecast_args(c);   // the targets take the test points' place (cgp_window_predict_multi_device)
+  za.ystore = static_cast<const double *>(c->wmbuf[0]);
+  za.ycount = static_cast<const int *>(c->wmbuf[1]);
+  za.zs = static_cast<double *>(c->wmbuf[2]);
+  za.P = P;
+  za.pt = a.pt;
+  const ForecastForm zf = multi_win_form(a.N, true, k_is_matern(a.kernel_id));   // by N alone
+  za.M = P;
+  za.nchunk = cdiv(P, zf.mc);
+  za.mlogml = lm;
+  const long long chunks = (long long)c->nwin * a.NB, ztotal = (long long)c->nwin * za.nchunk, tiles = (long long)c->nwin * a.pt;
+  if (chunks > (1ll << 30) || ztotal > (1ll << 30) || tiles > (1ll << 30)) return CGP_EINVAL;
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, za);
+  hipLaunchKernelGGL(zf.kernel, dim3((unsigned)(cdiv((int)ztotal, WF_XCDS) * WF_XCDS)), dim3(WF_THREADS), zf.lds, ws, za);
+  hipLaunchKernelGGL(k_window_multi_alpha, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, ws, a);
+  hipLaunchKernelGGL(k_window_multi_kinv_grad, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a);
+  hipLaunchKernelGGL(k_window_multi_grad_finish, dim3((unsigned)cdiv(c->nwin, 64)), dim3(64), 0, ws, a);
+  if (!hip_ok(c, hipGetLastError(), "window multi-target gradient launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_multi_nll_grad(cgp_ctx *c, int P, double *nll, double *grad, int grad_stride, double *logml) {
+  int rc = window_multi_grad_check(c, P, c && nll && grad && grad_stride >= ntheta(c->win.kernel_id, c->win.d));
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one device block [nll | grad | logml] and its pinned twin: the launches, one D2H, one synchronisation
+  const int nth = ntheta(c->win.kernel_id, c->win.d);
+  const size_t W = c->nwin, nl = logml ? W * P : 0, ndbl = W * (1 + nth) + nl;
+  double *h, *d;
+  if (!window_stage(c, ndbl * 8, ndbl * 8, h, d)) return CGP_ENOMEM;
+  hipStream_t s = c->stream;
+  rc = cgp_window_multi_nll_grad_device(c, P, d, d + W, nth, logml ? d + W * (1 + nth) : nullptr, s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h, d, ndbl * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  memcpy(nll, h, W * sizeof(double));
+  for (size_t w = 0; w < W; ++w) memcpy(grad + w * grad_stride, h + W + w * nth, nth * sizeof(double));
+  if (logml) memcpy(logml, h + W * (1 + nth), nl * sizeof(double));
+  return CGP_OK;
+}
+
+// cgp_window_optimize with the summed objective: the same driver and the same round, the evaluation above in cgp_window_nll_grad_device's place.
+extern "C" int cgp_window_optimize_multi(cgp_ctx *c, int P, int max_evals, const unsigned char *select, double *theta_out,
+                                         int theta_stride, double *logml_sum_out, int *n_evals) {
+  int rc = window_multi_grad_check(c, P, true);
+  if (rc != CGP_OK) return rc;
+  return window_optimize_impl(c, max_evals, select, theta_out, theta_stride, logml_sum_out, n_evals,
+                              [&](double *dnll, double *dgrad, int stride, hipStream_t s) {
+                                return cgp_window_multi_nll_grad_device(c, P, dnll, dgrad, stride, nullptr, s);
+                              });
 }

@@ -132,6 +132,10 @@ _SIGS = {
     "cgp_window_loo": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "cgp_window_loo_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cgp_window_optimize": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, ctypes.c_int, _dp, _ip]),
+    "cgp_window_multi_grad_reserve": (ctypes.c_int, [_vp]),
+    "cgp_window_multi_nll_grad": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp]),
+    "cgp_window_multi_nll_grad_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "cgp_window_optimize_multi": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _dp, ctypes.c_int, _dp, _ip]),
     "cgp_set_streams": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_set_refine": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_debug_read": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong)]),
@@ -822,6 +826,39 @@ class Context:
         sel, selp = self._select(select)
         theta, logml, nev = np.full((nwin, stride), np.nan), np.full(nwin, np.nan), np.zeros(nwin, dtype=np.int32)
         self._chk(self.lib.cgp_window_optimize(self.h, max_evals, selp, _p(theta), stride, _p(logml), nev.ctypes.data_as(_ip)))
+        return theta, logml, nev
+
+    def window_multi_grad_reserve(self):
+        """Scratch for window_multi_nll_grad / window_optimize_multi; after window_multi_reserve, at any fill state."""
+        return self._chk(self.lib.cgp_window_multi_grad_reserve(self.h))
+
+    def window_multi_nll_grad(self, want_logml=True, nth=None):
+        """Negative summed log marginal likelihood of the P target columns and its gradient wrt the natural parameters of
+        every window at the theta it holds: (nll (nwin,), grad (nwin, nth), logml (nwin, P)) (logml None with
+        want_logml=False); nll = -logml.sum(axis=1)."""
+        nwin, _ = self._win
+        P = self._win_p
+        stride = self._win_nth if nth is None else nth
+        nll, grad = np.empty(nwin), np.zeros((nwin, stride))
+        logml = np.empty((nwin, P)) if want_logml else None
+        self._chk(self.lib.cgp_window_multi_nll_grad(self.h, P, _p(nll), _p(grad), stride, _p(logml) if want_logml else None))
+        return nll, grad, logml
+
+    def window_multi_nll_grad_device(self, P, dnll, dgrad, grad_stride, dlogml, stream=0):
+        """Device pointers (ints; dlogml 0 / None = not wanted)."""
+        return self._chk(self.lib.cgp_window_multi_nll_grad_device(self.h, P, dnll, dgrad, grad_stride, dlogml or None,
+                                                                   ctypes.c_void_p(stream)))
+
+    def window_optimize_multi(self, max_evals=1000, select=None, nth=None):
+        """m.optimize() with Y (n, P) on the resident windows: the P columns' summed logML maximised over one theta per
+        window, started at the theta each holds: (theta (nwin, nth), logml_sum, n_evals); rows of unselected windows are
+        NaN / 0."""
+        nwin, _ = self._win
+        stride = self._win_nth if nth is None else nth
+        sel, selp = self._select(select)
+        theta, logml, nev = np.full((nwin, stride), np.nan), np.full(nwin, np.nan), np.zeros(nwin, dtype=np.int32)
+        self._chk(self.lib.cgp_window_optimize_multi(self.h, self._win_p, max_evals, selp, _p(theta), stride, _p(logml),
+                                                     nev.ctypes.data_as(_ip)))
         return theta, logml, nev
 
     def window_state(self, w=0):

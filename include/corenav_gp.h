@@ -101,7 +101,9 @@ const char *cgp_last_error(const cgp_ctx *ctx);
  * earlier library answers CGP_EINVAL for them; probe with cgp_fit on a two-sample window).  cgp_window_predict_gradients and
  * cgp_window_predict_gradients_device (predictive gradients from the resident windows): revision 3, symbols added only.
  * cgp_window_multi_reserve, cgp_window_push_multi, cgp_window_push_multi_device, cgp_window_predict_multi and
- * cgp_window_predict_multi_device (multi-target sliding windows): revision 3, symbols added only. */
+ * cgp_window_predict_multi_device (multi-target sliding windows): revision 3, symbols added only.  The same holds for
+ * cgp_window_multi_grad_reserve, cgp_window_multi_nll_grad, cgp_window_multi_nll_grad_device and cgp_window_optimize_multi (the
+ * multi-target windows' summed objective and its optimiser). */
 #define CGP_ABI_VERSION 3
 int cgp_abi_version(void);
 /* How the library was built: 0 for the shipped library.  CGP_BUILD_ABLATION (-DCGP_ABLATION): env
@@ -722,8 +724,9 @@ int cgp_window_predict_gradients_device(cgp_ctx *ctx, int M, const double *dxs, 
  *
  * The other window calls on a multi-target context -- cgp_window_predict, cgp_window_predict_gradients, cgp_window_predict_cov,
  * cgp_window_sample, cgp_window_loo, cgp_window_nll_grad and cgp_window_optimize -- keep working and speak of COLUMN 0.
- * Not provided: a multi-target window optimiser (the summed objective of the P columns), multi-target joint forecast /
- * leave-one-out / predictive gradients, and one-step-ahead outputs for the columns >= 1.
+ * The summed objective of the P columns and its optimiser are cgp_window_multi_nll_grad and cgp_window_optimize_multi, below
+ * cgp_window_optimize.  Not provided: multi-target joint forecast / leave-one-out / predictive gradients, and one-step-ahead
+ * outputs for the columns >= 1.
  * Cost of a forecast: the forecast's n^2 M flops, n^2 P for Z and 2 n M P for the mean rows, per window, on the fp64 matrix
  * cores.  Shares the scratch of the diagonal blocks' inverses with cgp_window_predict: not to run concurrently with the other
  * window forecasts on other streams of the same context. */
@@ -810,6 +813,68 @@ int cgp_window_loo_device(cgp_ctx *ctx, double *dloo_mean, double *dloo_var, dou
  * the entries of selected windows are written.  Returns CGP_ESTATE / CGP_EINVAL / 0.  Blocks. */
 int cgp_window_optimize(cgp_ctx *ctx, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
                         double *logml_out, int *n_evals);
+
+/* ---- multi-target sliding windows: the P columns' summed log marginal likelihood, its gradient and its optimiser ----
+ * The window form of cgp_multi_nll_grad_batch / cgp_optimize_multi_batch: with Y (n, P) the reference's m.optimize() maximises
+ * sum_p logml[p] over ONE theta, and a multi-target window set re-estimates its hyper-parameters for the model it forecasts,
+ * from what is resident -- the factor, the inputs and the target store -- with no host mirror of the samples:
+ *   Z = L^-1 Y    A = L^-T Z = Ky^-1 Y
+ *   nll  = - sum_p logml[p]                                     (logml[p] as cgp_window_predict_multi defines it, summed in p order)
+ *   dnll/dtheta_q = -1/2 sum_ij (sum_p A_ip A_jp - P (Ky^-1)_ij) dK_ij/dtheta_q
+ * One pass over the factor serves all P columns (2 n^3 / 3 + n^2 P flops per window and 2 n^2 P more for A and the rank-P term,
+ * on the fp64 matrix cores); P single-target window sets cost P such passes.  CGP_F64 contexts only, all five kernel ids,
+ * 1 <= P <= 64.
+ *
+ * cgp_window_multi_grad_reserve: after cgp_window_multi_reserve, whose P it takes (CGP_ESTATE without windows or without that
+ * reservation; CGP_EINVAL in a CGP_F32 context): the scratch for A, nwin x ceil(P / 16) x (N rounded up to 16) x 16 doubles
+ * in the Z scratch's tile order, zeroed, and nwin x P doubles for the per-column values of a call that passes no logml.  It holds
+ * no stream state, so it may be called at any fill state of the windows.  CGP_ENOMEM leaves no reservation; calling it again
+ * replaces the reservation; cgp_window_multi_reserve, cgp_window_init and cgp_destroy drop it.  Blocks (it synchronises the
+ * device).
+ *
+ * cgp_window_multi_nll_grad: nll (nwin), grad (nwin, grad_stride), logml (nwin, P) or NULL.  The gradient is with respect to the
+ * natural parameters, in cgp_window_nll_grad's layout and conventions.  Everything is evaluated AT THE THETA THE WINDOW HOLDS,
+ * from the factor, the inputs and the target store as they stand and from n read on the device: a window that is still filling
+ * works, and after cgp_window_set_theta every column is right with no further call.  A failed window answers NaN in nll, in the
+ * gradient and in its P logml entries; an empty window answers 0, a zero gradient and logml 0; neighbours are unaffected.
+ * Status, checked before anything is enqueued: CGP_EINVAL in a CGP_F32 context; CGP_ESTATE without windows or with either
+ * reservation missing; CGP_EINVAL for a P that is not the reservation's, a NULL nll or grad, or grad_stride < ntheta; else 0.
+ * Blocks.
+ * Read-only on the windows: the factor's lower triangle and diagonal, z, the samples, the target store and its tick word and the
+ * state words are not written -- a push, a forecast or a cgp_window_nll_grad after the call is bitwise what it is without it.
+ * Like cgp_window_nll_grad it uses the slabs' strict upper triangle, the scratch of the diagonal blocks' inverses and the gradient
+ * scratch, and like cgp_window_predict_multi the Z scratch: it is not to run beside cgp_window_predict, cgp_window_predict_multi,
+ * cgp_window_predict_gradients, cgp_window_nll_grad, cgp_window_loo, cgp_window_set_theta or the joint forecast on other streams
+ * of the same context.
+ * Determinism: no atomics, every sum in a fixed order.  A window's result depends on the window, its targets, P and N only, not
+ * on its slot or its neighbours; two calls in a row, the host and the device form and a graph replay are bitwise equal; nll and
+ * grad do not depend on whether logml is passed.  Permuting the columns permutes logml bitwise and moves nll and grad by
+ * rounding only.  At P = 1 the result agrees with cgp_window_nll_grad to rounding, not bitwise (the resident z is incremental, Z
+ * is a fresh solve).
+ * Against the routes without it (measured, 1 024 windows x N = 512, d = 3, SE-ARD; DESIGN section 9i has the table): one
+ * evaluation costs 52 ms whatever P <= 16 is (54 ms at P = 64) against 38 ms of one cgp_window_nll_grad_device, so against P
+ * single-target evaluations the crossover is P = 2 (0.73 x at P = 1, 2.9 x at 4, 11.7 x at 16, 45 x at 64).  Against
+ * cgp_multi_nll_grad_batch on a host mirror of the samples (11 ... 17 ms, upload included) it LOSES at every P, by 3.3 ... 4.8 x:
+ * the in-place evaluation is slower than the batch engine's refit, as cgp_window_nll_grad is; what it saves is the mirror.
+ *
+ * cgp_window_optimize_multi: cgp_window_optimize with the summed objective -- the same L-BFGS driver, the same round
+ * (cgp_window_set_theta_device at the trial points, the evaluation above, one copy back), a non-positive-definite trial point
+ * infeasible, the best theta's factor put back where the last trial was not the best.  A start theta <= 0 in a selected window:
+ * CGP_EINVAL before anything is changed.  Afterwards the selected windows hold the optimum and its factor: the next
+ * cgp_window_predict_multi is right for every column with no further call, the next push continues under the new theta.
+ * theta_out (nwin, theta_stride), logml_sum_out (nwin; sum_p logml[p] at the optimum), n_evals (nwin) may be NULL; only the
+ * entries of selected windows are written.  Status as cgp_window_multi_nll_grad, and CGP_EINVAL for theta_stride < ntheta with a
+ * theta_out.  Blocks. */
+int cgp_window_multi_grad_reserve(cgp_ctx *ctx);
+int cgp_window_multi_nll_grad(cgp_ctx *ctx, int P, double *nll, double *grad, int grad_stride, double *logml);
+/* Device-resident variant: device pointers (dlogml may be NULL); five launches enqueued on hip_stream, without allocation,
+ * attribute call or synchronisation (capturable into a hipGraph, like cgp_window_nll_grad_device).  Nothing outside the
+ * documented extents is written, every documented element is written (the first ntheta entries of every gradient row), element
+ * alignment suffices. */
+int cgp_window_multi_nll_grad_device(cgp_ctx *ctx, int P, double *dnll, double *dgrad, int grad_stride, double *dlogml,
+                                     void *hip_stream);
+int cgp_window_optimize_multi(cgp_ctx *ctx, int P, int max_evals, const unsigned char *select, double *theta_out,
+                              int theta_stride, double *logml_sum_out, int *n_evals);
 
 /* ---- joint forecast from the resident windows: full posterior covariance and sample paths ---------
  * cgp_window_predict answers with the marginals (the diagonal of the posterior).  The reference's model also offers the JOINT
