@@ -19,6 +19,7 @@
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
 #include "cgp_loo.hpp"
+#include "cgp_loo_grad.hpp"
 #include "cgp_refine.hpp"
 #include "gp_predictor_core.hpp"
 #include "gp_predictor.h"
@@ -165,6 +166,9 @@ struct cgp_ctx {
   // predictive gradients (cgp_pgrad_reserve): B^T = (Ky^-1 K*)^T and alpha of up to max_batch fits x max_dim test points,
   // [fit][NT 128][M + 1 padded to 128]; the host calls' outputs [dmean | dvar]
   Scratch pg;
+  // leave-one-out objective (cgp_loo_grad_reserve): S = Ky^-1 diag(sqrt c) of up to max_batch fits, [fit][NTmax 128][NTmax 128], then
+  // four vectors per fit, lpd_sum and logml (max_dim is 1); staging of the host calls [nlpd | grad | logml]
+  Scratch lg;
   // cgp_window_push staging, grown on demand and kept: one pinned host block and one device block per direction
   void *win_pin = nullptr, *win_dev = nullptr;
   size_t win_pin_cap = 0, win_dev_cap = 0;
@@ -1524,7 +1528,7 @@ void cgp_destroy(cgp_ctx *c) {
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
   window_free(c, false);
-  for (Scratch *r : {&c->fj, &c->mz, &c->ma, &c->pg}) scratch_free(*r);
+  for (Scratch *r : {&c->fj, &c->mz, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -2980,4 +2984,6 @@ extern "C" int cgp_loo(cgp_ctx *c, const double *X, const double *y, int N, int 
 
 // multi-target objective: cgp_multi_grad_reserve ... cgp_optimize_multi_batch
 #include "cgp_multi_grad_host.hpp"
+// leave-one-out objective: cgp_loo_grad_reserve ... cgp_optimize_loo_batch
+#include "cgp_loo_grad_host.hpp"
 #include "cgp_pgrad_host.hpp"

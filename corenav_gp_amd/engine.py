@@ -67,6 +67,13 @@ _SIGS = {
     "cgp_loo": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     "cgp_loo_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cgp_loo_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp] * 11),
+    "cgp_loo_grad_reserve": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "cgp_loo_nll_grad": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]),
+    "cgp_loo_nll_grad_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_dp, _dp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                                                           _dp, _ip]),
+    "cgp_loo_nll_grad_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                                                                  _vp, _vp, _vp]),
+    "cgp_optimize_loo_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_dp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _ip]),
     "cgp_slip_node_callback_opt": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp,
                                                   ctypes.c_int, _ip]),
     "cgp_slip_node_callback": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp,
@@ -329,6 +336,61 @@ class Context:
         return self._chk(self.lib.cgp_loo_batch_device(self.h, B, N, d, kernel_id, dX, dy, dtheta, djitter or None,
                                                        dloo_mean or None, dloo_var or None, dloo_lpd or None, dlpd_sum or None,
                                                        dlogml, dinfo, ctypes.c_void_p(stream)))
+
+    # -- the leave-one-out objective nlpd = -lpd_sum: gradient and optimiser (fp64 contexts) -------------------
+    def loo_grad_reserve(self, max_batch):
+        """Scratch for the four calls below: max_batch x (max_n rounded up to 128)^2 doubles."""
+        return self._chk(self.lib.cgp_loo_grad_reserve(self.h, int(max_batch)))
+
+    def loo_nll_grad(self, X, y, kernel_id, theta):
+        """(nlpd, grad) of one window: nlpd = -lpd_sum of loo() and its gradient with respect to theta.  Leaves the context
+        fitted at theta, like loo()."""
+        X = _d(X)
+        if X.ndim == 1:
+            X = X[:, None]
+        y, theta = _d(y).reshape(-1), _d(theta)
+        nlpd, grad = ctypes.c_double(0.0), np.empty(len(theta))
+        rc = self._chk(self.lib.cgp_loo_nll_grad(self.h, _p(X), _p(y), X.shape[0], X.shape[1], kernel_id, _p(theta),
+                                                 ctypes.byref(nlpd), _p(grad)))
+        if rc > 0:
+            raise CgpError(rc)
+        self._n = X.shape[0]
+        return nlpd.value, grad
+
+    def loo_nll_grad_batch(self, X, y, theta, kernel_id, want_logml=True):
+        """X (B, N, d), y (B, N), theta (B, nth) -> (rc, nlpd (B,), grad (B, nth), logml (B,) or None, info (B,))."""
+        X, y, theta = _d(X), _d(y), _d(theta)
+        B, N, d = X.shape
+        nth = theta.shape[1]
+        nlpd, grad = np.empty(B), np.empty((B, nth))
+        logml, info = (np.empty(B) if want_logml else None), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_loo_nll_grad_batch(self.h, B, N, d, kernel_id, _p(X), _p(y), _p(theta), nth, _p(nlpd),
+                                                       _p(grad), nth, _p(logml) if want_logml else None,
+                                                       info.ctypes.data_as(_ip)))
+        return rc, nlpd, grad, logml, info
+
+    def loo_nll_grad_batch_device(self, B, N, d, kernel_id, dX, dy, dtheta, djitter, dnlpd, dgrad, grad_stride, dlogml, dinfo,
+                                  stream=0):
+        """Device pointers as loo_batch_device; dnlpd (B,), dgrad (B, grad_stride), dlogml (B,) or 0."""
+        return self._chk(self.lib.cgp_loo_nll_grad_batch_device(self.h, B, N, d, kernel_id, dX, dy, dtheta, djitter or None,
+                                                                dnlpd, dgrad, int(grad_stride), dlogml or None, dinfo,
+                                                                ctypes.c_void_p(stream)))
+
+    def optimize_loo_batch(self, X, y, kernel_id, theta0, max_evals=1000):
+        """theta chosen by the leave-one-out pseudo-likelihood: X (B, N, d), y (B, N), theta0 (B, nth) or (nth,) ->
+        (theta_opt (B, nth), lpd_sum (B,), logml (B,), n_evals (B,)), both objectives at theta_opt."""
+        X, y = _d(X), _d(y)
+        B, N, d = X.shape
+        theta = np.array(theta0, dtype=np.float64)
+        if theta.ndim == 1:
+            theta = np.tile(theta, (B, 1))
+        theta = np.ascontiguousarray(theta)
+        lpd, logml, nev = np.empty(B), np.empty(B), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_optimize_loo_batch(self.h, B, N, d, kernel_id, _p(X), _p(y), _p(theta), theta.shape[1],
+                                                       max_evals, _p(lpd), _p(logml), nev.ctypes.data_as(_ip)))
+        if rc > 0:
+            raise CgpError(rc)
+        return theta, lpd, logml, nev
 
     def optimize(self, X, y, kernel_id, theta0, max_evals=1000):
         """GPy m.optimize() equivalent; returns (theta_opt, logml, n_evals)."""

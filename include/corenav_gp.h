@@ -226,6 +226,53 @@ int cgp_loo_batch_device(cgp_ctx *ctx, int batch, int N, int d, int kernel_id, c
                          double *dloo_mean, double *dloo_var, double *dloo_lpd, double *dlpd_sum,
                          double *dlogml, int *dinfo, void *hip_stream);
 
+/* ---- the leave-one-out objective: value, gradient and optimiser (Rasmussen & Williams 5.4.2) -----
+ * theta chosen by the second opinion: the objective MINIMISED is nlpd = -lpd_sum, bitwise cgp_loo_batch's lpd_sum negated (for
+ * the same number of fits in the call; it comes from the same kernels).  With alpha, kd as above and
+ *     c_i = 1/2 (1 / kd_i + alpha_i^2 / kd_i^2)        b_i = alpha_i / kd_i        beta = Ky^-1 b
+ *     d lpd_sum / dK = -Ky^-1 diag(c) Ky^-1 + 1/2 (beta alpha^T + alpha beta^T)
+ * contracted with dK / dtheta exactly as cgp_nll_grad contracts 1/2 (alpha alpha^T - Ky^-1): the gradient is with respect to the
+ * natural parameters, the noise sees dK / dsigma_n^2 = I, the jitter is a constant of the evaluation.
+ * Cost per fit: the gradient-mode factorisation (5 N^3 / 6), Ky^-1 materialised once (N^3 / 3) and the symmetric product
+ * Ky^-1 diag(c) Ky^-1 on the lower tile pairs (N^3), all on the fp64 matrix cores: about 1.9 x a cgp_nll_grad evaluation, against
+ * 2 ntheta evaluations of cgp_loo_batch for central differences.
+ * Scratch: cgp_loo_grad_reserve(ctx, max_batch) takes max_batch x (the context's max_n rounded up to 128)^2 doubles (+ four vectors
+ * of that length per fit).  1 <= max_batch <= the context's, else CGP_EINVAL; CGP_ENOMEM leaves no reservation and a usable
+ * context; calling it again replaces the reservation.  Blocks.  cgp_destroy frees it.
+ * Status of the calls below, before anything is enqueued: CGP_F32 context: CGP_EINVAL; no reservation: CGP_ESTATE; batch beyond it:
+ * CGP_ECAPACITY; then cgp_loo_batch's shape rules (max_m >= N among them); a NULL required pointer, theta_stride or grad_stride
+ * < ntheta, and for the optimiser a theta <= 0: CGP_EINVAL.  A failed call leaves the context usable.  All five kernel ids; every
+ * shape takes the tiled schedules, as cgp_loo does.
+ * Determinism: run to run bitwise; a fit's nlpd and gradient depend on its own data and on the schedule its call size selects,
+ * never on its slot or its neighbours; no atomics; host, device and graph-replay forms are bitwise equal. */
+int cgp_loo_grad_reserve(cgp_ctx *ctx, int max_batch);
+/* cgp_loo_nll_grad: one window, arguments as cgp_nll_grad; *nlpd and grad (ntheta).  The jitter ladder as cgp_loo runs it.  Returns
+ * 0, or the fit's positive status with NaN in both outputs.  Bitwise cgp_loo_nll_grad_batch of that one fit.  Leaves the context
+ * fitted at theta: cgp_predict may follow. */
+int cgp_loo_nll_grad(cgp_ctx *ctx, const double *X, const double *y, int N, int d, int kernel_id,
+                     const double *theta, double *nlpd, double *grad);
+/* cgp_loo_nll_grad_batch: host buffers in cgp_loo_batch's layouts; nlpd (batch), grad (batch, grad_stride), logml (batch) or NULL,
+ * info (batch) or NULL.  The jitter ladder per fit exactly as cgp_loo_batch runs it.  A fit whose info stays non-zero has NaN in
+ * nlpd and in its gradient; its neighbours are unaffected.  Returns a negative error, else 0 or the first non-zero per-fit status.
+ * Blocks. */
+int cgp_loo_nll_grad_batch(cgp_ctx *ctx, int batch, int N, int d, int kernel_id, const double *X, const double *y,
+                           const double *theta, int theta_stride, double *nlpd, double *grad, int grad_stride,
+                           double *logml, int *info);
+/* Device-resident variant, buffers as cgp_loo_batch_device: dnlpd (batch), dgrad (batch, grad_stride; entries from ntheta on are
+ * not written), dlogml (batch) or NULL, dinfo (batch) int32 (required).  cgp_loo_batch_device's launches plus five on hip_stream:
+ * no allocation, no synchronisation, no ladder (capturable into a hipGraph) -- read dinfo and re-submit the failed fits with
+ * djitter set.  A fit with dinfo != 0 gets NaN. */
+int cgp_loo_nll_grad_batch_device(cgp_ctx *ctx, int batch, int N, int d, int kernel_id, const double *dX, const double *dy,
+                                  const double *dtheta, const double *djitter, double *dnlpd, double *dgrad, int grad_stride,
+                                  double *dlogml, int *dinfo, void *hip_stream);
+/* cgp_optimize_loo_batch: cgp_optimize_batch's host L-BFGS (Logexp transform, pgtol 1e-5, factr 1e7, the jitter ladder per trial
+ * point, +inf for a point that stays infeasible) over the evaluation above: each fit's theta (batch, theta_stride) is replaced by
+ * its optimum.  lpd_sum, logml (batch: both objectives at the returned theta, from one more evaluation that n_evals does not count)
+ * and n_evals (batch) may be NULL.  max_evals <= 0: 1000.  Follow it with cgp_fit_predict_batch at the optima.  Blocks. */
+int cgp_optimize_loo_batch(cgp_ctx *ctx, int batch, int N, int d, int kernel_id, const double *X, const double *y,
+                           double *theta_inout, int theta_stride, int max_evals,
+                           double *lpd_sum, double *logml, int *n_evals);
+
 /* ---- the node callback in one call -------------------------------------------------------------
  * Everything gp_slip_node.py:16-63 computes between "GP Input Arrived" and pub.publish(), at fixed
  * theta: first int(0.9 n) samples train (:27-29), grid arange(min, max + 600, 1) (:45), output
