@@ -8,6 +8,7 @@
 #include "cgp_window_forecast.hpp"
 #include "cgp_window_adapt.hpp"
 #include "cgp_window_loo.hpp"
+#include "cgp_window_loo_grad.hpp"
 #include "cgp_window_joint.hpp"
 #include "cgp_window_pgrad.hpp"
 #include "cgp_window_multi.hpp"
@@ -153,6 +154,9 @@ struct cgp_ctx {
   // multi-target window objective (cgp_window_multi_grad_reserve): the A scratch [nwin][ceil(P / 16)][NB * 16][16] and the
   // per-column values [nwin][P] a call without a logml buffer writes; both null = no reservation
   void *wgbuf[2] = {nullptr};
+  // leave-one-out objective of the windows (cgp_window_loo_grad_reserve): Ky^-1 of every window [nwin][NP][NP], NP = N rounded up
+  // to 64, and one block of per-sample vectors, partial sums and per-window values (cgp_window_host.hpp); both null = none
+  void *wlbuf[2] = {nullptr};
   // joint forecast after batch / single fits (cgp_joint_reserve): the posterior covariance or its factor [max_batch][(mt * 16)^2],
   // then the factorisations' failure words [max_batch]; staging of the host sampling calls [xi | out]
   Scratch fj;

@@ -253,6 +253,7 @@ void window_free(cgp_ctx *c, bool joint_only) {   // (declared in cgp_engine.hip
     release(c->winbuf);
     release(c->wmbuf);
     release(c->wgbuf);   // (the objective's scratch was sized for the reservation's P)
+    release(c->wlbuf);   // (the leave-one-out objective's scratch was sized for these windows)
     c->win_multi_p = 0;
     c->win_multi_ticks = 0;
   }
@@ -1205,5 +1206,130 @@ extern "C" int cgp_window_optimize_multi(cgp_ctx *c, int P, int max_evals, const
   return window_optimize_impl(c, max_evals, select, theta_out, theta_stride, logml_sum_out, n_evals,
                               [&](double *dnll, double *dgrad, int stride, hipStream_t s) {
                                 return cgp_window_multi_nll_grad_device(c, P, dnll, dgrad, stride, nullptr, s);
+                              });
+}
+
+// ---- leave-one-out objective of the resident windows: value, gradient and optimiser (cgp_window_loo_grad.hpp) ----------
+namespace {
+// the reservation's second block, in doubles: loo_var [W][N] | k_window_loo's chunk sums [W][NB] | lpd_sum [W] | c, b, beta
+// [3][W][NP] | k_window_loo_grad's pair sums [W][npair][GRAD_N]
+struct WindowLooGradPlan {
+  size_t NP, nsup, npair, o_part, o_sum, o_c, o_b, o_beta, o_gpart, ndbl;
+};
+WindowLooGradPlan window_loo_grad_plan(const cgp_ctx *c) {
+  WindowLooGradPlan q{};
+  const size_t W = c->nwin, N = c->win.N, NB = cdiv(c->win.N, WPB);
+  q.nsup = cdiv(c->win.N, WJ_ST * WPB);
+  q.NP = q.nsup * WJ_ST * WPB;
+  q.npair = q.nsup * (q.nsup + 1) / 2;
+  q.o_part = W * N;
+  q.o_sum = q.o_part + W * NB;
+  q.o_c = q.o_sum + W;
+  q.o_b = q.o_c + W * q.NP;
+  q.o_beta = q.o_b + W * q.NP;
+  q.o_gpart = q.o_beta + W * q.NP;
+  q.ndbl = q.o_gpart + W * q.npair * GRAD_N;
+  return q;
+}
+// the checks the objective's calls start with, before anything is enqueued
+int window_loo_grad_check(const cgp_ctx *c, bool args_ok) {
+  if (!c || c->nwin < 1 || !c->wlbuf[0] || !c->wlbuf[1]) return CGP_ESTATE;
+  return args_ok ? CGP_OK : CGP_EINVAL;
+}
+}  // namespace
+
+extern "C" int cgp_window_loo_grad_reserve(cgp_ctx *c) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());   // an earlier reservation's buffers are idle
+  auto drop = [&]() {
+    for (void *&b : c->wlbuf) {
+      if (b) (void)hipFree(b);
+      b = nullptr;
+    }
+  };
+  drop();
+  const WindowLooGradPlan q = window_loo_grad_plan(c);
+  const size_t sizes[2] = {(size_t)c->nwin * q.NP * q.NP * 8, q.ndbl * 8};
+  for (int i = 0; i < 2; ++i)
+    if (hipMalloc(&c->wlbuf[i], sizes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      c->wlbuf[i] = nullptr;
+      drop();
+      return CGP_ENOMEM;
+    }
+  // no memset of Ky^-1: every reader masks what the call itself did not write (cgp_window_loo_grad.hpp)
+  if (!hip_ok(c, hipMemset(c->wlbuf[1], 0, sizes[1]), "window LOO gradient scratch memset") ||
+      !hip_ok(c, hipDeviceSynchronize(), "window LOO gradient reserve synchronise")) {   // (cgp_window_init on why)
+    drop();
+    return CGP_EHIP;
+  }
+  return CGP_OK;
+}
+
+// Nine launches: cgp_window_loo_device's four as they stand (loo_var and lpd_sum into the reservation), then c and b, Ky^-1,
+// beta, the product with its contraction, the finish.  Sized by the capacity N; origin, size and failure word are read on the device.
+extern "C" int cgp_window_loo_nll_grad_device(cgp_ctx *c, double *dnlpd, double *dgrad, int grad_stride, double *dlogml,
+                                              void *hip_stream) {
+  int rc = window_loo_grad_check(c, c && c->nwin >= 1 && dnlpd && dgrad && grad_stride >= ntheta(c->win.kernel_id, c->win.d));
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t ws = pick_stream(c, hip_stream);
+  AdaptArgs a = adapt_args(c);
+  a.grad = dgrad; a.grad_stride = grad_stride;
+  const WindowLooGradPlan q = window_loo_grad_plan(c);
+  double *blk = static_cast<double *>(c->wlbuf[1]);
+  const WindowLooOut out{nullptr, blk, nullptr, blk + q.o_sum, blk + q.o_part};
+  WindowLooGradArgs g{};
+  g.kinv = static_cast<double *>(c->wlbuf[0]);
+  g.var = blk; g.lsum = blk + q.o_sum;
+  g.cv = blk + q.o_c; g.bv = blk + q.o_b; g.beta = blk + q.o_beta; g.part = blk + q.o_gpart;
+  g.nlpd = dnlpd; g.logml = dlogml;
+  g.NP = (int)q.NP; g.npair = (int)q.npair; g.per_win = cdiv((int)q.npair, WJ_WAVES);
+  const ForecastArgs f = forecast_args(c);   // k_window_diag_inv reads the windows and writes the inverses only
+  const long long chunks = (long long)c->nwin * a.NB, units = (long long)c->nwin * g.per_win;
+  if (chunks > (1ll << 30) || units > (1ll << 30) || c->nwin > 65535) return CGP_EINVAL;
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, f);
+  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, a);
+  hipLaunchKernelGGL(k_window_loo, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a, out);
+  hipLaunchKernelGGL(k_window_loo_finish, dim3(c->nwin), dim3(64), 0, ws, a, out);
+  hipLaunchKernelGGL(k_window_loo_prep, dim3((unsigned)cdiv(g.NP, 256), c->nwin), dim3(256), 0, ws, a, g);
+  hipLaunchKernelGGL(k_window_loo_kinv, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a, g);
+  hipLaunchKernelGGL(k_window_loo_beta, dim3((unsigned)(g.NP / WLG_EB), c->nwin), dim3(WLG_WAVES * 64), 0, ws, a, g);
+  hipLaunchKernelGGL(k_window_loo_grad, dim3((unsigned)(cdiv((int)units, WF_XCDS) * WF_XCDS)), dim3(WJ_THREADS), 0, ws, a, g);
+  hipLaunchKernelGGL(k_window_loo_grad_finish, dim3((unsigned)cdiv(c->nwin, 64)), dim3(64), 0, ws, a, g);
+  if (!hip_ok(c, hipGetLastError(), "window LOO gradient launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_loo_nll_grad(cgp_ctx *c, double *nlpd, double *grad, int grad_stride, double *logml) {
+  int rc = window_loo_grad_check(c, c && c->nwin >= 1 && nlpd && grad && grad_stride >= ntheta(c->win.kernel_id, c->win.d));
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one device block [nlpd | grad | logml] and its pinned twin: the launches, one D2H, one synchronisation
+  const int nth = ntheta(c->win.kernel_id, c->win.d);
+  const size_t W = c->nwin, ndbl = W * (2 + nth);
+  double *h, *d;
+  if (!window_stage(c, ndbl * 8, ndbl * 8, h, d)) return CGP_ENOMEM;
+  hipStream_t s = c->stream;
+  rc = cgp_window_loo_nll_grad_device(c, d, d + W, nth, logml ? d + W * (1 + nth) : nullptr, s);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(h, d, ndbl * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  memcpy(nlpd, h, W * sizeof(double));
+  for (size_t w = 0; w < W; ++w) memcpy(grad + w * grad_stride, h + W + w * nth, nth * sizeof(double));
+  if (logml) memcpy(logml, h + W * (1 + nth), W * sizeof(double));
+  return CGP_OK;
+}
+
+// cgp_window_optimize with the leave-one-out objective: the same driver and the same round, the evaluation above in
+// cgp_window_nll_grad_device's place; the driver's -f at the returned theta is lpd_sum.
+extern "C" int cgp_window_optimize_loo(cgp_ctx *c, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
+                                       double *lpd_sum_out, int *n_evals) {
+  int rc = window_loo_grad_check(c, true);
+  if (rc != CGP_OK) return rc;
+  return window_optimize_impl(c, max_evals, select, theta_out, theta_stride, lpd_sum_out, n_evals,
+                              [&](double *dnlpd, double *dgrad, int stride, hipStream_t s) {
+                                return cgp_window_loo_nll_grad_device(c, dnlpd, dgrad, stride, nullptr, s);
                               });
 }

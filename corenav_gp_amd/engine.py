@@ -143,6 +143,10 @@ _SIGS = {
     "cgp_window_multi_nll_grad": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp]),
     "cgp_window_multi_nll_grad_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "cgp_window_optimize_multi": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _dp, ctypes.c_int, _dp, _ip]),
+    "cgp_window_loo_grad_reserve": (ctypes.c_int, [_vp]),
+    "cgp_window_loo_nll_grad": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, _dp]),
+    "cgp_window_loo_nll_grad_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "cgp_window_optimize_loo": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, ctypes.c_int, _dp, _ip]),
     "cgp_set_streams": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_set_refine": (ctypes.c_int, [_vp, ctypes.c_int]),
     "cgp_debug_read": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong)]),
@@ -922,6 +926,35 @@ class Context:
         self._chk(self.lib.cgp_window_optimize_multi(self.h, self._win_p, max_evals, selp, _p(theta), stride, _p(logml),
                                                      nev.ctypes.data_as(_ip)))
         return theta, logml, nev
+
+    def window_loo_grad_reserve(self):
+        """Scratch for window_loo_nll_grad / window_optimize_loo; after window_init, at any fill state."""
+        return self._chk(self.lib.cgp_window_loo_grad_reserve(self.h))
+
+    def window_loo_nll_grad(self, want_logml=True, nth=None):
+        """Leave-one-out objective nlpd = -lpd_sum and its gradient wrt the natural parameters of every window at the theta
+        it holds: (nlpd (nwin,), grad (nwin, nth), logml (nwin,)) (logml None with want_logml=False)."""
+        nwin, _ = self._win
+        stride = self._win_nth if nth is None else nth
+        nlpd, grad = np.empty(nwin), np.zeros((nwin, stride))
+        logml = np.empty(nwin) if want_logml else None
+        self._chk(self.lib.cgp_window_loo_nll_grad(self.h, _p(nlpd), _p(grad), stride, _p(logml) if want_logml else None))
+        return nlpd, grad, logml
+
+    def window_loo_nll_grad_device(self, dnlpd, dgrad, grad_stride, dlogml, stream=0):
+        """Device pointers (ints; dlogml 0 / None = not wanted)."""
+        return self._chk(self.lib.cgp_window_loo_nll_grad_device(self.h, dnlpd, dgrad, grad_stride, dlogml or None,
+                                                                 ctypes.c_void_p(stream)))
+
+    def window_optimize_loo(self, max_evals=1000, select=None, nth=None):
+        """L-BFGS on the leave-one-out objective of the resident windows, started at the theta each holds:
+        (theta (nwin, nth), lpd_sum, n_evals); rows of unselected windows are NaN / 0."""
+        nwin, _ = self._win
+        stride = self._win_nth if nth is None else nth
+        sel, selp = self._select(select)
+        theta, lpd, nev = np.full((nwin, stride), np.nan), np.full(nwin, np.nan), np.zeros(nwin, dtype=np.int32)
+        self._chk(self.lib.cgp_window_optimize_loo(self.h, max_evals, selp, _p(theta), stride, _p(lpd), nev.ctypes.data_as(_ip)))
+        return theta, lpd, nev
 
     def window_state(self, w=0):
         n, info = ctypes.c_int(0), ctypes.c_int(0)

@@ -103,7 +103,8 @@ const char *cgp_last_error(const cgp_ctx *ctx);
  * cgp_window_multi_reserve, cgp_window_push_multi, cgp_window_push_multi_device, cgp_window_predict_multi and
  * cgp_window_predict_multi_device (multi-target sliding windows): revision 3, symbols added only.  The same holds for
  * cgp_window_multi_grad_reserve, cgp_window_multi_nll_grad, cgp_window_multi_nll_grad_device and cgp_window_optimize_multi (the
- * multi-target windows' summed objective and its optimiser). */
+ * multi-target windows' summed objective and its optimiser), and for cgp_window_loo_grad_reserve, cgp_window_loo_nll_grad,
+ * cgp_window_loo_nll_grad_device and cgp_window_optimize_loo (the windows' leave-one-out objective and its optimiser). */
 #define CGP_ABI_VERSION 3
 int cgp_abi_version(void);
 /* How the library was built: 0 for the shipped library.  CGP_BUILD_ABLATION (-DCGP_ABLATION): env
@@ -922,6 +923,65 @@ int cgp_window_multi_nll_grad_device(cgp_ctx *ctx, int P, double *dnll, double *
                                      void *hip_stream);
 int cgp_window_optimize_multi(cgp_ctx *ctx, int P, int max_evals, const unsigned char *select, double *theta_out,
                               int theta_stride, double *logml_sum_out, int *n_evals);
+
+/* ---- sliding windows: the leave-one-out objective, its gradient and its optimiser ----
+ * The window form of cgp_loo_nll_grad_batch / cgp_optimize_loo_batch (the cgp_loo_nll_grad section above has the algebra): a
+ * window set re-estimates its hyper-parameters by the leave-one-out pseudo-likelihood from what is resident -- the factor L of
+ * Ky = K + (sigma_n^2 + 1e-8) I, z, the inputs and the targets -- with no host mirror of the samples and no jitter ladder:
+ *   alpha = L^-T z    kd_i = (Ky^-1)_ii    c_i = 1/2 (1 / kd_i + alpha_i^2 / kd_i^2)    b_i = alpha_i / kd_i    beta = Ky^-1 b
+ *   nlpd = - lpd_sum                                                   (lpd_sum as cgp_window_loo defines it)
+ *   dnlpd/dtheta_q = -1/2 sum_ij (-2 sum_k Ky^-1_ik c_k Ky^-1_kj + beta_i alpha_j + alpha_i beta_j) dK_ij/dtheta_q
+ * fp64 whatever the context's dtype, as cgp_window_loo and cgp_window_nll_grad are; all five kernel ids, d <= 8.  Per window
+ * 4 n^3 / 3 flops for Ky^-1 and cgp_window_loo's pass and n^3 for the product, on the fp64 matrix cores.
+ *
+ * cgp_window_loo_grad_reserve: after cgp_window_init (CGP_ESTATE without windows).  With NP = N rounded up to 64 (the product
+ * kernel's super-tile) and S = NP / 64 it holds Ky^-1 of every window, nwin x NP x NP doubles (2.1 GB for 1 024 x N = 512), and
+ * one block of nwin x (N + ceil(N / 16) + 1 + 3 NP + 12 S (S + 1) / 2) doubles: loo_var, cgp_window_loo's chunk sums, lpd_sum,
+ * the vectors c, b and beta, and the product kernel's twelve partial sums per super-tile pair.  It holds no stream state, so it
+ * may be called at any fill state of the windows.  CGP_ENOMEM leaves no reservation and a usable context; calling it again
+ * replaces the reservation; cgp_window_init and cgp_destroy drop it.  Blocks (it synchronises the device).
+ *
+ * cgp_window_loo_nll_grad: nlpd (nwin), grad (nwin, grad_stride; only the first ntheta entries of a row are written), logml
+ * (nwin) or NULL -- the log marginal likelihood at no extra cost.  The gradient is with respect to the natural parameters, in
+ * cgp_window_nll_grad's layout.  Everything is evaluated AT THE THETA THE WINDOW HOLDS, from the factor, z, the inputs and the
+ * targets as they stand and from n, the origin and the failure word read on the device: a window that is still filling works,
+ * n = 1 included.  A failed window answers NaN in nlpd, in the gradient and in logml; an empty window answers 0, a zero
+ * gradient and 0; neighbours are unaffected.  nlpd is bitwise cgp_window_loo's lpd_sum negated and logml bitwise
+ * cgp_window_nll_grad's nll negated (their launches run first, as they stand).
+ * Status, checked before anything is enqueued: CGP_ESTATE without windows or without the reservation; CGP_EINVAL for a NULL
+ * nlpd or grad, grad_stride < ntheta, or more than 65 535 windows; else 0.  Blocks.
+ * Read-only on the windows: the factor's lower triangle and diagonal, z, the samples and the state words are not written -- a
+ * push, a forecast, a cgp_window_nll_grad or a cgp_window_loo after the call is bitwise what it is without it.  Like
+ * cgp_window_loo it uses the slabs' strict upper triangle, the scratch of the diagonal blocks' inverses, the alpha buffer and
+ * the gradient scratch: it is not to run beside cgp_window_predict, cgp_window_predict_multi, cgp_window_predict_gradients,
+ * cgp_window_nll_grad, cgp_window_multi_nll_grad, cgp_window_loo, cgp_window_set_theta, a push or the joint forecast on other
+ * streams of the same context.
+ * Determinism: no atomics, every sum in a fixed order.  A window's result depends on the window alone, not on its slot or its
+ * neighbours; two calls in a row, the host and the device form and a graph replay are bitwise equal; nlpd and grad do not depend
+ * on whether logml is passed, nor on what the scratch held before (every reader masks the rows and columns from n on).
+ * Against the routes without it (measured, 1 024 windows x N = 512, d = 3, SE-ARD; DESIGN section 9k has the table): one
+ * evaluation costs 52 ms (26 ms of it Ky^-1, 12 ms cgp_window_loo's pass, 12 ms the product) against 223 ms for central differences
+ * on the windows -- 2 ntheta = 10 rounds of cgp_window_set_theta_device + cgp_window_loo_device -- so it wins 4.3 x there and
+ * carries no finite-difference noise.  Against cgp_loo_nll_grad_batch on a host mirror of the samples (12.7 ms, upload included)
+ * it LOSES, by 4.1 x, and a full cgp_window_optimize_loo loses to cgp_optimize_loo_batch on the mirror by 5.3 x: the in-place
+ * evaluation is slower than the batch engine's refit, as cgp_window_nll_grad is; what it saves is the mirror.
+ *
+ * cgp_window_optimize_loo: cgp_window_optimize with the leave-one-out objective -- the same L-BFGS driver, the same round
+ * (cgp_window_set_theta_device at the trial points, the evaluation above, one copy back), a non-positive-definite trial point
+ * infeasible, the best theta's factor put back where the last trial was not the best.  A start theta <= 0 in a selected window:
+ * CGP_EINVAL before anything is changed.  Afterwards the selected windows hold the optimum and its factor; pushes and forecasts
+ * continue under it.  theta_out (nwin, theta_stride), lpd_sum_out (nwin; lpd_sum at the returned theta), n_evals (nwin) may be
+ * NULL; only the entries of selected windows are written.  Status as cgp_window_loo_nll_grad, and CGP_EINVAL for theta_stride <
+ * ntheta with a theta_out.  Blocks. */
+int cgp_window_loo_grad_reserve(cgp_ctx *ctx);
+int cgp_window_loo_nll_grad(cgp_ctx *ctx, double *nlpd, double *grad, int grad_stride, double *logml);
+/* Device-resident variant: device pointers (dlogml may be NULL); nine launches enqueued on hip_stream, without allocation,
+ * attribute call or synchronisation (capturable into a hipGraph, like cgp_window_loo_device).  Nothing outside the documented
+ * extents is written, every documented element is written (the first ntheta entries of every gradient row), element alignment
+ * suffices. */
+int cgp_window_loo_nll_grad_device(cgp_ctx *ctx, double *dnlpd, double *dgrad, int grad_stride, double *dlogml, void *hip_stream);
+int cgp_window_optimize_loo(cgp_ctx *ctx, int max_evals, const unsigned char *select, double *theta_out, int theta_stride,
+                            double *lpd_sum_out, int *n_evals);
 
 /* ---- joint forecast from the resident windows: full posterior covariance and sample paths ---------
  * cgp_window_predict answers with the marginals (the diagonal of the posterior).  The reference's model also offers the JOINT

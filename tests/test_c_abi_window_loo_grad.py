@@ -1,0 +1,44 @@
+"""A compiled ISO C11 caller of the windows' leave-one-out objective (tests/c_abi/window_loo_grad.c: cgp_window_loo_grad_reserve,
+cgp_window_loo_nll_grad, cgp_window_optimize_loo), built `-pedantic -Werror` like the other callers; on the GPU it checks the
+empty window, the n = 1 closed form, which the C file writes out itself, and a few more ticks."""
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+HERE = os.path.join(ROOT, "tests", "c_abi")
+LIBDIR = os.path.join(ROOT, "corenav_gp_amd")
+SYMBOLS = ("cgp_window_loo_grad_reserve", "cgp_window_loo_nll_grad", "cgp_window_loo_nll_grad_device", "cgp_window_optimize_loo")
+
+
+@pytest.fixture(scope="module")
+def caller(tmp_path_factory):
+    if not os.path.exists(os.path.join(LIBDIR, "libcorenav_gp.so")):
+        import __graft_entry__ as ge
+        ge.build()
+    exe = os.path.join(str(tmp_path_factory.mktemp("c_abi_window_loo_grad")), "window_loo_grad")
+    subprocess.check_call(["gcc", "-std=c11", "-pedantic", "-Wall", "-Wextra", "-Werror", "-O1", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(HERE, "window_loo_grad.c"), "-o", exe, "-L", LIBDIR, "-lcorenav_gp", "-lm",
+                           f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_c_window_loo_grad_caller_builds_and_links(caller):
+    assert os.access(caller, os.X_OK)
+
+
+def test_the_four_symbols_are_declared_and_bound():
+    import corenav_gp_amd.engine as engine
+    hdr = open(os.path.join(ROOT, "include", "corenav_gp.h")).read()
+    for name in SYMBOLS:
+        assert f"int {name}(cgp_ctx *ctx" in hdr and name in engine.EXPORTS
+    assert "#define CGP_ABI_VERSION 3" in hdr
+
+
+@pytest.mark.gpu
+def test_c_caller_checks_the_closed_form_on_the_gpu(caller):
+    r = subprocess.run([caller], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout, r.stderr)
+    assert "window_loo_grad.c ok" in r.stdout
