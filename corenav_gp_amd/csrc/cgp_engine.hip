@@ -71,6 +71,39 @@ struct Scratch {
   size_t stage_cap = 0;
 };
 
+// The sliding windows' device buffers: one record per reservation, one hipMalloc per member, the reservation's capacity beside
+// them.  each() names the members once, for window_release; which record goes with which is window_drop's to say (cgp_window_host.hpp).
+struct WinBufs {   // cgp_window_init: factors [nwin][CAP][CAP], z = L^-1 y [nwin][CAP], inputs [nwin][d][CAP], targets [nwin][CAP],
+  double *L = nullptr, *z = nullptr, *xw = nullptr, *yw = nullptr;
+  int *state = nullptr;            // state words [nwin][4],
+  double *prep_theta = nullptr;    // prep [nwin][PREP_N] | theta [nwin][MAX_THETA],
+  double *dinv = nullptr;          // k_window_diag_inv's inverses of the factors' 16 x 16 diagonal blocks [nwin][NB][256],
+  double *grad_scratch = nullptr;  // alpha [nwin][NB * 16] | chunk sums [nwin][NB][GRAD_N] | values [nwin] (adapt_args carves it)
+  template <class F> void each(F &&f) { f(L); f(z); f(xw); f(yw); f(state); f(prep_theta); f(dinv); f(grad_scratch); }
+};
+struct WinJointBufs {   // cgp_window_joint_reserve: V kept [nwin][mt][NB * 16][16], the matrix / its factor [nwin][(mt * 16)^2],
+  double *V = nullptr, *C = nullptr, *mean_var = nullptr;   // mean | variance [2][nwin][max_m],
+  int *jinfo = nullptr;                                     // failure words [nwin]
+  int max_m = 0;                                            // test points the reservation holds; 0 = none
+  template <class F> void each(F &&f) { f(V); f(C); f(mean_var); f(jinfo); }
+};
+struct WinMultiBufs {   // cgp_window_multi_reserve: the target store [nwin][P][N], its tick counts [nwin], the Z scratch
+  double *ystore = nullptr;   // [nwin][ceil(P / 16)][NB * 16][16], and column 0 of a push gathered for the push kernels
+  int *ycount = nullptr;      // [nwin][ticks], which regrows on its own (cgp_window_push_multi_device)
+  double *zs = nullptr, *y0 = nullptr;
+  int P = 0;          // the reservation's P; 0 = none
+  size_t ticks = 0;   // ticks per push the gather block holds
+  template <class F> void each(F &&f) { f(ystore); f(ycount); f(zs); f(y0); }
+};
+struct WinMultiGradBufs {   // cgp_window_multi_grad_reserve: the A scratch [nwin][ceil(P / 16)][NB * 16][16] (null = none) and the
+  double *am = nullptr, *colval = nullptr;   // per-column values [nwin][P] a call without a logml buffer writes
+  template <class F> void each(F &&f) { f(am); f(colval); }
+};
+struct WinLooGradBufs {   // cgp_window_loo_grad_reserve: Ky^-1 of every window [nwin][NP][NP], NP = N rounded up to 64 (null = none),
+  double *kinv = nullptr, *blk = nullptr;   // and one block of per-sample vectors, partial sums and per-window values (WindowLooGradPlan)
+  template <class F> void each(F &&f) { f(kinv); f(blk); }
+};
+
 }  // namespace
 
 struct cgp_ctx {
@@ -141,22 +174,14 @@ struct cgp_ctx {
   WindowArgs win{};
   int nwin = 0;
   int win_o = 0, win_n = 0;   // origin / size of the windows (they advance in lock-step), mirrored on the host to cut a push into launches
-  void *winbuf[8] = {nullptr};
-  // joint forecast (cgp_window_joint_reserve): V kept [nwin][mt][NB * 16][16], the matrix / its factor [nwin][(mt * 16)^2],
-  // mean | variance [2][nwin][max_m], failure words [nwin]
-  void *jointbuf[4] = {nullptr};
-  int joint_max_m = 0;
-  // multi-target windows (cgp_window_multi_reserve): the target store [nwin][P][N], its tick counts [nwin] (ints), the Z scratch
-  // [nwin][ceil(P / 16)][NB * 16][16], and column 0 of a push gathered for the push kernels [nwin][win_multi_ticks]
-  void *wmbuf[4] = {nullptr};
-  int win_multi_p = 0;          // the reservation's P; 0 = none
-  size_t win_multi_ticks = 0;   // ticks per push the gather block holds
-  // multi-target window objective (cgp_window_multi_grad_reserve): the A scratch [nwin][ceil(P / 16)][NB * 16][16] and the
-  // per-column values [nwin][P] a call without a logml buffer writes; both null = no reservation
-  void *wgbuf[2] = {nullptr};
-  // leave-one-out objective of the windows (cgp_window_loo_grad_reserve): Ky^-1 of every window [nwin][NP][NP], NP = N rounded up
-  // to 64, and one block of per-sample vectors, partial sums and per-window values (cgp_window_host.hpp); both null = none
-  void *wlbuf[2] = {nullptr};
+  // their buffers and the four reservations' (the records above name every member and its shape).  Lifetimes, as window_drop
+  // states them: the windows go -> every reservation goes; the multi-target reservation goes -> its objective's scratch goes;
+  // the joint forecast's and the leave-one-out objective's scratch go alone.
+  WinBufs wb;            // cgp_window_init (win points into it)
+  WinJointBufs wj;       // joint forecast: cgp_window_joint_reserve
+  WinMultiBufs wm;       // multi-target windows: cgp_window_multi_reserve
+  WinMultiGradBufs wg;   // their summed objective: cgp_window_multi_grad_reserve
+  WinLooGradBufs wl;     // leave-one-out objective: cgp_window_loo_grad_reserve
   // joint forecast after batch / single fits (cgp_joint_reserve): the posterior covariance or its factor [max_batch][(mt * 16)^2],
   // then the factorisations' failure words [max_batch]; staging of the host sampling calls [xi | out]
   Scratch fj;
@@ -352,7 +377,8 @@ int node_callback_small(cgp_ctx *c, const double *time_array, const double *slip
                         double *mean, double *sigma, int cap, int *m_out);
 bool grow_pinned(void *&p, size_t &cap, size_t bytes);
 bool grow_device(void *&p, size_t &cap, size_t bytes);
-void window_free(cgp_ctx *c, bool joint_only);   // cgp_window_host.hpp
+enum class WinDrop { Windows, Multi, MultiGrad, Joint, LooGrad };
+void window_drop(cgp_ctx *c, WinDrop what);   // cgp_window_host.hpp: frees what goes with `what`
 // What a batch entry point with more than mean / variance to compute (joint, multi-target, predictive-gradient calls) enqueues on s
 // for the `nfit` fits whose panels are slabs slab, slab + 1, ... into the slots slot, slot + 1, ... of its own arrays, while the
 // fits' V rows are still in the panel.  Each entry point builds its own, next to the arrays (fit_predict_batch_host calls it):
@@ -1531,7 +1557,7 @@ void cgp_destroy(cgp_ctx *c) {
   }
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
-  window_free(c, false);
+  window_drop(c, WinDrop::Windows);
   for (Scratch *r : {&c->fj, &c->mz, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);

@@ -1,7 +1,7 @@
 // cgp_window_host.hpp -- host layer of the sliding windows: the cgp_window_* entry points of include/corenav_gp.h.  The kernels
 // are in cgp_window.hpp (push), cgp_window_forecast.hpp, cgp_window_pgrad.hpp, cgp_window_multi.hpp, cgp_window_multi_grad.hpp, cgp_window_adapt.hpp and cgp_window_joint.hpp.  Not a translation unit
-// of its own: cgp_engine.hip includes it after cgp_ctx and the helpers it uses (hip_ok / HIP_TRY, grow_pinned, grow_device,
-// pick_stream, cdiv, ntheta).
+// of its own: cgp_engine.hip includes it after cgp_ctx (whose WinBufs ... WinLooGradBufs records hold the windows' device buffers)
+// and the helpers it uses (hip_ok / HIP_TRY, grow_pinned, grow_device, pick_stream, cdiv, xcd_grid, ntheta).
 #pragma once
 
 namespace {
@@ -172,7 +172,7 @@ ForecastArgs forecast_args(cgp_ctx *c) {
   const WindowArgs &wa = c->win;
   ForecastArgs a{};
   a.L = wa.L; a.z = wa.z; a.xw = wa.xw; a.state = wa.state; a.prep = wa.prep; a.theta = wa.theta;
-  a.dinv = static_cast<double *>(c->winbuf[6]);
+  a.dinv = c->wb.dinv;
   a.N = wa.N; a.CAP = wa.CAP; a.d = wa.d; a.kernel_id = wa.kernel_id; a.nwin = c->nwin;
   a.NB = cdiv(wa.N, WPB);
   return a;
@@ -181,9 +181,9 @@ JointArgs joint_args(cgp_ctx *c) {   // with the scratch of cgp_window_joint_res
   const WindowArgs &wa = c->win;
   JointArgs j{};
   j.state = wa.state; j.prep = wa.prep; j.theta = wa.theta;
-  j.V = static_cast<double *>(c->jointbuf[0]);
-  j.C = static_cast<double *>(c->jointbuf[1]);
-  j.jinfo = static_cast<int *>(c->jointbuf[3]);
+  j.V = c->wj.V;
+  j.C = c->wj.C;
+  j.jinfo = c->wj.jinfo;
   j.d = wa.d; j.kernel_id = wa.kernel_id; j.nwin = c->nwin;
   j.nrow = cdiv(wa.N, WPB) * WPB;
   return j;
@@ -196,17 +196,54 @@ AdaptArgs adapt_args(cgp_ctx *c) {
   a.theta = const_cast<double *>(wa.theta);
   a.N = wa.N; a.CAP = wa.CAP; a.d = wa.d; a.kernel_id = wa.kernel_id; a.nwin = c->nwin;
   a.NB = cdiv(wa.N, WPB);
-  a.dinv = static_cast<double *>(c->winbuf[6]);
-  double *sc = static_cast<double *>(c->winbuf[7]);
-  a.alpha = sc;
-  a.gpart = sc + (size_t)c->nwin * a.NB * WPB;
+  a.dinv = c->wb.dinv;
+  a.alpha = c->wb.grad_scratch;   // alpha | chunk sums | values
+  a.gpart = a.alpha + (size_t)c->nwin * a.NB * WPB;
   a.nllv = a.gpart + (size_t)c->nwin * a.NB * GRAD_N;
   // the multi-target objective (null / 0 without its reservations)
-  a.zs = static_cast<const double *>(c->wmbuf[2]);
-  a.am = static_cast<double *>(c->wgbuf[0]);
-  a.P = c->win_multi_p;
-  a.pt = cdiv(c->win_multi_p, WPB);
+  a.zs = c->wm.zs;
+  a.am = c->wg.am;
+  a.P = c->wm.P;
+  a.pt = cdiv(c->wm.P, WPB);
   return a;
+}
+// k_window_multi_z's view: Z = L^-1 Y of the reservation's P columns into the Z scratch, with the columns' logml to mlogml (or
+// null).  The targets take the test points' place: M = P, the chunks are zf's.
+ForecastArgs multi_z_args(cgp_ctx *c, const ForecastForm &zf, double *mlogml) {
+  ForecastArgs za = forecast_args(c);
+  za.ystore = c->wm.ystore; za.ycount = c->wm.ycount; za.zs = c->wm.zs;
+  za.P = c->wm.P;
+  za.pt = cdiv(c->wm.P, WPB);
+  za.M = c->wm.P;
+  za.nchunk = cdiv(c->wm.P, zf.mc);
+  za.mlogml = mlogml;
+  return za;
+}
+
+// ---- launches several entry points share.  They enqueue and check nothing: every limit of a call is checked by the call, before
+// its first launch, with fits_grid (a plain grid) or the engine's xcd_grid (a grid rounded up to the XCDs) ----------------------
+inline bool fits_grid(long long workgroups) { return workgroups <= (1ll << 30); }
+inline long long diag_inv_groups(const cgp_ctx *c) { return (long long)cdiv(cdiv(c->win.N, WPB), 4) * c->nwin; }   // four blocks per workgroup
+inline long long window_chunks(const cgp_ctx *c) { return (long long)c->nwin * cdiv(c->win.N, WPB); }              // four per workgroup of 256
+// the inverses of the factors' diagonal blocks (the kernel reads the windows and writes the inverses only)
+void launch_diag_inv(cgp_ctx *c, hipStream_t ws) {
+  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)diag_inv_groups(c)), dim3(64), 0, ws, forecast_args(c));
+}
+// ... and alpha = L^-T z into the gradient's scratch
+void launch_alpha(cgp_ctx *c, const AdaptArgs &a, hipStream_t ws) {
+  launch_diag_inv(c, ws);
+  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, a);
+}
+// ... and the leave-one-out pass with its finish
+void launch_loo(cgp_ctx *c, const AdaptArgs &a, const WindowLooOut &out, hipStream_t ws) {
+  launch_alpha(c, a, ws);
+  hipLaunchKernelGGL(k_window_loo, dim3((unsigned)((window_chunks(c) + 3) / 4)), dim3(256), 0, ws, a, out);
+  hipLaunchKernelGGL(k_window_loo_finish, dim3(c->nwin), dim3(64), 0, ws, a, out);
+}
+// every instantiation a launch can pick gets its LDS limit in cgp_window_init / cgp_window_multi_reserve only: the _device entry
+// points make no attribute call (they are captured into graphs)
+template <class K> bool lds_limit(K kernel, int bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
 }
 
 // The host entry points stage through one pinned block and its device twin, which live in the context, grown on demand and kept.
@@ -241,24 +278,64 @@ inline int first_flagged_window(const int *info, size_t W) {
   return CGP_OK;
 }
 
-// Frees the joint forecast's scratch and, unless joint_only, the windows' buffers: the scratch goes with the windows it was sized for.
-void window_free(cgp_ctx *c, bool joint_only) {   // (declared in cgp_engine.hip for cgp_destroy)
-  auto release = [](auto &bufs) {
-    for (void *&b : bufs) {
-      if (b) (void)hipFree(b);
-      b = nullptr;
+// What the host forms of the forecasts and of the multi-target push share, after their checks: one pinned block [nin doubles of
+// inputs | nout of outputs | state words] and its device twin; fill(h) stages the inputs, run(io, stream) is the device form on
+// the block at io, of whose outputs the first nback come back.  zero_copy: a block of up to kWinZeroCopyBytes is read and
+// written in place by the kernels (no copy command); else one H2D and two D2H (outputs, state words), one synchronisation.
+// Returns a negative code, or what first_failing_tick says with the outputs at h + nin for the caller to hand out.
+template <class Fill, class Run>
+int window_staged_call(cgp_ctx *c, size_t nin, size_t nout, size_t nback, bool zero_copy, double *&h, Fill &&fill, Run &&run) {
+  const size_t W = c->nwin, ndbl = nin + nout, bytes = ndbl * 8 + W * 4 * sizeof(int);
+  double *d;
+  if (!window_stage(c, bytes, ndbl * 8, h, d)) return CGP_ENOMEM;
+  int *hst = reinterpret_cast<int *>(h + ndbl);
+  fill(h);
+  hipStream_t s = c->stream;
+  const bool inplace = zero_copy && bytes <= kWinZeroCopyBytes;
+  if (!inplace) HIP_TRY(c, hipMemcpyAsync(d, h, nin * 8, hipMemcpyHostToDevice, s));
+  int rc = run(inplace ? h : d, s);
+  if (rc != CGP_OK) return rc;
+  if (!inplace) HIP_TRY(c, hipMemcpyAsync(h + nin, d + nin, nback * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
+  return first_failing_tick(hst + 2, W, 4);
+}
+
+// ---- the windows' buffer records (WinBufs ... WinLooGradBufs, cgp_engine.hip) ---------------------------------------------------
+template <class R> void window_release(R &r) {   // a record's buffers freed, its capacity back to none
+  r.each([](auto *p) { if (p) (void)hipFree(p); });
+  r = R{};
+}
+// The lifetime rules, here and nowhere else: what goes when `what` goes (a new cgp_window_init, a new reservation, cgp_destroy).
+// Every reservation was sized for the windows it was made on, and the multi-target objective's scratch for the reservation's P.
+void window_drop(cgp_ctx *c, WinDrop what) {   // (declared in cgp_engine.hip for cgp_destroy)
+  const bool all = what == WinDrop::Windows;
+  if (all) window_release(c->wb);
+  if (all || what == WinDrop::Multi) window_release(c->wm);
+  if (all || what == WinDrop::Multi || what == WinDrop::MultiGrad) window_release(c->wg);
+  if (all || what == WinDrop::LooGrad) window_release(c->wl);
+  if (all || what == WinDrop::Joint) window_release(c->wj);
+}
+// One buffer of the reservation `what` (a member of its record, null when the call starts): its size, and whether it starts as zeros.
+struct WinSlot { void **p; size_t bytes; bool zero; };
+template <class T> WinSlot slot(T *&p, size_t bytes, bool zero = false) { return {reinterpret_cast<void **>(&p), bytes, zero}; }
+// one hipMalloc per slot; on failure the HIP error is cleared and the reservation is dropped, which frees what it got
+template <size_t K> int window_alloc(cgp_ctx *c, WinDrop what, const WinSlot (&slots)[K]) {
+  for (const WinSlot &s : slots)
+    if (hipMalloc(s.p, s.bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      *s.p = nullptr;
+      window_drop(c, what);
+      return CGP_ENOMEM;
     }
-  };
-  if (!joint_only) {   // the multi-target reservation was sized for these windows and their (empty) state
-    release(c->winbuf);
-    release(c->wmbuf);
-    release(c->wgbuf);   // (the objective's scratch was sized for the reservation's P)
-    release(c->wlbuf);   // (the leave-one-out objective's scratch was sized for these windows)
-    c->win_multi_p = 0;
-    c->win_multi_ticks = 0;
-  }
-  release(c->jointbuf);
-  c->joint_max_m = 0;
+  return CGP_OK;
+}
+// the zero-filled slots' memsets and the synchronisation they need (cgp_window_init on why); on failure the reservation is dropped
+template <size_t K> int window_zero(cgp_ctx *c, WinDrop what, const WinSlot (&slots)[K], const char *name) {
+  bool ok = true;
+  for (const WinSlot &s : slots) ok = ok && (!s.zero || hip_ok(c, hipMemset(*s.p, 0, s.bytes), name));
+  if (ok && hip_ok(c, hipDeviceSynchronize(), name)) return CGP_OK;
+  window_drop(c, what);
+  return CGP_EHIP;
 }
 
 }  // namespace
@@ -270,12 +347,8 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
   const int nth = ntheta(kid, d);
   if (theta_stride < nth) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
-  // every instantiation a launch can pick for this kernel id gets its LDS limit, here only: the _device entry points make no
-  // attribute call (they are captured into graphs)
+  // every instantiation a launch can pick for this kernel id gets its LDS limit (lds_limit on why here)
   const bool mat = k_is_matern(kid);
-  auto lds_limit = [](auto kernel, int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-  };
   for (int wpw : {1, 2, 4})
     if (!lds_limit(pairs_kernel(wpw, mat), kWinPushLdsMax)) return CGP_EHIP;
   if (!lds_limit(k_window_multi<kWinMulti>, kWinPushLdsMax)) return CGP_EHIP;
@@ -288,26 +361,19 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
   // not with stale pointers (cgp_window_push checks nwin)
   c->nwin = 0;
   c->win = WindowArgs{};
-  window_free(c, false);
+  window_drop(c, WinDrop::Windows);
   const int CAP = 2 * N + CGP_WIN_CAP_PAD;   // ring capacity = leading dimension of the windows' slabs
-  const size_t W = nwin;
-  // [6]: cgp_window_predict's inverses of the factors' 16 x 16 diagonal blocks (allocated here: no allocation between launches of a call)
-  // [7]: cgp_window_nll_grad's alpha, per-chunk partial sums and values (cgp_window_adapt.hpp): 28 N / 16 + 1 doubles per window
-  size_t sizes[8] = {W * CAP * CAP * 8, W * CAP * 8, W * d * CAP * 8, W * CAP * 8, W * 4 * sizeof(int),
-                     W * (PREP_N + MAX_THETA) * 8, W * cdiv(N, WPB) * WPB * WPB * 8, W * ((size_t)cdiv(N, WPB) * (WPB + GRAD_N) + 1) * 8};
-  for (int i = 0; i < 8; ++i)
-    if (hipMalloc(&c->winbuf[i], sizes[i]) != hipSuccess) {
-      c->winbuf[i] = nullptr;
-      window_free(c, false);
-      return CGP_ENOMEM;
-    }
+  const size_t W = nwin, NB = cdiv(N, WPB);
+  WinBufs &b = c->wb;
+  // dinv: cgp_window_predict's (allocated here: no allocation between launches of a call); grad_scratch: cgp_window_nll_grad's
+  // alpha, per-chunk partial sums and values (cgp_window_adapt.hpp): 28 N / 16 + 1 doubles per window
+  const WinSlot slots[] = {slot(b.L, W * CAP * CAP * 8), slot(b.z, W * CAP * 8), slot(b.xw, W * d * CAP * 8), slot(b.yw, W * CAP * 8),
+                           slot(b.state, W * 4 * sizeof(int), true), slot(b.prep_theta, W * (PREP_N + MAX_THETA) * 8),
+                           slot(b.dinv, W * NB * WPB * WPB * 8), slot(b.grad_scratch, W * (NB * (WPB + GRAD_N) + 1) * 8)};
+  if (window_alloc(c, WinDrop::Windows, slots) != CGP_OK) return CGP_ENOMEM;
   WindowArgs wa{};
-  wa.L = (double *)c->winbuf[0];
-  wa.z = (double *)c->winbuf[1];
-  wa.xw = (double *)c->winbuf[2];
-  wa.yw = (double *)c->winbuf[3];
-  wa.state = (int *)c->winbuf[4];
-  double *pt = (double *)c->winbuf[5];
+  wa.L = b.L; wa.z = b.z; wa.xw = b.xw; wa.yw = b.yw; wa.state = b.state;
+  double *pt = b.prep_theta;
   wa.prep = pt;
   wa.theta = pt + W * PREP_N;
   wa.N = N;
@@ -328,12 +394,11 @@ extern "C" int cgp_window_init(cgp_ctx *c, int nwin, int N, int d, int kid, cons
   // push could read the windows' state words before they were zeroed (found by round 6's sweep under load: fourteen processes
   // sharing the GPU -- a memory access fault, or garbage for one window; never seen on an idle GPU, where the fill is over
   // before the first launch is issued).
-  if (!hip_ok(c, hipMemcpy(pt, h.data(), h.size() * 8, hipMemcpyHostToDevice), "window theta H2D") ||
-      !hip_ok(c, hipMemset(wa.state, 0, W * 4 * sizeof(int)), "window state memset") ||
-      !hip_ok(c, hipDeviceSynchronize(), "window init synchronise")) {
-    window_free(c, false);
+  if (!hip_ok(c, hipMemcpy(pt, h.data(), h.size() * 8, hipMemcpyHostToDevice), "window theta H2D")) {
+    window_drop(c, WinDrop::Windows);
     return CGP_EHIP;
   }
+  if (window_zero(c, WinDrop::Windows, slots, "window state memset / synchronise") != CGP_OK) return CGP_EHIP;
   c->win = wa;  // published only when every allocation and copy has succeeded
   c->nwin = nwin;
   c->win_o = c->win_n = 0;
@@ -346,7 +411,7 @@ int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, in
 }
 extern "C" int cgp_window_push_device(cgp_ctx *c, int T, const double *dxs, const double *dys, int include_noise,
                                       double *dpm, double *dpv, double *dl, void *hip_stream) {
-  if (!c || c->nwin < 1 || c->win_multi_p > 0) return CGP_ESTATE;   // (a single-target push would leave the other columns behind)
+  if (!c || c->nwin < 1 || c->wm.P > 0) return CGP_ESTATE;   // (a single-target push would leave the other columns behind)
   if (T < 1 || !dxs || !dys || !dpm || !dpv || !dl) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   return window_push_impl(c, T, dxs, dys, include_noise, dpm, dpv, dl, nullptr, pick_stream(c, hip_stream));
@@ -394,7 +459,7 @@ int window_push_impl(cgp_ctx *c, int T, const double *dxs, const double *dys, in
 
 extern "C" int cgp_window_push(cgp_ctx *c, int T, const double *xs, const double *ys, int include_noise, double *pm,
                                double *pv, double *logml) {
-  if (!c || c->nwin < 1 || c->win_multi_p > 0) return CGP_ESTATE;
+  if (!c || c->nwin < 1 || c->wm.P > 0) return CGP_ESTATE;
   if (T < 1 || !xs || !ys || !pm || !pv || !logml) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   // The per-tick host entry (configs[3] is "streamed per IMU tick": T = 1 is the common call): no allocation and no
@@ -462,10 +527,9 @@ extern "C" int cgp_window_predict_device(cgp_ctx *c, int M, const double *dxs, i
   // stream), so the launches are sized by the capacity N and need no host mirror.  The form depends on N alone.
   const ForecastForm form = forecast_form(a.N, false, k_is_matern(a.kernel_id));
   a.nchunk = cdiv(M, form.mc);
-  const long long total = (long long)c->nwin * a.nchunk;
-  if (total > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
+  unsigned grid;
+  if (xcd_grid((long long)c->nwin * a.nchunk, grid) != CGP_OK || !fits_grid(diag_inv_groups(c))) return CGP_EINVAL;
+  launch_diag_inv(c, ws);
   hipLaunchKernelGGL(form.kernel, dim3(grid), dim3(WF_THREADS), form.lds, ws, a);
   if (!hip_ok(c, hipGetLastError(), "window forecast launches")) return CGP_EHIP;
   return CGP_OK;
@@ -478,22 +542,14 @@ extern "C" int cgp_window_predict(cgp_ctx *c, int M, const double *xs, int inclu
   // staged like a push: one pinned block [xs | mean var | state] and its device twin; a small call is read and written in
   // place by the kernels (no copy command), a large one is one H2D and two D2H
   const size_t W = c->nwin, nx = W * M * c->win.d, ny = W * M;
-  const size_t ndbl = nx + 2 * ny, bytes = ndbl * 8 + W * 4 * sizeof(int);
-  double *h, *d;
-  if (!window_stage(c, bytes, ndbl * 8, h, d)) return CGP_ENOMEM;
-  int *hst = reinterpret_cast<int *>(h + ndbl);
-  memcpy(h, xs, nx * 8);
-  hipStream_t s = c->stream;
-  const bool inplace = bytes <= kWinZeroCopyBytes;
-  if (!inplace) HIP_TRY(c, hipMemcpyAsync(d, h, nx * 8, hipMemcpyHostToDevice, s));
-  double *io = inplace ? h : d;
-  int rc = cgp_window_predict_device(c, M, io, include_noise, io + nx, io + nx + ny, s);
-  if (rc != CGP_OK) return rc;
-  if (!inplace) HIP_TRY(c, hipMemcpyAsync(h + nx, d + nx, 2 * ny * 8, hipMemcpyDeviceToHost, s));
-  if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
+  double *h;
+  const int rc = window_staged_call(
+      c, nx, 2 * ny, 2 * ny, true, h, [&](double *hx) { memcpy(hx, xs, nx * 8); },
+      [&](double *io, hipStream_t s) { return cgp_window_predict_device(c, M, io, include_noise, io + nx, io + nx + ny, s); });
+  if (rc < 0) return rc;
   memcpy(mean, h + nx, ny * 8);
   memcpy(var, h + nx + ny, ny * 8);
-  return first_failing_tick(hst + 2, W, 4);
+  return rc;
 }
 
 // ---- predictive gradients from the windows as they stand (cgp_window_pgrad.hpp) --------------------------------------
@@ -512,11 +568,9 @@ extern "C" int cgp_window_predict_gradients_device(cgp_ctx *c, int M, const doub
   a.alpha = ad.alpha; a.gdmean = ddmean; a.gdvar = ddvar;
   const ForecastForm form = pgrad_win_form(a.N, k_is_matern(a.kernel_id));   // by N alone, as the forecast's
   a.nchunk = cdiv(M, form.mc);
-  const long long total = (long long)c->nwin * a.nchunk;
-  if (total > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
-  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, ad);
+  unsigned grid;
+  if (xcd_grid((long long)c->nwin * a.nchunk, grid) != CGP_OK || !fits_grid(diag_inv_groups(c))) return CGP_EINVAL;
+  launch_alpha(c, ad, ws);
   hipLaunchKernelGGL(form.kernel, dim3(grid), dim3(WF_THREADS), form.lds, ws, a);
   if (!hip_ok(c, hipGetLastError(), "window gradient forecast launches")) return CGP_EHIP;
   return CGP_OK;
@@ -529,36 +583,31 @@ extern "C" int cgp_window_predict_gradients(cgp_ctx *c, int M, const double *xs,
   HIP_TRY(c, hipSetDevice(c->device));
   // staged as cgp_window_predict: one pinned block [xs | mean var | dmean dvar | state] and its device twin
   const size_t W = c->nwin, nx = W * M * c->win.d, ny = W * M;
-  const size_t ndbl = 3 * nx + 2 * ny, bytes = ndbl * 8 + W * 4 * sizeof(int);
-  double *h, *d;
-  if (!window_stage(c, bytes, ndbl * 8, h, d)) return CGP_ENOMEM;
-  int *hst = reinterpret_cast<int *>(h + ndbl);
-  memcpy(h, xs, nx * 8);
-  hipStream_t s = c->stream;
-  const bool inplace = bytes <= kWinZeroCopyBytes;
-  if (!inplace) HIP_TRY(c, hipMemcpyAsync(d, h, nx * 8, hipMemcpyHostToDevice, s));
-  double *io = inplace ? h : d;
   const size_t om = nx, ov = nx + ny, odm = nx + 2 * ny, odv = 2 * nx + 2 * ny;
-  int rc = cgp_window_predict_gradients_device(c, M, io, include_noise, mean ? io + om : nullptr, var ? io + ov : nullptr,
-                                               dmean ? io + odm : nullptr, dvar ? io + odv : nullptr, s);
-  if (rc != CGP_OK) return rc;
-  if (!inplace) HIP_TRY(c, hipMemcpyAsync(h + nx, d + nx, (2 * ny + 2 * nx) * 8, hipMemcpyDeviceToHost, s));
-  if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
+  double *h;
+  const int rc = window_staged_call(c, nx, 2 * ny + 2 * nx, 2 * ny + 2 * nx, true, h, [&](double *hx) { memcpy(hx, xs, nx * 8); },
+                                    [&](double *io, hipStream_t s) {
+                                      return cgp_window_predict_gradients_device(c, M, io, include_noise, mean ? io + om : nullptr,
+                                                                                 var ? io + ov : nullptr, dmean ? io + odm : nullptr,
+                                                                                 dvar ? io + odv : nullptr, s);
+                                    });
+  if (rc < 0) return rc;
   if (mean) memcpy(mean, h + om, ny * 8);
   if (var) memcpy(var, h + ov, ny * 8);
   if (dmean) memcpy(dmean, h + odm, nx * 8);
   if (dvar) memcpy(dvar, h + odv, nx * 8);
-  return first_failing_tick(hst + 2, W, 4);
+  return rc;
 }
 
 // ---- multi-target windows: P target columns share the resident factor (cgp_window_multi.hpp) --------------------------
 namespace {
-// the checks the four multi-target calls start with, before anything is enqueued
-int window_multi_check(const cgp_ctx *c, int P, bool args_ok) {
+// the checks the multi-target calls start with, before anything is enqueued; objective: the calls that need
+// cgp_window_multi_grad_reserve's scratch as well
+int window_multi_check(const cgp_ctx *c, int P, bool args_ok, bool objective = false) {
   if (!c) return CGP_ESTATE;
   if (c->dtype != CGP_F64) return CGP_EINVAL;
-  if (c->nwin < 1 || c->win_multi_p < 1) return CGP_ESTATE;
-  if (P != c->win_multi_p || !args_ok) return CGP_EINVAL;
+  if (c->nwin < 1 || c->wm.P < 1 || (objective && !c->wg.am)) return CGP_ESTATE;
+  if (P != c->wm.P || !args_ok) return CGP_EINVAL;
   return CGP_OK;
 }
 }  // namespace
@@ -577,46 +626,22 @@ extern "C" int cgp_window_multi_reserve(cgp_ctx *c, int P) {
     for (size_t w = 0; w < W; ++w)
       if (st[w * 4 + 1] != 0 || st[w * 4 + 3] != 0) return CGP_ESTATE;
   }
-  // every instantiation a multi-target launch can pick gets its LDS limit, here only (the _device entry points make no attribute call)
+  // every instantiation a multi-target launch can pick gets its LDS limit (lds_limit on why here)
   const int N = c->win.N;
   const bool mat = k_is_matern(c->win.kernel_id);
   for (int n : kWinClassMaxN)
     for (bool z : {false, true})
-      if (hipFuncSetAttribute(reinterpret_cast<const void *>(multi_win_form(n, z, mat).kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kWinForecastLdsMax) != hipSuccess)
-        return CGP_EHIP;
-  auto drop = [&]() {
-    for (void *&b : c->wmbuf) {
-      if (b) (void)hipFree(b);
-      b = nullptr;
-    }
-    for (void *&b : c->wgbuf) {   // cgp_window_multi_grad_reserve's scratch was sized for the reservation that goes
-      if (b) (void)hipFree(b);
-      b = nullptr;
-    }
-    c->win_multi_p = 0;
-    c->win_multi_ticks = 0;
-  };
-  drop();
+      if (!lds_limit(multi_win_form(n, z, mat).kernel, kWinForecastLdsMax)) return CGP_EHIP;
+  window_drop(c, WinDrop::Multi);
   const size_t pt = cdiv(P, WPB), nrow = (size_t)cdiv(N, WPB) * WPB, ticks = std::max(N, 256);
-  const size_t sizes[4] = {W * P * N * 8, W * sizeof(int), W * pt * nrow * WPB * 8, W * ticks * 8};
-  for (int i = 0; i < 4; ++i)
-    if (hipMalloc(&c->wmbuf[i], sizes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      c->wmbuf[i] = nullptr;
-      drop();
-      return CGP_ENOMEM;
-    }
+  WinMultiBufs &b = c->wm;
   // (the Z scratch starts as zeros: the columns past P of the last target tile are never written and stay so)
-  if (!hip_ok(c, hipMemset(c->wmbuf[0], 0, sizes[0]), "window target store memset") ||
-      !hip_ok(c, hipMemset(c->wmbuf[1], 0, sizes[1]), "window target count memset") ||
-      !hip_ok(c, hipMemset(c->wmbuf[2], 0, sizes[2]), "window Z scratch memset") ||
-      !hip_ok(c, hipDeviceSynchronize(), "window multi reserve synchronise")) {   // (cgp_window_init on why: the fills are ordered on the legacy stream only)
-    drop();
-    return CGP_EHIP;
-  }
-  c->win_multi_p = P;
-  c->win_multi_ticks = ticks;
+  const WinSlot slots[] = {slot(b.ystore, W * P * N * 8, true), slot(b.ycount, W * sizeof(int), true),
+                           slot(b.zs, W * pt * nrow * WPB * 8, true), slot(b.y0, W * ticks * 8)};
+  if (window_alloc(c, WinDrop::Multi, slots) != CGP_OK) return CGP_ENOMEM;
+  if (window_zero(c, WinDrop::Multi, slots, "window multi reserve memsets / synchronise") != CGP_OK) return CGP_EHIP;
+  b.P = P;
+  b.ticks = ticks;
   return CGP_OK;
 }
 
@@ -626,21 +651,21 @@ extern "C" int cgp_window_push_multi_device(cgp_ctx *c, int T, int P, const doub
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t ws = pick_stream(c, hip_stream);
-  if ((size_t)T > c->win_multi_ticks) {   // a push longer than any before it: the gather block grows (an allocation; the free waits for the device)
+  if ((size_t)T > c->wm.ticks) {   // a push longer than any before it: the gather block grows (an allocation; the free waits for the device)
     void *nb = nullptr;
     if (hipMalloc(&nb, (size_t)c->nwin * T * 8) != hipSuccess) {
       (void)hipGetLastError();
       return CGP_ENOMEM;
     }
-    (void)hipFree(c->wmbuf[3]);
-    c->wmbuf[3] = nb;
-    c->win_multi_ticks = T;
+    (void)hipFree(c->wm.y0);
+    c->wm.y0 = static_cast<double *>(nb);
+    c->wm.ticks = T;
   }
   TargetStoreArgs s{};
   s.Ys = dYs;
-  s.ystore = static_cast<double *>(c->wmbuf[0]);
-  s.ycount = static_cast<int *>(c->wmbuf[1]);
-  s.y0 = static_cast<double *>(c->wmbuf[3]);
+  s.ystore = c->wm.ystore;
+  s.ycount = c->wm.ycount;
+  s.y0 = c->wm.y0;
   s.N = c->win.N; s.P = P; s.T = T;
   hipLaunchKernelGGL(k_window_targets_store, dim3(c->nwin), dim3(256), 0, ws, s);
   return window_push_impl(c, T, dxs, s.y0, include_noise, dpm, dpv, dl, nullptr, ws);
@@ -653,23 +678,22 @@ extern "C" int cgp_window_push_multi(cgp_ctx *c, int T, int P, const double *xs,
   HIP_TRY(c, hipSetDevice(c->device));
   // staged like a large cgp_window_push: one pinned block [xs | Ys | pm pv logml | state] and its device twin, one H2D, two D2H
   const size_t W = c->nwin, nx = W * T * c->win.d, ny = W * T, nY = ny * P;
-  const size_t ndbl = nx + nY + 3 * ny, bytes = ndbl * 8 + W * 4 * sizeof(int);
-  double *h, *d;
-  if (!window_stage(c, bytes, ndbl * 8, h, d)) return CGP_ENOMEM;
-  int *hst = reinterpret_cast<int *>(h + ndbl);
-  memcpy(h, xs, nx * 8);
-  memcpy(h + nx, Ys, nY * 8);
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(d, h, (nx + nY) * 8, hipMemcpyHostToDevice, s));
   const size_t oo = nx + nY;
-  rc = cgp_window_push_multi_device(c, T, P, d, d + nx, include_noise, d + oo, d + oo + ny, d + oo + 2 * ny, s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + oo, d + oo, 3 * ny * 8, hipMemcpyDeviceToHost, s));
-  if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
+  double *h;
+  rc = window_staged_call(
+      c, oo, 3 * ny, 3 * ny, false, h,
+      [&](double *hx) {
+        memcpy(hx, xs, nx * 8);
+        memcpy(hx + nx, Ys, nY * 8);
+      },
+      [&](double *io, hipStream_t s) {
+        return cgp_window_push_multi_device(c, T, P, io, io + nx, include_noise, io + oo, io + oo + ny, io + oo + 2 * ny, s);
+      });
+  if (rc < 0) return rc;
   memcpy(pm, h + oo, ny * 8);
   memcpy(pv, h + oo + ny, ny * 8);
   memcpy(logml, h + oo + 2 * ny, ny * 8);
-  return first_failing_tick(hst + 2, W, 4);
+  return rc;
 }
 
 // Three launches: the diagonal blocks' inverses, Z = L^-1 Y of the P columns into the scratch (with logml), the forecast whose
@@ -680,27 +704,21 @@ extern "C" int cgp_window_predict_multi_device(cgp_ctx *c, int M, int P, const d
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t ws = pick_stream(c, hip_stream);
-  ForecastArgs a = forecast_args(c);
-  a.include_noise = include_noise;
-  a.ystore = static_cast<const double *>(c->wmbuf[0]);
-  a.ycount = static_cast<const int *>(c->wmbuf[1]);
-  a.zs = static_cast<double *>(c->wmbuf[2]);
-  a.P = P;
-  a.pt = cdiv(P, WPB);
-  const bool matern = k_is_matern(a.kernel_id);
-  const ForecastForm zf = multi_win_form(a.N, true, matern), mf = multi_win_form(a.N, false, matern);   // by N alone, as the forecast's
-  ForecastArgs za = a;   // the targets take the test points' place
-  za.M = P;
-  za.nchunk = cdiv(P, zf.mc);
-  za.mlogml = dlogml;
+  const bool matern = k_is_matern(c->win.kernel_id);
+  const ForecastForm zf = multi_win_form(c->win.N, true, matern), mf = multi_win_form(c->win.N, false, matern);   // by N alone, as the forecast's
+  const ForecastArgs za = multi_z_args(c, zf, dlogml);
+  ForecastArgs a = za;   // the forecast proper: the test points back in their place, the Z scratch read
+  a.mlogml = nullptr;
   a.xs = dxs; a.mean = dmean; a.var = dvar;
-  a.M = M;
+  a.M = M; a.include_noise = include_noise;
   a.nchunk = cdiv(M, mf.mc);
-  const long long total = (long long)c->nwin * a.nchunk, ztotal = (long long)c->nwin * za.nchunk;
-  if (total > (1ll << 30) || ztotal > (1ll << 30) || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
-  hipLaunchKernelGGL(zf.kernel, dim3((unsigned)(cdiv((int)ztotal, WF_XCDS) * WF_XCDS)), dim3(WF_THREADS), zf.lds, ws, za);
-  hipLaunchKernelGGL(mf.kernel, dim3((unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS)), dim3(WF_THREADS), mf.lds, ws, a);
+  unsigned grid, zgrid;
+  if (xcd_grid((long long)c->nwin * a.nchunk, grid) != CGP_OK || xcd_grid((long long)c->nwin * za.nchunk, zgrid) != CGP_OK ||
+      !fits_grid(diag_inv_groups(c)))
+    return CGP_EINVAL;
+  launch_diag_inv(c, ws);
+  hipLaunchKernelGGL(zf.kernel, dim3(zgrid), dim3(WF_THREADS), zf.lds, ws, za);
+  hipLaunchKernelGGL(mf.kernel, dim3(grid), dim3(WF_THREADS), mf.lds, ws, a);
   if (!hip_ok(c, hipGetLastError(), "window multi-target forecast launches")) return CGP_EHIP;
   return CGP_OK;
 }
@@ -712,21 +730,17 @@ extern "C" int cgp_window_predict_multi(cgp_ctx *c, int M, int P, const double *
   HIP_TRY(c, hipSetDevice(c->device));
   // one pinned block [xs | mean | var | logml | state] and its device twin: one H2D, one D2H of the outputs, the state words
   const size_t W = c->nwin, nx = W * M * c->win.d, nm = W * P * M, nv = W * M, nl = W * P;
-  const size_t ndbl = nx + nm + nv + nl, bytes = ndbl * 8 + W * 4 * sizeof(int);
-  double *h, *d;
-  if (!window_stage(c, bytes, ndbl * 8, h, d)) return CGP_ENOMEM;
-  int *hst = reinterpret_cast<int *>(h + ndbl);
-  memcpy(h, xs, nx * 8);
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(d, h, nx * 8, hipMemcpyHostToDevice, s));
-  rc = cgp_window_predict_multi_device(c, M, P, d, include_noise, d + nx, d + nx + nm, logml ? d + nx + nm + nv : nullptr, s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h + nx, d + nx, (nm + nv + (logml ? nl : 0)) * 8, hipMemcpyDeviceToHost, s));
-  if ((rc = window_read_state(c, hst, s)) != CGP_OK) return rc;
+  double *h;
+  rc = window_staged_call(c, nx, nm + nv + nl, nm + nv + (logml ? nl : 0), false, h, [&](double *hx) { memcpy(hx, xs, nx * 8); },
+                          [&](double *io, hipStream_t s) {
+                            return cgp_window_predict_multi_device(c, M, P, io, include_noise, io + nx, io + nx + nm,
+                                                                   logml ? io + nx + nm + nv : nullptr, s);
+                          });
+  if (rc < 0) return rc;
   memcpy(mean, h + nx, nm * 8);
   memcpy(var, h + nx + nm, nv * 8);
   if (logml) memcpy(logml, h + nx + nm + nv, nl * 8);
-  return first_failing_tick(hst + 2, W, 4);
+  return rc;
 }
 
 // ---- joint forecast: full posterior covariance and sample paths (cgp_window_joint.hpp) -------------------------------
@@ -735,17 +749,13 @@ extern "C" int cgp_window_joint_reserve(cgp_ctx *c, int max_m) {
   if (max_m < 1 || max_m > 1024) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipDeviceSynchronize());   // an earlier joint forecast may still read the buffers that go
-  window_free(c, true);
+  window_drop(c, WinDrop::Joint);
   const size_t W = c->nwin, mpad = (size_t)cdiv(max_m, WPB) * WPB, nrow = (size_t)cdiv(c->win.N, WPB) * WPB;
-  const size_t sizes[4] = {W * nrow * mpad * 8, W * mpad * mpad * 8, 2 * W * (size_t)max_m * 8, W * sizeof(int)};
-  for (int i = 0; i < 4; ++i)
-    if (hipMalloc(&c->jointbuf[i], sizes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      c->jointbuf[i] = nullptr;
-      window_free(c, true);
-      return CGP_ENOMEM;
-    }
-  c->joint_max_m = max_m;
+  WinJointBufs &b = c->wj;
+  const WinSlot slots[] = {slot(b.V, W * nrow * mpad * 8), slot(b.C, W * mpad * mpad * 8), slot(b.mean_var, 2 * W * (size_t)max_m * 8),
+                           slot(b.jinfo, W * sizeof(int))};
+  if (window_alloc(c, WinDrop::Joint, slots) != CGP_OK) return CGP_ENOMEM;
+  b.max_m = max_m;
   return CGP_OK;
 }
 
@@ -757,14 +767,14 @@ unsigned joint_cov_grid(int M, int nunit, int &mt, int &nsup, int &npair, int &p
   nsup = cdiv(mt, WJ_ST);
   npair = nsup * (nsup + 1) / 2;
   per_unit = cdiv(npair, WJ_WAVES);
-  const long long total = (long long)nunit * per_unit;
-  return total > (1ll << 30) ? 0u : (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
+  unsigned grid;
+  return xcd_grid((long long)nunit * per_unit, grid) == CGP_OK ? grid : 0u;
 }
 // C C^T = scratch matrix + jitter I in place, then out = mean + C xi, for the nunit windows or fits whose buffers, M, mt and S j
 // names: the tail of every sampling route.  CGP_EINVAL (nothing enqueued) when the paths' grid would pass 2^30.
 int joint_chol_paths_launch(JointArgs &j, int nunit, hipStream_t s) {
   const long long per = ((long long)j.mt * cdiv(j.S, WPB) + WJ_WAVES - 1) / WJ_WAVES;   // one wave per 16 x 16 tile of the paths
-  if (per * nunit > (1ll << 30)) return CGP_EINVAL;
+  if (!fits_grid(per * nunit)) return CGP_EINVAL;
   j.per_win = (int)per;
   if (j.mt <= 4 * WA_WAVES) hipLaunchKernelGGL(k_window_joint_chol<4>, dim3(nunit), dim3(WA_THREADS), 0, s, j);
   else hipLaunchKernelGGL(k_window_joint_chol<8>, dim3(nunit), dim3(WA_THREADS), 0, s, j);
@@ -773,9 +783,9 @@ int joint_chol_paths_launch(JointArgs &j, int nunit, hipStream_t s) {
 }
 // the checks every window joint call starts with: windows and reservation, the arguments, the reservation's capacity
 int window_joint_check(const cgp_ctx *c, int M, bool args_ok) {
-  if (!c || c->nwin < 1 || c->joint_max_m < 1) return CGP_ESTATE;
+  if (!c || c->nwin < 1 || c->wj.max_m < 1) return CGP_ESTATE;
   if (M < 1 || !args_ok) return CGP_EINVAL;
-  if (M > c->joint_max_m) return CGP_ECAPACITY;
+  if (M > c->wj.max_m) return CGP_ECAPACITY;
   return CGP_OK;
 }
 
@@ -784,9 +794,9 @@ int window_joint_check(const cgp_ctx *c, int M, bool args_ok) {
 int window_joint_launch(cgp_ctx *c, int M, const double *dxs, int include_noise, double *dmean, double *dcov, JointArgs &j, hipStream_t ws) {
   ForecastArgs a = forecast_args(c);
   a.xs = dxs; a.mean = dmean;
-  a.var = static_cast<double *>(c->jointbuf[2]) + (size_t)c->nwin * c->joint_max_m;
+  a.var = c->wj.mean_var + (size_t)c->nwin * c->wj.max_m;
   a.M = M; a.include_noise = include_noise;
-  a.vkeep = static_cast<double *>(c->jointbuf[0]);
+  a.vkeep = c->wj.V;
   a.mt = cdiv(M, WPB);
   const ForecastForm form = forecast_form(a.N, true, k_is_matern(a.kernel_id));   // the forecast's forms, by N alone
   a.nchunk = cdiv(M, form.mc);
@@ -794,10 +804,9 @@ int window_joint_launch(cgp_ctx *c, int M, const double *dxs, int include_noise,
   j.xs = dxs; j.mean = dmean; j.var = a.var; j.cov = dcov;
   j.M = M;
   const unsigned jgrid = joint_cov_grid(M, c->nwin, j.mt, j.nsup, j.npair, j.per_win);
-  const long long total = (long long)c->nwin * a.nchunk;
-  if (total > (1ll << 30) || jgrid == 0 || (long long)cdiv(a.NB, 4) * c->nwin > (1ll << 30)) return CGP_EINVAL;
-  const unsigned grid = (unsigned)(cdiv((int)total, WF_XCDS) * WF_XCDS);
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, a);
+  unsigned grid;
+  if (xcd_grid((long long)c->nwin * a.nchunk, grid) != CGP_OK || jgrid == 0 || !fits_grid(diag_inv_groups(c))) return CGP_EINVAL;
+  launch_diag_inv(c, ws);
   hipLaunchKernelGGL(form.kernel, dim3(grid), dim3(WF_THREADS), form.lds, ws, a);
   if (dcov) hipLaunchKernelGGL(k_window_joint_cov<false>, dim3(jgrid), dim3(WJ_THREADS), 0, ws, j);
   else hipLaunchKernelGGL(k_window_joint_cov<true>, dim3(jgrid), dim3(WJ_THREADS), 0, ws, j);
@@ -824,7 +833,7 @@ extern "C" int cgp_window_sample_device(cgp_ctx *c, int M, const double *dxs, in
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t ws = pick_stream(c, hip_stream);
   JointArgs j;
-  rc = window_joint_launch(c, M, dxs, include_noise, static_cast<double *>(c->jointbuf[2]), nullptr, j, ws);
+  rc = window_joint_launch(c, M, dxs, include_noise, c->wj.mean_var, nullptr, j, ws);
   if (rc != CGP_OK) return rc;
   j.xi = dxi; j.out = dout; j.S = S; j.info = dinfo; j.jitter_rel = jitter_rel;
   if ((rc = joint_chol_paths_launch(j, c->nwin, ws)) != CGP_OK) return rc;
@@ -948,38 +957,50 @@ extern "C" int cgp_window_nll_grad_device(cgp_ctx *c, double *dnll, double *dgra
   hipStream_t ws = pick_stream(c, hip_stream);
   AdaptArgs a = adapt_args(c);
   a.nll = dnll; a.grad = dgrad; a.grad_stride = grad_stride;
-  const ForecastArgs f = forecast_args(c);   // k_window_diag_inv reads the windows and writes the inverses only
-  const long long chunks = (long long)c->nwin * a.NB;
-  if (chunks > (1ll << 30)) return CGP_EINVAL;
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, f);
-  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, a);
+  const long long chunks = window_chunks(c);
+  if (!fits_grid(chunks)) return CGP_EINVAL;
+  launch_alpha(c, a, ws);
   hipLaunchKernelGGL(k_window_kinv_grad, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a);
   hipLaunchKernelGGL(k_window_grad_finish, dim3((unsigned)cdiv(c->nwin, 64)), dim3(64), 0, ws, a);
   if (!hip_ok(c, hipGetLastError(), "window gradient launches")) return CGP_EHIP;
   return CGP_OK;
 }
 
-extern "C" int cgp_window_nll_grad(cgp_ctx *c, double *nll, double *grad, int grad_stride) {
-  if (!c || c->nwin < 1) return CGP_ESTATE;
-  const int nth = ntheta(c->win.kernel_id, c->win.d);
-  if (!nll || !grad || grad_stride < nth) return CGP_EINVAL;
+namespace {
+// The host form of the three objectives (cgp_window_nll_grad, _multi_nll_grad, _loo_nll_grad), after the call's own checks: one
+// device block [value | grad | nextra more doubles] and its pinned twin, `eval(dvalue, dgrad, grad_stride, dextra, stream)` -- the
+// objective's device form; dextra is null when the caller passed no `extra` --, one D2H, one synchronisation, the gradient
+// scattered by grad_stride.
+template <class Eval>
+int window_objective_host(cgp_ctx *c, double *value, double *grad, int grad_stride, double *extra, size_t nextra, Eval &&eval) {
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t W = c->nwin, ndbl = W * (1 + nth);
+  const int nth = ntheta(c->win.kernel_id, c->win.d);
+  const size_t W = c->nwin, ndbl = W * (1 + nth) + nextra;
   double *h, *d;
   if (!window_stage(c, ndbl * 8, ndbl * 8, h, d)) return CGP_ENOMEM;
   hipStream_t s = c->stream;
-  int rc = cgp_window_nll_grad_device(c, d, d + W, nth, s);
+  int rc = eval(d, d + W, nth, extra ? d + W * (1 + nth) : nullptr, s);
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(h, d, ndbl * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  memcpy(nll, h, W * sizeof(double));
+  memcpy(value, h, W * sizeof(double));
   for (size_t w = 0; w < W; ++w) memcpy(grad + w * grad_stride, h + W + w * nth, nth * sizeof(double));
+  if (extra) memcpy(extra, h + W * (1 + nth), nextra * sizeof(double));
   return CGP_OK;
+}
+}  // namespace
+
+extern "C" int cgp_window_nll_grad(cgp_ctx *c, double *nll, double *grad, int grad_stride) {
+  if (!c || c->nwin < 1) return CGP_ESTATE;
+  if (!nll || !grad || grad_stride < ntheta(c->win.kernel_id, c->win.d)) return CGP_EINVAL;
+  return window_objective_host(c, nll, grad, grad_stride, nullptr, 0, [&](double *dnll, double *dgrad, int stride, double *, hipStream_t s) {
+    return cgp_window_nll_grad_device(c, dnll, dgrad, stride, s);
+  });
 }
 
 // Leave-one-out cross-validation of the windows as they stand (cgp_window_loo.hpp): the gradient's first two launches, then the
 // forward half of its substitution and the finish.  Alpha and the chunks' partial sums live where the gradient keeps alpha and
-// its partial sums (winbuf[7]: one double per chunk against the gradient's GRAD_N).
+// its partial sums (WinBufs::grad_scratch: one double per chunk against the gradient's GRAD_N).
 extern "C" int cgp_window_loo_device(cgp_ctx *c, double *dloo_mean, double *dloo_var, double *dloo_lpd, double *dlpd_sum,
                                      void *hip_stream) {
   if (!c || c->nwin < 1) return CGP_ESTATE;
@@ -988,13 +1009,8 @@ extern "C" int cgp_window_loo_device(cgp_ctx *c, double *dloo_mean, double *dloo
   hipStream_t ws = pick_stream(c, hip_stream);
   const AdaptArgs a = adapt_args(c);
   const WindowLooOut out{dloo_mean, dloo_var, dloo_lpd, dlpd_sum, a.gpart};
-  const ForecastArgs f = forecast_args(c);   // k_window_diag_inv reads the windows and writes the inverses only
-  const long long chunks = (long long)c->nwin * a.NB;
-  if (chunks > (1ll << 30)) return CGP_EINVAL;
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, f);
-  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, a);
-  hipLaunchKernelGGL(k_window_loo, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a, out);
-  hipLaunchKernelGGL(k_window_loo_finish, dim3(c->nwin), dim3(64), 0, ws, a, out);
+  if (!fits_grid(window_chunks(c))) return CGP_EINVAL;
+  launch_loo(c, a, out, ws);
   if (!hip_ok(c, hipGetLastError(), "window LOO launches")) return CGP_EHIP;
   return CGP_OK;
 }
@@ -1103,74 +1119,38 @@ extern "C" int cgp_window_optimize(cgp_ctx *c, int max_evals, const unsigned cha
 }
 
 // ---- multi-target windows: value, gradient and optimiser of the P columns' summed logML (cgp_window_multi_grad.hpp) ----
-namespace {
-// the checks the multi-target objective's calls start with, before anything is enqueued
-int window_multi_grad_check(const cgp_ctx *c, int P, bool args_ok) {
-  if (!c) return CGP_ESTATE;
-  if (c->dtype != CGP_F64) return CGP_EINVAL;
-  if (c->nwin < 1 || c->win_multi_p < 1 || !c->wgbuf[0] || !c->wgbuf[1]) return CGP_ESTATE;
-  if (P != c->win_multi_p || !args_ok) return CGP_EINVAL;
-  return CGP_OK;
-}
-}  // namespace
-
 extern "C" int cgp_window_multi_grad_reserve(cgp_ctx *c) {
   if (!c) return CGP_ESTATE;
   if (c->dtype != CGP_F64) return CGP_EINVAL;
-  if (c->nwin < 1 || c->win_multi_p < 1) return CGP_ESTATE;
+  if (c->nwin < 1 || c->wm.P < 1) return CGP_ESTATE;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipDeviceSynchronize());   // an earlier reservation's buffers are idle
-  auto drop = [&]() {
-    for (void *&b : c->wgbuf) {
-      if (b) (void)hipFree(b);
-      b = nullptr;
-    }
-  };
-  drop();
-  const size_t W = c->nwin, P = c->win_multi_p, pt = cdiv(c->win_multi_p, WPB), nrow = (size_t)cdiv(c->win.N, WPB) * WPB;
-  const size_t sizes[2] = {W * pt * nrow * WPB * 8, W * P * 8};
-  for (int i = 0; i < 2; ++i)
-    if (hipMalloc(&c->wgbuf[i], sizes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      c->wgbuf[i] = nullptr;
-      drop();
-      return CGP_ENOMEM;
-    }
-  if (!hip_ok(c, hipMemset(c->wgbuf[0], 0, sizes[0]), "window A scratch memset") ||
-      !hip_ok(c, hipMemset(c->wgbuf[1], 0, sizes[1]), "window column values memset") ||
-      !hip_ok(c, hipDeviceSynchronize(), "window multi grad reserve synchronise")) {   // (cgp_window_init on why)
-    drop();
-    return CGP_EHIP;
-  }
-  return CGP_OK;
+  window_drop(c, WinDrop::MultiGrad);
+  const size_t W = c->nwin, P = c->wm.P, pt = cdiv(c->wm.P, WPB), nrow = (size_t)cdiv(c->win.N, WPB) * WPB;
+  const WinSlot slots[] = {slot(c->wg.am, W * pt * nrow * WPB * 8, true), slot(c->wg.colval, W * P * 8, true)};
+  if (window_alloc(c, WinDrop::MultiGrad, slots) != CGP_OK) return CGP_ENOMEM;
+  return window_zero(c, WinDrop::MultiGrad, slots, "window multi grad reserve memsets / synchronise");
 }
 
 // Five launches: the diagonal blocks' inverses, Z = L^-1 Y with the columns' logml (cgp_window_predict_multi's second launch), A =
 // L^-T Z, the contraction with dK/dtheta, the finish.  Sized by the capacity N; origin, size and tick count are read on the device.
 extern "C" int cgp_window_multi_nll_grad_device(cgp_ctx *c, int P, double *dnll, double *dgrad, int grad_stride, double *dlogml,
                                                 void *hip_stream) {
-  int rc = window_multi_grad_check(c, P, c && dnll && dgrad && grad_stride >= ntheta(c->win.kernel_id, c->win.d));
+  int rc = window_multi_check(c, P, c && dnll && dgrad && grad_stride >= ntheta(c->win.kernel_id, c->win.d), true);
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t ws = pick_stream(c, hip_stream);
   AdaptArgs a = adapt_args(c);
   a.nll = dnll; a.grad = dgrad; a.grad_stride = grad_stride;
-  double *lm = dlogml ? dlogml : static_cast<double *>(c->wgbuf[1]);   // the value is read from it by the finish
+  double *lm = dlogml ? dlogml : c->wg.colval;   // the value is read from it by the finish
   a.mlogml = lm;
-  ForecastArgs za = forecast_args(c);   // the targets take the test points' place (cgp_window_predict_multi_device)
-  za.ystore = static_cast<const double *>(c->wmbuf[0]);
-  za.ycount = static_cast<const int *>(c->wmbuf[1]);
-  za.zs = static_cast<double *>(c->wmbuf[2]);
-  za.P = P;
-  za.pt = a.pt;
   const ForecastForm zf = multi_win_form(a.N, true, k_is_matern(a.kernel_id));   // by N alone
-  za.M = P;
-  za.nchunk = cdiv(P, zf.mc);
-  za.mlogml = lm;
-  const long long chunks = (long long)c->nwin * a.NB, ztotal = (long long)c->nwin * za.nchunk, tiles = (long long)c->nwin * a.pt;
-  if (chunks > (1ll << 30) || ztotal > (1ll << 30) || tiles > (1ll << 30)) return CGP_EINVAL;
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, za);
-  hipLaunchKernelGGL(zf.kernel, dim3((unsigned)(cdiv((int)ztotal, WF_XCDS) * WF_XCDS)), dim3(WF_THREADS), zf.lds, ws, za);
+  const ForecastArgs za = multi_z_args(c, zf, lm);   // cgp_window_predict_multi_device's second launch
+  const long long chunks = window_chunks(c), tiles = (long long)c->nwin * a.pt;
+  unsigned zgrid;
+  if (!fits_grid(chunks) || xcd_grid((long long)c->nwin * za.nchunk, zgrid) != CGP_OK || !fits_grid(tiles)) return CGP_EINVAL;
+  launch_diag_inv(c, ws);
+  hipLaunchKernelGGL(zf.kernel, dim3(zgrid), dim3(WF_THREADS), zf.lds, ws, za);
   hipLaunchKernelGGL(k_window_multi_alpha, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, ws, a);
   hipLaunchKernelGGL(k_window_multi_kinv_grad, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a);
   hipLaunchKernelGGL(k_window_multi_grad_finish, dim3((unsigned)cdiv(c->nwin, 64)), dim3(64), 0, ws, a);
@@ -1179,29 +1159,18 @@ extern "C" int cgp_window_multi_nll_grad_device(cgp_ctx *c, int P, double *dnll,
 }
 
 extern "C" int cgp_window_multi_nll_grad(cgp_ctx *c, int P, double *nll, double *grad, int grad_stride, double *logml) {
-  int rc = window_multi_grad_check(c, P, c && nll && grad && grad_stride >= ntheta(c->win.kernel_id, c->win.d));
+  int rc = window_multi_check(c, P, c && nll && grad && grad_stride >= ntheta(c->win.kernel_id, c->win.d), true);
   if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // one device block [nll | grad | logml] and its pinned twin: the launches, one D2H, one synchronisation
-  const int nth = ntheta(c->win.kernel_id, c->win.d);
-  const size_t W = c->nwin, nl = logml ? W * P : 0, ndbl = W * (1 + nth) + nl;
-  double *h, *d;
-  if (!window_stage(c, ndbl * 8, ndbl * 8, h, d)) return CGP_ENOMEM;
-  hipStream_t s = c->stream;
-  rc = cgp_window_multi_nll_grad_device(c, P, d, d + W, nth, logml ? d + W * (1 + nth) : nullptr, s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h, d, ndbl * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  memcpy(nll, h, W * sizeof(double));
-  for (size_t w = 0; w < W; ++w) memcpy(grad + w * grad_stride, h + W + w * nth, nth * sizeof(double));
-  if (logml) memcpy(logml, h + W * (1 + nth), nl * sizeof(double));
-  return CGP_OK;
+  return window_objective_host(c, nll, grad, grad_stride, logml, logml ? (size_t)c->nwin * P : 0,   // [nll | grad | logml], the last only when asked for
+                               [&](double *dnll, double *dgrad, int stride, double *dlogml, hipStream_t s) {
+                                 return cgp_window_multi_nll_grad_device(c, P, dnll, dgrad, stride, dlogml, s);
+                               });
 }
 
 // cgp_window_optimize with the summed objective: the same driver and the same round, the evaluation above in cgp_window_nll_grad_device's place.
 extern "C" int cgp_window_optimize_multi(cgp_ctx *c, int P, int max_evals, const unsigned char *select, double *theta_out,
                                          int theta_stride, double *logml_sum_out, int *n_evals) {
-  int rc = window_multi_grad_check(c, P, true);
+  int rc = window_multi_check(c, P, true, true);
   if (rc != CGP_OK) return rc;
   return window_optimize_impl(c, max_evals, select, theta_out, theta_stride, logml_sum_out, n_evals,
                               [&](double *dnll, double *dgrad, int stride, hipStream_t s) {
@@ -1233,7 +1202,7 @@ WindowLooGradPlan window_loo_grad_plan(const cgp_ctx *c) {
 }
 // the checks the objective's calls start with, before anything is enqueued
 int window_loo_grad_check(const cgp_ctx *c, bool args_ok) {
-  if (!c || c->nwin < 1 || !c->wlbuf[0] || !c->wlbuf[1]) return CGP_ESTATE;
+  if (!c || c->nwin < 1 || !c->wl.kinv) return CGP_ESTATE;
   return args_ok ? CGP_OK : CGP_EINVAL;
 }
 }  // namespace
@@ -1242,29 +1211,12 @@ extern "C" int cgp_window_loo_grad_reserve(cgp_ctx *c) {
   if (!c || c->nwin < 1) return CGP_ESTATE;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipDeviceSynchronize());   // an earlier reservation's buffers are idle
-  auto drop = [&]() {
-    for (void *&b : c->wlbuf) {
-      if (b) (void)hipFree(b);
-      b = nullptr;
-    }
-  };
-  drop();
+  window_drop(c, WinDrop::LooGrad);
   const WindowLooGradPlan q = window_loo_grad_plan(c);
-  const size_t sizes[2] = {(size_t)c->nwin * q.NP * q.NP * 8, q.ndbl * 8};
-  for (int i = 0; i < 2; ++i)
-    if (hipMalloc(&c->wlbuf[i], sizes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      c->wlbuf[i] = nullptr;
-      drop();
-      return CGP_ENOMEM;
-    }
   // no memset of Ky^-1: every reader masks what the call itself did not write (cgp_window_loo_grad.hpp)
-  if (!hip_ok(c, hipMemset(c->wlbuf[1], 0, sizes[1]), "window LOO gradient scratch memset") ||
-      !hip_ok(c, hipDeviceSynchronize(), "window LOO gradient reserve synchronise")) {   // (cgp_window_init on why)
-    drop();
-    return CGP_EHIP;
-  }
-  return CGP_OK;
+  const WinSlot slots[] = {slot(c->wl.kinv, (size_t)c->nwin * q.NP * q.NP * 8), slot(c->wl.blk, q.ndbl * 8, true)};
+  if (window_alloc(c, WinDrop::LooGrad, slots) != CGP_OK) return CGP_ENOMEM;
+  return window_zero(c, WinDrop::LooGrad, slots, "window LOO gradient reserve memset / synchronise");
 }
 
 // Nine launches: cgp_window_loo_device's four as they stand (loo_var and lpd_sum into the reservation), then c and b, Ky^-1,
@@ -1278,25 +1230,22 @@ extern "C" int cgp_window_loo_nll_grad_device(cgp_ctx *c, double *dnlpd, double 
   AdaptArgs a = adapt_args(c);
   a.grad = dgrad; a.grad_stride = grad_stride;
   const WindowLooGradPlan q = window_loo_grad_plan(c);
-  double *blk = static_cast<double *>(c->wlbuf[1]);
+  double *blk = c->wl.blk;
   const WindowLooOut out{nullptr, blk, nullptr, blk + q.o_sum, blk + q.o_part};
   WindowLooGradArgs g{};
-  g.kinv = static_cast<double *>(c->wlbuf[0]);
+  g.kinv = c->wl.kinv;
   g.var = blk; g.lsum = blk + q.o_sum;
   g.cv = blk + q.o_c; g.bv = blk + q.o_b; g.beta = blk + q.o_beta; g.part = blk + q.o_gpart;
   g.nlpd = dnlpd; g.logml = dlogml;
   g.NP = (int)q.NP; g.npair = (int)q.npair; g.per_win = cdiv((int)q.npair, WJ_WAVES);
-  const ForecastArgs f = forecast_args(c);   // k_window_diag_inv reads the windows and writes the inverses only
-  const long long chunks = (long long)c->nwin * a.NB, units = (long long)c->nwin * g.per_win;
-  if (chunks > (1ll << 30) || units > (1ll << 30) || c->nwin > 65535) return CGP_EINVAL;
-  hipLaunchKernelGGL(k_window_diag_inv, dim3((unsigned)(cdiv(a.NB, 4) * c->nwin)), dim3(64), 0, ws, f);
-  hipLaunchKernelGGL(k_window_alpha, dim3(c->nwin), dim3(256), (size_t)a.NB * WPB * sizeof(double), ws, a);
-  hipLaunchKernelGGL(k_window_loo, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a, out);
-  hipLaunchKernelGGL(k_window_loo_finish, dim3(c->nwin), dim3(64), 0, ws, a, out);
+  const long long chunks = window_chunks(c);
+  unsigned ggrid;
+  if (!fits_grid(chunks) || xcd_grid((long long)c->nwin * g.per_win, ggrid) != CGP_OK || c->nwin > 65535) return CGP_EINVAL;   // (nwin is a grid.y below)
+  launch_loo(c, a, out, ws);
   hipLaunchKernelGGL(k_window_loo_prep, dim3((unsigned)cdiv(g.NP, 256), c->nwin), dim3(256), 0, ws, a, g);
   hipLaunchKernelGGL(k_window_loo_kinv, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, ws, a, g);
   hipLaunchKernelGGL(k_window_loo_beta, dim3((unsigned)(g.NP / WLG_EB), c->nwin), dim3(WLG_WAVES * 64), 0, ws, a, g);
-  hipLaunchKernelGGL(k_window_loo_grad, dim3((unsigned)(cdiv((int)units, WF_XCDS) * WF_XCDS)), dim3(WJ_THREADS), 0, ws, a, g);
+  hipLaunchKernelGGL(k_window_loo_grad, dim3(ggrid), dim3(WJ_THREADS), 0, ws, a, g);
   hipLaunchKernelGGL(k_window_loo_grad_finish, dim3((unsigned)cdiv(c->nwin, 64)), dim3(64), 0, ws, a, g);
   if (!hip_ok(c, hipGetLastError(), "window LOO gradient launches")) return CGP_EHIP;
   return CGP_OK;
@@ -1305,21 +1254,10 @@ extern "C" int cgp_window_loo_nll_grad_device(cgp_ctx *c, double *dnlpd, double 
 extern "C" int cgp_window_loo_nll_grad(cgp_ctx *c, double *nlpd, double *grad, int grad_stride, double *logml) {
   int rc = window_loo_grad_check(c, c && c->nwin >= 1 && nlpd && grad && grad_stride >= ntheta(c->win.kernel_id, c->win.d));
   if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  // one device block [nlpd | grad | logml] and its pinned twin: the launches, one D2H, one synchronisation
-  const int nth = ntheta(c->win.kernel_id, c->win.d);
-  const size_t W = c->nwin, ndbl = W * (2 + nth);
-  double *h, *d;
-  if (!window_stage(c, ndbl * 8, ndbl * 8, h, d)) return CGP_ENOMEM;
-  hipStream_t s = c->stream;
-  rc = cgp_window_loo_nll_grad_device(c, d, d + W, nth, logml ? d + W * (1 + nth) : nullptr, s);
-  if (rc != CGP_OK) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h, d, ndbl * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  memcpy(nlpd, h, W * sizeof(double));
-  for (size_t w = 0; w < W; ++w) memcpy(grad + w * grad_stride, h + W + w * nth, nth * sizeof(double));
-  if (logml) memcpy(logml, h + W * (1 + nth), W * sizeof(double));
-  return CGP_OK;
+  return window_objective_host(c, nlpd, grad, grad_stride, logml, c->nwin,   // [nlpd | grad | logml], the last staged whether asked for or not
+                               [&](double *dnlpd, double *dgrad, int stride, double *dlogml, hipStream_t s) {
+                                 return cgp_window_loo_nll_grad_device(c, dnlpd, dgrad, stride, dlogml, s);
+                               });
 }
 
 // cgp_window_optimize with the leave-one-out objective: the same driver and the same round, the evaluation above in

@@ -384,3 +384,77 @@ def test_failure_code_is_the_same_in_place_by_copy_and_polled(engine, tick):
     def single(plan):
         assert plan == [(P.PLAN_TICKS, 512, 0, 1)], plan
     run_failure(engine, kid, nwin, N, d, victim, pre + tl, 1, 0, single, 3200 + tick)
+
+
+# ---- lifetimes of the windows' four reservations --------------------------------------------------------------------------------
+EINVAL, ESTATE = -1, -4   # include/corenav_gp.h
+
+
+def test_reservation_lifetimes_across_init_and_reserve(engine):
+    """The lifetime rules of the windows' reservations, walked in one context: a new cgp_window_init drops all four (multi-target,
+    its objective, joint forecast, leave-one-out objective), a new cgp_window_multi_reserve drops the multi-target objective's
+    scratch with it and nothing else, and what is reserved afterwards holds nothing of what was dropped.  Two windows of
+    capacity 33 (two blocks of 16 and a one-row tail), d = 1, SE kernel, P = 2, joint max_m = 4.  A family is probed at the
+    argument-check level: with its reservation a call with a bad argument answers CGP_EINVAL, without it CGP_ESTATE (the state
+    is checked first)."""
+    W, N, d, kid, P, M, T = 2, 33, 1, 0, 2, 4, 5
+    rng = np.random.default_rng(33)
+    theta = np.tile([0.9, 1.3, 0.05], (W, 1))
+    X = np.cumsum(rng.uniform(0.2, 0.6, (W, T, d)), axis=1)
+    Y = np.sin(X) + 0.1 * rng.normal(size=(W, T, P))
+    Xs = X[:, -1:, :] + 0.3 * np.arange(1, M + 1)[None, :, None]
+    buf = np.zeros(64)
+    p, a = engine._p(buf), buf.ctypes.data
+
+    def reserve_all(c):
+        assert c.window_multi_reserve(P) == 0 and c.window_multi_grad_reserve() == 0
+        assert c.window_joint_reserve(M) == 0 and c.window_loo_grad_reserve() == 0
+
+    def families(c):
+        lib, h = c.lib, c.h
+        return {"multi": (lib.cgp_window_predict_multi(h, 0, P, p, 1, p, p, p), lib.cgp_window_push_multi(h, 0, P, p, p, 1, p, p, p)),
+                "multi_grad": (lib.cgp_window_multi_nll_grad(h, P, None, p, 4, p), lib.cgp_window_multi_nll_grad_device(h, P, None, a, 4, a, None),
+                               lib.cgp_window_optimize_multi(h, P, 10, None, p, 2, None, None)),
+                "joint": (lib.cgp_window_predict_cov(h, 0, p, 1, p, p), lib.cgp_window_sample(h, 0, p, 1, p, 1, 1e-6, p, None)),
+                "loo_grad": (lib.cgp_window_loo_nll_grad(h, None, p, 4, p), lib.cgp_window_loo_nll_grad_device(h, None, a, 4, a, None),
+                             lib.cgp_window_optimize_loo(h, 10, None, p, 2, None, None))}
+
+    def held(c):
+        out = {}
+        for name, codes in families(c).items():
+            assert all(rc == codes[0] for rc in codes) and codes[0] in (EINVAL, ESTATE), (name, codes)
+            out[name] = codes[0] == EINVAL
+        return out
+
+    def one_round(c):
+        out = list(c.window_push_multi(X, Y)) + list(c.window_multi_nll_grad()) + list(c.window_loo_nll_grad())
+        return out + list(c.window_predict_cov(Xs))
+
+    every, none = dict(multi=True, multi_grad=True, joint=True, loo_grad=True), dict(multi=False, multi_grad=False, joint=False, loo_grad=False)
+    ctx = engine.Context(max_n=8, max_m=8, max_d=d)
+    assert held(ctx) == none   # no windows
+    ctx.window_init(W, N, d, kid, theta)
+    assert held(ctx) == none
+    reserve_all(ctx)
+    assert held(ctx) == every
+    # the multi-target reservation made again (windows still empty): its objective's scratch goes with it, the other two stay
+    assert ctx.window_multi_reserve(P) == 0
+    assert held(ctx) == dict(every, multi_grad=False)
+    assert ctx.window_multi_grad_reserve() == 0 and held(ctx) == every
+    # the joint and the leave-one-out reservations made again: each goes alone
+    assert ctx.window_joint_reserve(M) == 0 and ctx.window_loo_grad_reserve() == 0 and held(ctx) == every
+    # new windows: every reservation goes
+    ctx.window_init(W, N, d, kid, theta)
+    assert held(ctx) == none
+    reserve_all(ctx)
+    assert held(ctx) == every
+    got = one_round(ctx)
+    fresh = engine.Context(max_n=8, max_m=8, max_d=d)
+    fresh.window_init(W, N, d, kid, theta)
+    reserve_all(fresh)
+    want = one_round(fresh)
+    assert len(got) == len(want) == 11
+    for u, v in zip(got, want):
+        assert np.all(np.isfinite(u)) and np.array_equal(u, v)
+    ctx.close()
+    fresh.close()

@@ -4,6 +4,7 @@
     CGP_LIB=<library A> python tools/window_joint_ab.py run a.npz
     CGP_LIB=<library B> python tools/window_joint_ab.py run b.npz
     python tools/window_joint_ab.py compare a.npz b.npz [verdict.txt]
+    CGP_LIB=<library> python tools/window_joint_ab.py run-windows-once a.npz     (the window calls at one shape: for a kernel trace)
 
 `run` sends a fixed list of calls through the library that CGP_LIB names (one process per library) and saves every output;
 `compare` is tools/grad_path_ab.py's: one line per call, equal (np.array_equal, NaNs in equal places) or the largest difference
@@ -19,7 +20,11 @@ in ulps, non-zero exit when any call differs.  Shapes are the smallest that reac
                window failed by a theta of negative noise (a push feeds every window of the context, so no window can stay
                empty beside filled ones: the empty state is all three windows before the first push, which takes the same
                n <= 0 branches); capacity 528 and 1040 (k_window_refactor<8> and <16>); one sample
-               call at M = 520 (k_window_joint_chol<8>)"""
+               call at M = 520 (k_window_joint_chol<8>)
+  window host  every entry point of the windows' host layer, host and device form, over the same four states at capacity 33 and
+               64: the pushes (T = 1, N / 2, N + 5), forecasts and predictive gradients at M = 1 / 20 / 70, the leave-one-out
+               objective with and without logml, the three optimisers at 12 evaluations, the multi-target family at P = 1 / 17;
+               one push and one forecast staged by copy (above 16 KiB) at capacity 528 (window_host_calls)"""
 import os
 import sys
 
@@ -175,10 +180,10 @@ def window_round(ctx, out, tag, Xs, xi, theta):
     out[f"window_loo after set_theta {tag}"] = flat(*ctx.window_loo())
 
 
-def window_calls(engine, out):
+def window_calls(engine, out, sizes=(33, 64), kinds=((0, 1), (0, 3), (2, 1), (4, 1), (4, 3)), long_windows=True):
     W, S = 3, 3
-    for N in (33, 64):
-        for kid, d in ((0, 1), (0, 3), (2, 1), (4, 1), (4, 3)):
+    for N in sizes:
+        for kid, d in kinds:
             M = 70 if N == 33 else 20
             T = N + 5
             Xw, Yw = zip(*[window(T, d, 10 * kid + N + d + w, kid) for w in range(W)])
@@ -203,6 +208,8 @@ def window_calls(engine, out):
             assert ctx.window_state(1)[1] != 0 and ctx.window_state(0)[1] == 0
             ctx.close()
 
+    if not long_windows:
+        return
     # the 8 and 16 tiles-per-wave factorisations of k_window_refactor, SE-ARD and Matern 5/2
     d, M = 2, 20
     for N, T in ((528, 600), (1040, 1100)):
@@ -231,23 +238,166 @@ def window_calls(engine, out):
     ctx.close()
 
 
-def run(out_path):
+def window_host_calls(engine, out, sizes=(33, 64), kinds=((0, 1), (0, 3), (2, 1), (4, 1), (4, 3))):
+    """Every window entry point of the host layer, host and device form, over the states of window_calls (empty, filling, origin
+    moved, window 1 failed) at capacity 33 and 64: the pushes themselves (T = 1, N / 2, N + 5: the ring wraps), forecasts and
+    predictive gradients at M = 1 / 20 / 70, the leave-one-out objective with and without logml, the optimisers capped at 12
+    evaluations; on contexts of their own the multi-target family at P = 1 and 17 (two target tiles).  Then one push and one
+    forecast of a capacity-528 window whose staged blocks pass 16 KiB (copied, not read in place)."""
+    import torch
+    W, S, EV = 3, 3, 12
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    def zeros(*shape, dtype=torch.float64):
+        return torch.zeros(shape, dtype=dtype, device="cuda")
+
+    def host(*ts):
+        torch.cuda.synchronize()
+        return flat(*[t.cpu().numpy() for t in ts])
+
+    def guarded(f):   # a call that may be refused (the optimisers on a window whose theta is not positive)
+        try:
+            return flat(*[x for x in f() if x is not None])
+        except engine.CgpError as e:
+            return flat(e.code)
+
+    def single_round(ctx, tag, Xs, xi, N, d, select):
+        nth = ctx._win_nth
+        for M in (1, 20, 70):
+            xs = Xs[:, :M]
+            out[f"window_predict {tag} M{M}"] = flat(*ctx.window_predict(xs, check=False))
+            out[f"window_predict_gradients {tag} M{M}"] = flat(*ctx.window_predict_gradients(xs, check=False))
+            out[f"window_predict_gradients dvar only {tag} M{M}"] = guarded(
+                lambda: ctx.window_predict_gradients(xs, check=False, want=("dvar",), moments=()))
+            dxs, m, v, gm, gv = dev(xs), zeros(W, M), zeros(W, M), zeros(W, M, d), zeros(W, M, d)
+            assert ctx.window_predict_device(M, dxs.data_ptr(), True, m.data_ptr(), v.data_ptr()) == 0
+            out[f"window_predict_device {tag} M{M}"] = host(m, v)
+            assert ctx.window_predict_gradients_device(M, dxs.data_ptr(), False, m.data_ptr(), v.data_ptr(), gm.data_ptr(), gv.data_ptr()) == 0
+            out[f"window_predict_gradients_device {tag} M{M}"] = host(m, v, gm, gv)
+        M = 20
+        dxs, dxi, m, cov, paths, info = dev(Xs[:, :M]), dev(xi[:, :, :M]), zeros(W, M), zeros(W, M, M), zeros(W, S, M), zeros(W, dtype=torch.int32)
+        assert ctx.window_predict_cov_device(M, dxs.data_ptr(), True, m.data_ptr(), cov.data_ptr()) == 0
+        assert ctx.window_sample_device(M, dxs.data_ptr(), S, dxi.data_ptr(), True, 1e-6, paths.data_ptr(), info.data_ptr()) == 0
+        out[f"window_predict_cov_device window_sample_device {tag}"] = host(m, cov, paths, info)
+        val, grad, lm = zeros(W), zeros(W, nth), zeros(W)
+        for want in (True, False):
+            out[f"window_loo_nll_grad logml {want} {tag}"] = guarded(lambda: ctx.window_loo_nll_grad(want_logml=want))
+            assert ctx.window_loo_nll_grad_device(val.data_ptr(), grad.data_ptr(), nth, lm.data_ptr() if want else 0) == 0
+            out[f"window_loo_nll_grad_device logml {want} {tag}"] = host(val, grad, lm)
+        assert ctx.window_nll_grad_device(val.data_ptr(), grad.data_ptr(), nth) == 0
+        out[f"window_nll_grad_device {tag}"] = host(val, grad)
+        lo = [zeros(W, N) for _ in range(3)]
+        assert ctx.window_loo_device(*[t.data_ptr() for t in lo], val.data_ptr()) == 0
+        out[f"window_loo_device {tag}"] = host(*lo, val)
+        out[f"window_optimize {tag}"] = guarded(lambda: ctx.window_optimize(max_evals=EV, select=select))
+        out[f"window_optimize_loo {tag}"] = guarded(lambda: ctx.window_optimize_loo(max_evals=EV, select=select))
+
+    def multi_round(ctx, tag, Xs, P, d, select):
+        nth = ctx._win_nth
+        for M in (1, 20):
+            xs = Xs[:, :M]
+            for want in (True, False):
+                out[f"window_predict_multi logml {want} {tag} M{M}"] = guarded(lambda: ctx.window_predict_multi(xs, check=False, want_logml=want))
+            dxs, m, v, lm = dev(xs), zeros(W, P, M), zeros(W, M), zeros(W, P)
+            assert ctx.window_predict_multi_device(M, P, dxs.data_ptr(), False, m.data_ptr(), v.data_ptr(), lm.data_ptr()) == 0
+            out[f"window_predict_multi_device {tag} M{M}"] = host(m, v, lm)
+        val, grad, lm = zeros(W), zeros(W, nth), zeros(W, P)
+        for want in (True, False):
+            out[f"window_multi_nll_grad logml {want} {tag}"] = guarded(lambda: ctx.window_multi_nll_grad(want_logml=want))
+            assert ctx.window_multi_nll_grad_device(P, val.data_ptr(), grad.data_ptr(), nth, lm.data_ptr() if want else 0) == 0
+            out[f"window_multi_nll_grad_device logml {want} {tag}"] = host(val, grad, lm)
+        out[f"window_optimize_multi {tag}"] = guarded(lambda: ctx.window_optimize_multi(max_evals=EV, select=select))
+
+    def push_device(ctx, X, Y, P):   # (W, T, d), (W, T, P): the device form of the push, single-target when P is 0
+        T = X.shape[1]
+        dx, dy, pm, pv, lm = dev(X), dev(Y), zeros(W, T), zeros(W, T), zeros(W, T)
+        if P:
+            assert ctx.window_push_multi_device(T, P, dx.data_ptr(), dy.data_ptr(), True, pm.data_ptr(), pv.data_ptr(), lm.data_ptr()) == 0
+        else:
+            assert ctx.window_push_device(T, dx.data_ptr(), dy.data_ptr(), True, pm.data_ptr(), pv.data_ptr(), lm.data_ptr()) == 0
+        return host(pm, pv, lm)
+
+    for N in sizes:
+        cuts = np.cumsum([0, 1, N // 2, N + 5, 2, 1])   # the pushes: T = 1, N / 2, N + 5, a device-form one of 2, one more after the failure
+        for kid, d in kinds:
+            for P in (0, 1, 17):   # 0: the single-target calls
+                Xw, Yw = zip(*[window(cuts[-1], d, 10 * kid + N + d + w, kid, max(P, 1)) for w in range(W)])
+                X, Y = np.stack(Xw), np.stack(Yw).transpose(0, 2, 1)   # (W, T, d), (W, T, P)
+                rng = np.random.default_rng(N + kid + d)
+                Xs = np.stack([points_for(kid, X[w, :N + 5], 70, rng) for w in range(W)])
+                xi = rng.normal(size=(W, S, 70))
+                theta = np.tile(theta_of(kid, d), (W, 1))
+                ctx = engine.Context(max_n=8, max_m=8, max_d=d)
+                ctx.window_init(W, N, d, kid, theta)
+                if P:
+                    assert ctx.window_multi_reserve(P) == 0 and ctx.window_multi_grad_reserve() == 0
+                else:
+                    assert ctx.window_joint_reserve(70) == 0 and ctx.window_loo_grad_reserve() == 0
+                tag = f"kid{kid} N{N} d{d}" + (f" P{P}" if P else "")
+
+                def push(i, check=True):
+                    x, y = X[:, cuts[i]:cuts[i + 1]], Y[:, cuts[i]:cuts[i + 1]]
+                    res = ctx.window_push_multi(x, y, check=check) if P else ctx.window_push(x, y[:, :, 0], check=check)
+                    out[f"window_push{'_multi' if P else ''} {tag} T{x.shape[1]} from tick {cuts[i]}"] = flat(*res)
+
+                def state(name, select=None):
+                    if P:
+                        multi_round(ctx, f"{tag} {name}", Xs, P, d, select)
+                    else:
+                        single_round(ctx, f"{tag} {name}", Xs, xi, N, d, select)
+
+                state("empty")
+                push(0)
+                push(1)
+                state("filling")
+                push(2)
+                state("origin moved")
+                x, y = X[:, cuts[3]:cuts[4]], Y[:, cuts[3]:cuts[4]]
+                out[f"window_push{'_multi' if P else ''}_device {tag}"] = push_device(ctx, x, y if P else y[:, :, 0], P)
+                bad = theta.copy()
+                bad[1, -1] = -2.0 * bad[1, 0]   # window 1's Ky is negative definite (window_calls)
+                ctx.window_set_theta(bad, check=False)
+                state("window 1 failed", select=[1, 0, 1])
+                push(4, check=False)
+                ctx.close()
+
+    # staged blocks above 16 KiB: one window of capacity 528, a push of 600 ticks (28 KB) and a forecast at 600 points (19 KB)
+    N, T, d, kid, M = 528, 600, 2, 1, 600
+    X, Y = window(T, d, N + kid, kid)
+    assert T * (d + 4) * 8 > 16 * 1024 and M * (d + 2) * 8 > 16 * 1024
+    ctx = engine.Context(max_n=8, max_m=8, max_d=d)
+    ctx.window_init(1, N, d, kid, theta_of(kid, d)[None])
+    out[f"window_push by copy N{N} T{T}"] = flat(*ctx.window_push(X[None], Y[:1]))
+    Xs = points_for(kid, X, M, np.random.default_rng(N))[None]
+    out[f"window_predict by copy N{N} M{M}"] = flat(*ctx.window_predict(Xs))
+    out[f"window_predict_gradients by copy N{N} M{M}"] = flat(*ctx.window_predict_gradients(Xs))
+    ctx.close()
+
+
+def run(out_path, windows_once=False):
     os.environ["CGP_SMALL"] = "off"
     sys.path.insert(0, ROOT)
     import torch  # noqa: F401  (before the library: torch brings its own HIP runtime, which has to be the process's first)
     import corenav_gp_amd.engine as engine
     engine.load()
     out = {}
-    batch_calls(engine, out)
-    hooked_calls(engine, out)
-    window_calls(engine, out)
+    if windows_once:   # every window entry point at one shape: short enough to read as a launch listing under a kernel trace
+        window_host_calls(engine, out, sizes=(33,), kinds=((4, 3),))
+        window_calls(engine, out, sizes=(33,), kinds=((4, 3),), long_windows=False)
+    else:
+        batch_calls(engine, out)
+        hooked_calls(engine, out)
+        window_calls(engine, out)
+        window_host_calls(engine, out)
     np.savez(out_path, **out)
     print(f"{len(out)} calls saved to {out_path} (library {engine.LIB_PATH})")
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 3 and sys.argv[1] == "run":
-        run(sys.argv[2])
+    if len(sys.argv) >= 3 and sys.argv[1] in ("run", "run-windows-once"):
+        run(sys.argv[2], sys.argv[1] != "run")
     elif len(sys.argv) >= 4 and sys.argv[1] == "compare":
         sys.exit(compare(*sys.argv[2:5]))
     else:
