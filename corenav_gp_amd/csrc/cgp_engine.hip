@@ -22,6 +22,7 @@
 #include "cgp_loo.hpp"
 #include "cgp_loo_grad.hpp"
 #include "cgp_refine.hpp"
+#include "cgp_sched_plan.hpp"
 #include "gp_predictor_core.hpp"
 #include "gp_predictor.h"
 #include "lbfgs.hpp"
@@ -49,12 +50,6 @@ static_assert(CGP_SMALL_OUT == SM_OUT, "header / kernel short-window record mism
 
 namespace {
 
-#ifdef CGP_AB
-constexpr bool kAbBuild = true;
-#else
-constexpr bool kAbBuild = false;
-#endif
-
 struct ProfRec {
   int kernel;
   hipEvent_t a, b;
@@ -69,6 +64,27 @@ struct Scratch {
   int max_batch = 0, max_dim = 0;
   void *stage = nullptr;
   size_t stage_cap = 0;
+};
+
+// The fit schedules' own device buffers (cgp_sched_host.hpp), each() naming the pointers once for cgp_destroy.
+struct LatBufs {   // latency schedule, allocated by cgp_create_ex:
+  void *dpart = nullptr;     // partial tiles [lat_units][SK_MAX][128*128]
+  int *dticket = nullptr;    // arrival tickets [lat_cap][sk_slots]
+  int *dwready = nullptr;    // published block steps [lat_cap]
+  void *dlatimg = nullptr;   // pre-updated diagonal tiles [lat_img_fits][2][LAT_IMG_MAX][DPART]
+  int lat_cap = 0;           // fits the latency slabs are sized for: min(LAT_FITS_ALLOC, max_batch)
+  size_t lat_units = 0;      // fits x tile slots the partial-tile slab holds
+  int lat_img_fits = 0;      // fits the pre-update image buffer holds (only windows of >= 3 block steps use it)
+  int sk_slots = 0;          // tile slots per fit of the longest window: NTmax + ETmax + 1
+  size_t part_bytes(size_t esz) const { return lat_units * SK_MAX * TS * TS * esz; }
+  size_t img_bytes(size_t esz) const { return (size_t)lat_img_fits * 2 * LAT_IMG_MAX * DPART * esz; }
+  template <class F> void each(F &&f) { f(dpart); f(dticket); f(dwready); f(dlatimg); }
+};
+struct OneLaunchBufs {   // one-launch schedule of a mid-size call (k_sched), grown on demand: task list of the last (fits, NT, ET) shape,
+  void *tasks = nullptr, *flags = nullptr, *bimg = nullptr, *cimg = nullptr;   // flag words, one image slot per tile index
+  size_t tasks_cap = 0, flags_cap = 0, bimg_cap = 0, cimg_cap = 0;
+  int key[3] = {0, 0, 0}, ntasks = 0, grid = 0;
+  template <class F> void each(F &&f) { f(tasks); f(flags); f(bimg); f(cimg); }
 };
 
 // The sliding windows' device buffers: one record per reservation, one hipMalloc per member, the reservation's capacity beside
@@ -147,19 +163,13 @@ struct cgp_ctx {
   double *dtheta = nullptr, *djitter = nullptr, *dlogml = nullptr, *dprep = nullptr;
   long long *ddbg = nullptr;
   double *dgpart = nullptr;
-  void *dpart = nullptr;   // latency schedule: partial tiles [lat_cap][slots][SK_MAX][128*128]
-  int *dticket = nullptr;  //                   arrival tickets [lat_cap][slots]
-  int lat_cap = 0;         //                   fits the latency slabs are sized for: min(LAT_FITS_ALLOC, max_batch)
-  int *dwready = nullptr;  //                   published block steps [lat_cap]
-  void *dlatimg = nullptr;  //                  pre-updated diagonal tiles [lat_cap][2][LAT_IMG_MAX][DPART]
+  LatBufs lat;             // latency schedule: its slabs and their capacities
   double *dmacc = nullptr;  // [max_batch][2][max_m] running predictive sums (throughput schedule, fp64)
   void *ddiagimg = nullptr;  // [max_batch][2][DPART] pre-updated diagonal tiles (throughput schedule, diag_next)
   void *dpanimg = nullptr;   // [min(max_batch, mid cap)][2][DPART] pre-updated kind-A panel tiles (k_panel kind C)
   int mid_cap = 0;
-  // one-launch schedule of a mid-size call (k_sched): task list of the last (fits, NT, ET) shape, flag words, one image slot per tile index
-  void *dsched_tasks = nullptr, *dsched_flags = nullptr, *dsched_bimg = nullptr, *dsched_cimg = nullptr;
-  size_t sched_tasks_cap = 0, sched_flags_cap = 0, sched_bimg_cap = 0, sched_cimg_cap = 0;
-  int sched_key[3] = {0, 0, 0}, sched_ntasks = 0, sched_grid = 0, n_cu = 0;
+  OneLaunchBufs ol;   // one-launch schedule of a mid-size call (k_sched, measurement library)
+  int n_cu = 0;
   // cgp_fit_predict_batch staging, grown on demand and kept: pinned host buffers (hipHostMalloc) so the
   // H2D / D2H copies are real asynchronous DMA, and a raw fp64 device buffer the pack kernels read
   void *pin_in = nullptr, *pin_out = nullptr, *draw = nullptr;
@@ -167,9 +177,6 @@ struct cgp_ctx {
   double *la_buf = nullptr;  // cgp_predict_stop_batch staging, grown on demand
   int *la_ibuf = nullptr;
   size_t la_nd = 0, la_ni = 0;
-  int sk_slots = 0;
-  size_t lat_units = 0;   // fits x tile slots the latency schedule's partial-tile slab holds
-  int lat_img_fits = 0;   // fits the pre-update image buffer of the latency schedule holds (only windows of >= 3 block steps use it)
   // sliding windows (cgp_window_*)
   WindowArgs win{};
   int nwin = 0;
@@ -448,156 +455,8 @@ hipEvent_t get_event(cgp_ctx *c) {
   return e;
 }
 
-struct Launcher {
-  cgp_ctx *c;
-  hipStream_t s;
-  int pending = -1;
-  void begin(int kernel, double flops, int step = -1) {
-    if (!c->prof) return;
-    if (c->prof_step >= 0 && !(kernel == 0 && step == c->prof_step)) return;  // one update launch per schedule
-    ProfRec r{kernel, get_event(c), get_event(c), flops};
-    (void)hipEventRecord(r.a, s);
-    c->recs.push_back(r);
-    pending = (int)c->recs.size() - 1;
-  }
-  void end() {
-    if (!c->prof || pending < 0) return;
-    (void)hipEventRecord(c->recs[pending].b, s);
-    pending = -1;
-  }
-};
-
-// Batches up to this size take the latency schedule: the measured crossover against the (mid-size) throughput
-// schedule (tools/lat_crossover.sh, round 3: N = 2048 fp64 8 fits 1.87 vs 2.64 ms, 12 fits 2.72 vs 2.66; N = 1024 fp32
-// 20 fits 0.641 vs 0.672 ms, 24 fits 0.769 vs 0.712) is 11 fits in fp64 and 20 in fp32 (16 / 24 before the mid-size form).
-constexpr int LAT_FITS_F64 = 11, LAT_FITS_F32 = 20;
-// The shorter the window, the larger the call the latency schedule still wins (tools/lat_crossover.sh by window length, end of
-// round 3, ms per call latency vs throughput).  fp64: N = 256 32 fits 0.171 vs 0.240, 48 fits 0.225 vs 0.245; N = 512 28 fits 0.417 vs
-// 0.422 (no extra-row split), 32 fits 0.464 vs 0.456; N = 768 20 fits 0.607 vs 0.657, 24 fits 0.681 vs 0.681; N = 1024 16 fits 0.835 vs
-// 0.920, 20 fits 1.010 vs 0.954; N = 1536 12 fits 1.487 vs 1.635, 16 fits 1.926 vs 1.682; N = 2048 11 (above).  fp32: N = 256 32 fits
-// 0.124 vs 0.133, 48 fits 0.154 vs 0.138; N = 512 24 fits 0.261 vs 0.272, 28 fits 0.290 vs 0.276; N = 768 20 fits 0.412 vs 0.414; N = 1024
-// 20 (above).  The slabs are sized for LAT_FITS_SHORT fits.
-// (Round 4, tools/check_crossovers.py: fp64 N = 256 33 fits 0.168 latency vs 0.205 throughput -- the limit of 32 was the slab's,
-// not the crossover's; with round 3's 48 fits 0.225 vs 0.245 the fp64 limit for one and two block steps is 48.)
-constexpr int LAT_FITS_SHORT = 32, LAT_FITS_SHORT64 = 48;
-inline int lat_fits_by_steps(bool f64, int NT) {
-  if (NT <= 2) return f64 ? LAT_FITS_SHORT64 : LAT_FITS_SHORT;
-  if (f64) return NT <= 4 ? 28 : NT <= 6 ? 22 : NT <= 8 ? 18 : NT <= 12 ? 13 : LAT_FITS_F64;
-  return NT <= 4 ? 24 : LAT_FITS_F32;
-}
-constexpr int FUSED64_BELOW = 512;                // fp64 throughput schedule: diagonal tiles inside the panel launches below this batch
-// Calls too small to fill the chip (a launch then lasts as long as its longest workgroup chain): the next launch's
-// kind-A tile is pre-updated by a kind-C workgroup (k_panel), and fp32 takes the deep-prefetch loops (DEEP).
-// Measured crossover (tools/r3_mid2.sh, same box, CGP_MID_FITS either side): fp32 N = 1024: 32 fits +14 %, 48 +13 %,
-// 64 +9 %, 96 +2 %, 128 -4 %; fp64 N = 2048: 24 fits +18 %, 32 +11 %, 48 +4 %, 64 -2 %.
-constexpr int MID_FITS_F64 = 48, MID_FITS_F32 = 96;
-#ifndef CGP_NO_EXTRA_SPLIT
-#define CGP_NO_EXTRA_SPLIT 0   // `make variant` A/B: mid-size calls keep the extra rows inside the factorisation launches
-#endif
-constexpr bool kNoExtraSplit = CGP_NO_EXTRA_SPLIT != 0;
-#ifndef CGP_LAT_MIN_NT
-#define CGP_LAT_MIN_NT 1   // block steps from which a handful of fits takes the latency schedule (3 until the end of round 3: `make variant` A/B)
-#endif
 constexpr size_t kOptPinIn = CGP_MAX_THETA + 8;   // doubles at the head of the gradient-mode pinned block: theta, jitter
-// fp64 mid-size calls put their extra rows on a second stream when there is enough of them: fits x block steps >= this
-// (tools/r3_xs_n.sh, same box, with / without, ms per call: N = 2048 28 fits 3.77 / 3.70, 36 fits 4.25 / 4.45, 48 fits 5.01 / 5.70;
-// N = 1536 36 fits 2.37 / 2.38, 48 fits 2.71 / 3.01; N = 1024 36 fits 1.27 / 1.17, 48 fits 1.29 / 1.31; N = 512 28 fits 0.52 / 0.42)
-constexpr int XSPLIT64_WORK = 480;
-#ifndef CGP_XSPLIT32_FITS
-#define CGP_XSPLIT32_FITS 0    // fp32 mid-size calls from this many fits: extra rows on the second stream as 64-row tiles (k_rows64); 0 = never.
-                               // Measured (round 5, ms per call without / with): 24 fits 0.629 / 0.647, 32 0.686 / 0.777, 48 0.770 / 0.791, 64 0.994 / 0.954,
-                               // 96 1.282 / 1.270 -- bitwise the one-stream results, but two stream GROUPS (0.895 at 64 fits) beat it: not taken
-#endif
-constexpr int XSPLIT32_FITS = CGP_XSPLIT32_FITS;
-constexpr int MID_FITS_ALLOC = kAbBuild ? 512 : (MID_FITS_F64 > MID_FITS_F32 ? MID_FITS_F64 : MID_FITS_F32);
-// fp64 by window length (tools/r3_mid_n2.sh, end of round 3, with the extra-row split by work; mid-size form off / on, ms per call):
-// N = 2048 64 fits 7.26 / 6.87, 96 fits 9.80 / 9.67; N = 1536 96 fits 5.14 / 4.95; N = 1024 96 fits 2.22 / 2.10; N = 768 64 fits 1.06 /
-// 1.01, 80 fits 1.16 / 1.16, 96 fits 1.27 / 1.28; N = 512 96 fits 0.645 / 0.663 -- up to 96 fits from eight block steps, 64 from six.
-template <typename T> inline int mid_fits(int NT) {     // ablation build: CGP_MID_FITS moves the crossover (measurement)
-  if constexpr (kAbBuild) {
-    const char *e = getenv("CGP_MID_FITS");
-    if (e) return std::max(0, std::min(atoi(e), MID_FITS_ALLOC));
-  }
-  if (sizeof(T) == 8) return NT >= 8 ? MID_FITS_F32 : NT >= 6 ? 64 : MID_FITS_F64;
-  return MID_FITS_F32;
-}
-constexpr int LAT_FITS_ALLOC = kAbBuild ? 64 : LAT_FITS_SHORT64;  // slabs are sized for min(this, max_batch) fits
-template <typename T> inline int lat_fits(int NT) {     // ablation build: CGP_LAT_FITS moves the crossover (measurement)
-  if constexpr (kAbBuild) {
-    const char *e = getenv("CGP_LAT_FITS");
-    if (e) return std::max(0, std::min(atoi(e), LAT_FITS_ALLOC));
-  }
-  return lat_fits_by_steps(sizeof(T) == 8, NT);
-}
-
-inline size_t alpha_lds_bytes(int NT) { return (size_t)(NT * TS + TS) * sizeof(double); }
-template <typename T> constexpr int upd_lds_bytes() { return 4 * KT * LDST * (int)sizeof(T); }
-template <typename T> constexpr int panel_lds_bytes() {   // + z of one block column; fp32 with the bf16 planes: planes + Gram inputs + z
-  return (kF32Bf16x6 && sizeof(T) == 4) ? (bx_z_offset<false>() + TS) * 4 : upd_lds_bytes<T>() + TS * (int)sizeof(T);
-}
-static_assert(panel_lds_bytes<float>() >= WIMG * 4 && panel_lds_bytes<float>() >= upd_lds_bytes<float>() + TS * 4,
-              "the panel kernels stage W_k's image (and k_rows64 its chunk buffers) over the loop's LDS");
-template <typename T> constexpr int paneldiag_lds_bytes() { return std::max(panel_lds_bytes<T>(), diag_lds_elems<T>() * (int)sizeof(T)); }
-// mid-size build: fp32 factors the diagonal tile in the fat form (potf2_tile), see mid_fat
-template <typename T> constexpr int paneldiag_mid_lds_bytes() {
-  return mid_fat<T, true>() ? std::max(paneldiag_lds_bytes<T>(), potf2_lds_elems<T>() * (int)sizeof(T)) : paneldiag_lds_bytes<T>();
-}
-static_assert(!kF32Bf16x6 || (bx_z_offset<true>() + TS) * 4 <= paneldiag_mid_lds_bytes<float>(), "mid-size build: the two plane buffers do not fit its LDS");
-// the deep loop's chunk ring + z of one block column must fit what the mid-size build's launches carry
-static_assert(deep_ring<float, true>() * KT * LDST * 4 + TS * 4 <= paneldiag_mid_lds_bytes<float>() &&
-              deep_ring<double, true>() * KT * LDST * 8 + TS * 8 <= paneldiag_mid_lds_bytes<double>(), "mid-size build: ring does not fit its LDS");
-template <typename T> constexpr int potf2_lds_bytes() {
-  return (TS * LDP + 8 * DB * DB + 4 * DB * DB) * (int)sizeof(T) + 16;
-}
-
-#ifndef CGP_F32_FULL_DEEP
-#define CGP_F32_FULL_DEEP 0   // `make variant` A/B: the deep-prefetch fp32 loops at full batch too (measured slower: 128 -> 168 VGPRs)
-#endif
-// hipFuncSetAttribute applies to the CURRENT device's function object: called from cgp_create after
-// hipSetDevice, once per (device, dtype).
-// (two contexts may be created from two threads at once: the per-device "done" marks are guarded by a mutex)
-std::mutex g_attr_mutex;
-template <typename T> int set_lds_attrs(int device) {
-  static bool done[64] = {false};
-  std::lock_guard<std::mutex> lk(g_attr_mutex);
-  if (device >= 0 && device < 64 && done[device]) return 0;
-  const int upd = upd_lds_bytes<T>(), tile = potf2_lds_bytes<T>();
-  auto set = [](const void *fn, int bytes) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess; };
-  bool ok = true;
-  ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, false>), panel_lds_bytes<T>());
-  ok = ok && set(reinterpret_cast<const void *>(&k_grad<T>), upd);
-  if constexpr (sizeof(T) == 8) {   // the Matern instantiations (fp64 only)
-    ok = ok && set(reinterpret_cast<const void *>(&k_grad<T, 1>), upd);
-    ok = ok && set(reinterpret_cast<const void *>(&k_grad<T, 2>), upd);
-    ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, false, true, false, true>), panel_lds_bytes<T>());
-    ok = ok && set(reinterpret_cast<const void *>(&k_tile_sk<T, true>), tile);
-    ok = ok && set(reinterpret_cast<const void *>(&k_diag_lean<T, false, true>), paneldiag_lds_bytes<T>());
-    ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, true, true, false, true>), paneldiag_lds_bytes<T>());
-    ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, true, true, true, true>), paneldiag_mid_lds_bytes<T>());
-#ifdef CGP_AB
-    ok = ok && set(reinterpret_cast<const void *>(&k_diag<T, true>), tile);
-#endif
-  }
-  ok = ok && set(reinterpret_cast<const void *>(&k_tile_sk<T>), tile);
-  ok = ok && set(reinterpret_cast<const void *>(&k_trmm_sk<T>), upd);
-  ok = ok && set(reinterpret_cast<const void *>(&k_diag_lean<T>), paneldiag_lds_bytes<T>());
-  ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, true>), paneldiag_lds_bytes<T>());
-  ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, true, true, true>), paneldiag_mid_lds_bytes<T>());
-#ifdef CGP_AB
-  ok = ok && set(reinterpret_cast<const void *>(&k_sched<T>), paneldiag_mid_lds_bytes<T>());
-#endif
-  if constexpr (sizeof(T) == 4) ok = ok && set(reinterpret_cast<const void *>(&k_refine_solve<float>), 160 * 1024);
-  if constexpr (sizeof(T) == 4) ok = ok && set(reinterpret_cast<const void *>(&k_refine_gated<float>), 160 * 1024);
-  if constexpr (mid_fat<T, true>()) ok = ok && set(reinterpret_cast<const void *>(&k_diag_lean<T, true>), paneldiag_mid_lds_bytes<T>());
-  if constexpr (CGP_F32_FULL_DEEP && sizeof(T) == 4) ok = ok && set(reinterpret_cast<const void *>(&k_panel<T, true, true, false>), paneldiag_lds_bytes<T>());
-#ifdef CGP_AB
-  ok = ok && set(reinterpret_cast<const void *>(&k_diag<T>), tile);
-#endif
-  if (!ok) return -1;
-  if (device >= 0 && device < 64) done[device] = true;
-  return 0;
-}
-
+std::mutex g_attr_mutex;   // guards the per-device "done" marks of set_lds_attrs (cgp_sched_host.hpp) and set_small_attr
 constexpr size_t kLdsPerWorkgroup = 160 * 1024;   // gfx950
 // k_small<BROWN, DMAX>: the reference's kernel, and SE kernels compiled for d <= 1 / 3 / 8 (the smallest that fits is launched)
 template <typename F> int for_each_small_kernel(F &&f) {
@@ -671,519 +530,12 @@ template <typename T> FitArgs group_view(const FitArgs &a, int g0) {
   return v;
 }
 
-// A/B switches of the schedule.  The shipped library has ONE schedule pair (throughput: k_diag_lean +
-// k_panel with running predictive sums; latency: k_tile_sk + k_trmm_sk for <= LAT_FITS_F64 / LAT_FITS_F32 fits); the
-// alternatives measured in DESIGN.md (one diagonal launch per step, two-stream overlap,
-// fat diagonal, finalize without accumulators, fused trmm) exist only in a -DCGP_AB build, where the
-// environment selects them once per process.
-struct SchedSwitches {
-  bool no_latency = false, split_diag = false, fused_diag = false, overlap = false, fat_diag = false, acc_off = false,
-       sk_fused_trmm = false;
-};
-const SchedSwitches &sched_switches() {
-  static const SchedSwitches sw = [] {
-    SchedSwitches w;
-    // CGP_SCHED=throughput is honoured by every build: the tests use it to run the throughput schedule
-    // on a handful of fits.
-    const char *e = getenv("CGP_SCHED");
-    const std::string sch = e ? e : "";
-    w.no_latency = sch == "throughput";
-#ifdef CGP_AB
-    w.no_latency = w.no_latency || sch == "overlap" || sch == "splitdiag";
-    w.split_diag = sch == "splitdiag";
-    w.fused_diag = sch == "fuseddiag";
-    w.no_latency = w.no_latency || w.fused_diag;
-    w.overlap = sch == "overlap";
-    const char *dg = getenv("CGP_DIAG");
-    w.fat_diag = dg && std::string(dg) == "fat";
-    const char *ac = getenv("CGP_ACC");
-    w.acc_off = ac && std::string(ac) == "off";
-    const char *tk = getenv("CGP_SK_TRMM");
-    w.sk_fused_trmm = tk && std::string(tk) == "fused";
-#endif
-    return w;
-  }();
-  return sw;
-}
+}  // namespace
 
-// A launch of a kernel that builds Gram tiles: a Matern fit (fp64 contexts only, check_shape) runs the kernel's MAT = true
-// instantiation, every other kernel id the instantiation it ran before the Matern kernels existed.
-#define CGP_LAUNCH_GRAM(T, A, KERN, KERN_MAT, ...)                    \
-  do {                                                                \
-    bool cgp_matern_ = false;                                         \
-    if constexpr (sizeof(T) == 8) {                                   \
-      if (k_is_matern((A).kernel_id)) {                               \
-        hipLaunchKernelGGL(KERN_MAT, __VA_ARGS__);                    \
-        cgp_matern_ = true;                                           \
-      }                                                               \
-    }                                                                 \
-    if (!cgp_matern_) hipLaunchKernelGGL(KERN, __VA_ARGS__);          \
-  } while (0)
+// the fit schedules: the launch helpers, one enqueue function per schedule, run_schedule / run
+#include "cgp_sched_host.hpp"
 
-// k_panel<T, true> has two builds: the full-batch one, and the one for calls that leave CUs underfilled (kinds C /
-// image-A compiled in; fp32: deep-prefetch loops)
-template <typename T> void launch_panel_diag(bool mid, dim3 grid, hipStream_t s, const FitArgs &a, int k) {
-  if (mid) {
-    CGP_LAUNCH_GRAM(T, a, (k_panel<T, true, true, true>), (k_panel<T, true, true, true, true>), grid, dim3(256), paneldiag_mid_lds_bytes<T>(), s, a, k);
-    return;
-  }
-  if constexpr (CGP_F32_FULL_DEEP && sizeof(T) == 4) hipLaunchKernelGGL((k_panel<T, true, true, false>), grid, dim3(256), paneldiag_lds_bytes<T>(), s, a, k);
-  else CGP_LAUNCH_GRAM(T, a, (k_panel<T, true>), (k_panel<T, true, true, false, true>), grid, dim3(256), paneldiag_lds_bytes<T>(), s, a, k);
-}
-
-// The extra-row tiles of block step k alone (rows_from_extra), in the loop flavour of the mid-size build
-template <typename T> void launch_panel_rows(dim3 grid, hipStream_t s, const FitArgs &a, int k) {
-  CGP_LAUNCH_GRAM(T, a, (k_panel<T, false, true, false>), (k_panel<T, false, true, false, true>), grid, dim3(256), panel_lds_bytes<T>(), s, a, k);
-}
-
-template <typename T> void launch_diag(const FitArgs &a, int nfits, int k, bool fat, hipStream_t s, bool mid = false) {
-  if constexpr (mid_fat<T, true>()) {
-    if (mid) {
-      hipLaunchKernelGGL((k_diag_lean<T, true>), dim3(nfits), dim3(256), paneldiag_mid_lds_bytes<T>(), s, a, k);
-      return;
-    }
-  }
-#ifdef CGP_AB
-  if (fat) {
-    CGP_LAUNCH_GRAM(T, a, (k_diag<T>), (k_diag<T, true>), dim3(nfits), dim3(256), potf2_lds_bytes<T>(), s, a, k);
-    return;
-  }
-#endif
-  (void)fat;
-  CGP_LAUNCH_GRAM(T, a, (k_diag_lean<T>), (k_diag_lean<T, false, true>), dim3(nfits), dim3(256), paneldiag_lds_bytes<T>(), s, a, k);
-}
-
-// A mid-size fit call as ONE persistent launch (k_sched, cgp_kernels_fused.hpp): the tile programs of the NT + 1 launches
-// become tasks of a list ordered by block step; per-fit progress counters replace the launch boundaries.  Bitwise the
-// launches' results; measured slower than them (round 4), so it exists in the -DCGP_AB library only.
-bool sched_enabled() {   // measurement builds only (-DCGP_AB), CGP_SCHED=onelaunch: as measured it does not beat the launches
-  if constexpr (!kAbBuild) return false;
-  static const bool on = [] {
-    const char *e = getenv("CGP_SCHED");
-    return e && std::string(e) == "onelaunch";
-  }();
-  return on;
-}
-#ifdef CGP_AB
-template <typename T>
-int run_sched(cgp_ctx *c, FitArgs a, int batch, hipStream_t s) {
-  const int NT = a.NT, ET = a.ET;
-  if (c->sched_key[0] != batch || c->sched_key[1] != NT || c->sched_key[2] != ET) {
-    std::vector<int4> tasks;
-    auto put = [&](int kind, int k, int b, int rt) { tasks.push_back(make_int4(kind, k, b, rt)); };
-    // Order: by block step; inside a step the chain first (A, then the pre-updates C and B), then the matrix rows' tiles (the
-    // next step's chain reads them), and only then the EXTRA rows' tiles of the step BEFORE -- they feed nothing but their own
-    // next block column, so they lag one step behind and fill in beside the chain.  CGP_SCHED_LAG=0: no lag (measurement).
-    static const int lag = [] { const char *e = getenv("CGP_SCHED_LAG"); return e ? atoi(e) : 1; }();
-    auto extra = [&](int k) {
-      for (int e = 0; e < ET; ++e)
-        for (int b = 0; b < batch; ++b) put(SCHED_T, k, b, NT + e);
-    };
-    for (int k = 0; k < NT; ++k) {
-      if (k + 1 < NT) for (int b = 0; b < batch; ++b) put(SCHED_A, k, b, k + 1);
-      if (k + 2 < NT) for (int b = 0; b < batch; ++b) put(SCHED_C, k, b, k + 2);
-      if (k + 2 < NT && k >= 1) for (int b = 0; b < batch; ++b) put(SCHED_B, k, b, k + 2);
-      for (int rt = k + 2; rt < NT; ++rt)
-        for (int b = 0; b < batch; ++b) put(SCHED_T, k, b, rt);
-      if (k - lag >= 0) extra(k - lag);
-    }
-    for (int k = std::max(0, NT - lag); k < NT; ++k) extra(k);
-    if (!grow_device(c->dsched_tasks, c->sched_tasks_cap, tasks.size() * sizeof(int4))) return CGP_ENOMEM;
-    HIP_TRY(c, hipMemcpyAsync(c->dsched_tasks, tasks.data(), tasks.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipStreamSynchronize(s));   // `tasks` is a local (once per shape)
-    c->sched_ntasks = (int)tasks.size();
-    c->sched_key[0] = batch;
-    c->sched_key[1] = NT;
-    c->sched_key[2] = ET;
-    int occ = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_sched<T>, 256, paneldiag_mid_lds_bytes<T>()));
-    c->sched_grid = std::max(1, std::min(c->sched_ntasks, std::max(1, occ) * std::max(1, c->n_cu)));
-  }
-  const int pstride = c->NTmax + c->ETmax, fstride = c->NTmax + 2;
-  const size_t nflag = 2 + (size_t)batch * (pstride + 1 + 2 * fstride);
-  const size_t img_bytes = (size_t)batch * c->NTmax * DPART * sizeof(T);
-  if (!grow_device(c->dsched_flags, c->sched_flags_cap, nflag * sizeof(int)) || !grow_device(c->dsched_bimg, c->sched_bimg_cap, img_bytes) ||
-      !grow_device(c->dsched_cimg, c->sched_cimg_cap, img_bytes))
-    return CGP_ENOMEM;
-  HIP_TRY(c, hipMemsetAsync(c->dsched_flags, 0, nflag * sizeof(int), s));
-  int *fl = static_cast<int *>(c->dsched_flags);
-  SchedArgs q{};
-  q.tasks = static_cast<const int4 *>(c->dsched_tasks);
-  q.ntasks = c->sched_ntasks;
-  q.head = fl;
-  q.abort = fl + 1;
-  q.prog = fl + 2;
-  q.prog_stride = pstride;
-  q.wdone = q.prog + (size_t)batch * pstride;
-  q.bflag = q.wdone + batch;
-  q.cflag = q.bflag + (size_t)batch * fstride;
-  q.flag_stride = fstride;
-  a.dpart = c->dsched_bimg;
-  a.pimg = c->dsched_cimg;
-  a.img_slots = c->NTmax;
-  a.diag_slots = 0;
-  a.diag_stride = 0;
-  hipLaunchKernelGGL(k_sched<T>, dim3(c->sched_grid), dim3(256), paneldiag_mid_lds_bytes<T>(), s, a, q);
-  return CGP_OK;
-}
-#else
-template <typename T> int run_sched(cgp_ctx *, FitArgs, int, hipStream_t) { return CGP_EINVAL; }
-#endif
-
-// Refinement of an fp32 fit (cgp_refine.hpp): how many steps this call takes, and whether every fit takes them or only the
-// ones k_finalize marks as dense (FitArgs::rflag, RF_RHO).  -1 (the default) = one step; every fit of a window of at most three
-// input dimensions (measured, 40 fits of N = 1000, mean error against the oracle without / with: d = 1 1.0e-3 / 6e-7, d = 2
-// 7e-4 / 1.5e-7, d = 3 3.1e-4 with a worst fit at 1.1e-3 / 1e-7), the marked fits beyond (d = 4: two windows of 43 000 fuzz cases
-// at 1.1 and 1.3e-3, rho = 21; d = 6: 7e-5, worst 1.8e-4, rho 3 ... 8): BASELINE configs[2] (d = 6, rho 3 ... 11.5) pays one
-// launch whose workgroups return at once (k_refine_gated).
-constexpr int kRefineAutoMaxD = 3;
-inline int refine_steps(const cgp_ctx *c, const FitArgs &a) {
-  if (c->dtype != CGP_F32 || !c->dref_a || a.xid || a.NT > kRefineMaxNT) return 0;
-  // one step contracts the mean's error by ~1e-3 on most windows (N = 1536 / 2048 / 3000, d = 1, a lone fit: 2.4e-3 / 8.8e-4 / 2.4e-3 ->
-  // 1.8e-6 / 6.0e-6 / 1.9e-6) but by as little as 2e-2 on some -- 6.7e-3 -> 1.4e-4 -> 2.6e-6 at N = 4 500; in batched calls of N = 1 100
-  // the sweep found single fits at 3 ... 7e-5 after one step (six in ~3 000 refined cases) -- so windows of more than 1 024 samples
-  // take two (the contract for a refined mean is 5e-5: include/corenav_gp.h)
-  if (c->refine < 0) return a.NT > 8 ? 2 : 1;
-  return std::min(c->refine, 3);
-}
-inline bool refine_gated(const cgp_ctx *c, const FitArgs &a) { return c->refine < 0 && a.d > kRefineAutoMaxD; }
-template <bool MEAN> void launch_refine_gemv(int rows, int nfits, hipStream_t s, const FitArgs &a, const RefineArgs &q) {
-  const dim3 grid(cdiv(rows, RF_ROWS), nfits);
-  if (a.kernel_id == K_RBF_BROWNIAN) hipLaunchKernelGGL((k_refine_gemv<float, 1, true, MEAN>), grid, dim3(256), 0, s, a, q);
-  else if (a.d == 1) hipLaunchKernelGGL((k_refine_gemv<float, 1, false, MEAN>), grid, dim3(256), 0, s, a, q);
-  else if (a.d == 2) hipLaunchKernelGGL((k_refine_gemv<float, 2, false, MEAN>), grid, dim3(256), 0, s, a, q);
-  else if (a.d == 3) hipLaunchKernelGGL((k_refine_gemv<float, 3, false, MEAN>), grid, dim3(256), 0, s, a, q);
-  else hipLaunchKernelGGL((k_refine_gemv<float, 0, false, MEAN>), grid, dim3(256), 0, s, a, q);
-}
-// The launches that follow k_finalize of `nfits` fits starting at fit g0 of the call: alpha_0 = L^-T z in double (in place of
-// k_alpha), `steps` correction steps (solve = false: alpha of the last fit call is already in dref_a -- predict after fit),
-// then the mean of the M test points.
-inline void launch_refine(cgp_ctx *c, const FitArgs &a, int nfits, int g0, hipStream_t s, int steps, bool solve, bool alpha_for_all) {
-  const RefineArgs q{c->dref_r + (size_t)g0 * c->alpha_stride, c->dref_a + (size_t)g0 * c->alpha_stride, c->alpha_stride, a.rflag};
-  if (solve && q.flag && !alpha_for_all && a.NT <= kRefineGatedMaxNT) {
-    // d > 3 under the default setting: k_finalize marked the dense fits, almost always none -- one launch, not four
-    hipLaunchKernelGGL(k_refine_gated<float>, dim3(nfits), dim3(RS_THREADS), refine_gated_lds_bytes(a.NT), s, a, q, steps, a.M > 0 ? 1 : 0);
-    return;
-  }
-  if (solve) {
-    const size_t lds = refine_solve_lds_bytes(a.NT);
-    RefineArgs q0 = q;
-    if (alpha_for_all) q0.flag = nullptr;   // the caller asked for alpha (cgp_get_alpha): alpha_0 of every fit, marked or not
-    hipLaunchKernelGGL(k_refine_solve<float>, dim3(nfits), dim3(RS_THREADS), lds, s, a, q0, 0);
-    for (int st = 0; st < steps; ++st) {
-      launch_refine_gemv<false>(a.N, nfits, s, a, q);
-      hipLaunchKernelGGL(k_refine_solve<float>, dim3(nfits), dim3(RS_THREADS), lds, s, a, q, 1);
-    }
-  }
-  if (a.M > 0) launch_refine_gemv<true>(a.M, nfits, s, a, q);
-}
-inline double refine_flops(const FitArgs &a, int nfits, int steps, bool solve) {   // covariance entries at (3 d + 20) flops + the two passes over the factor
-  const double ent = (solve ? (double)steps * a.N * a.N : 0.0) + (double)a.M * a.N;
-  return nfits * (ent * (3.0 * a.d + 20.0) + (solve ? (steps + 0.5) * 2.0 * a.N * a.N : 0.0));
-}
-
-// How every schedule of a call ends: decided once, at the head of run_schedule
-struct Epilogue {
-  bool in_rows, want_alpha;
-  int rsteps;   // refinement steps (0: none), with a solve for alpha_0 or on the alpha the fit call left, alpha of every fit or of the marked
-  bool rsolve, ralpha_all;
-};
-// The launches that end the schedule of the `nfits` fits from fit g0 of the call (a: their view), on L's stream and each bracketed
-// by L: k_finalize with TM test points per workgroup, k_alpha when the caller wants alpha, the fp32 refinement
-template <typename T, int TM>
-void launch_epilogue(cgp_ctx *c, Launcher &L, const FitArgs &a, const Epilogue &e, int nfits, int g0) {
-  L.begin(3, nfits * (4.0 * a.M * a.N + 2.0 * a.N));
-  hipLaunchKernelGGL((k_finalize<T, TM>), dim3(cdiv(a.M, TM) + 1, nfits), dim3(256), 0, L.s, a, e.in_rows ? 1 : 0);
-  L.end();
-  if (e.want_alpha) {
-    L.begin(4, nfits * (double)a.N * a.N);
-    hipLaunchKernelGGL(k_alpha<T>, dim3(nfits), dim3(256), alpha_lds_bytes(a.NT), L.s, a);
-    L.end();
-  }
-  if (e.rsteps > 0) {
-    L.begin(4, refine_flops(a, nfits, e.rsteps, e.rsolve));
-    launch_refine(c, a, nfits, g0, L.s, e.rsteps, e.rsolve, e.ralpha_all);
-    L.end();
-  }
-}
-
-// Enqueue the whole schedule for `batch` fits.  The batch is cut into up to c->nstreams contiguous
-// groups, one worker stream each, forked from / joined to the caller's stream `s` with events; the
-// launches are issued step-interleaved so every stream always has work queued.
-// in_rows = false: predict after fit (only the extra row tiles).
-template <typename T>
-int run_schedule(cgp_ctx *c, FitArgs a, int batch, bool in_rows, bool want_alpha, hipStream_t s) {
-  const SchedSwitches &sw = sched_switches();
-  a.rows_from_extra = in_rows ? 0 : 1;
-  // fp32: alpha and the mean refined against a double-precision residual (cgp_refine.hpp).  A fit call computes alpha for it;
-  // a predict-after-fit call (in_rows = false) reuses the alpha the fit call left in dref_a.
-  int rsteps = 0;
-  if constexpr (sizeof(T) == 4) rsteps = refine_steps(c, a);
-  const bool rsolve = rsteps > 0 && (in_rows || want_alpha);
-  if (rsteps > 0 && !rsolve && !c->refined) rsteps = 0;
-  if (in_rows || want_alpha) c->refined = rsolve;
-  const bool ralpha_all = rsolve && want_alpha;
-  if (rsolve) want_alpha = false;   // alpha_0 comes from k_refine_solve (double precision, dref_a): no k_alpha launch
-  if constexpr (sizeof(T) == 4) a.rflag = rsteps > 0 && refine_gated(c, a) ? c->dref_flag : nullptr;
-  const Epilogue ep{in_rows, want_alpha, rsteps, rsolve, ralpha_all};
-  const int upd_lds = upd_lds_bytes<T>();
-  const int tile_lds = potf2_lds_bytes<T>();
-  const bool auto_groups = c->nstreams == 0;
-  int G = auto_groups ? 1 : std::max(1, std::min(std::min(c->nstreams, (int)cgp_ctx::kMaxStreams), batch));
-  // latency schedule: a handful of fits, windows long enough for splitting to pay and short enough for the
-  // diagonal tile's pre-update images (N <= 2560); anything else takes the throughput schedule
-  // (the slab / image capacities are part of the predicate: a call they cannot hold -- only reachable with the measurement
-  // build's CGP_LAT_FITS override -- takes the mid-size or throughput schedule instead of failing after k_prep was queued)
-  const bool latency = !sw.no_latency && batch <= std::min(lat_fits<T>(a.NT), c->lat_cap) && a.NT >= CGP_LAT_MIN_NT && lat_images(a.NT - 1) <= LAT_IMG_MAX &&
-                       (size_t)batch * (a.NT + a.ET + 1) <= c->lat_units && (a.NT < 3 || batch <= c->lat_img_fits);
-  const bool mid = batch <= std::min(mid_fits<T>(a.NT), c->mid_cap);  // the whole call (the images are indexed by fit)
-  // A latency-schedule call is one chain; an fp64 mid-size call has its own concurrency (factorisation || extra rows, below).
-  // An fp32 mid-size call honours cgp_set_streams: cut into groups on worker streams, the chain-bound early launches of
-  // one group run beside the others' (64 x N=1024: 0.99 -> 0.92 ms per call at two groups) -- as long as every group stays
-  // above the latency schedule's range (a group that small would switch schedule: four groups of 16 measured 1.50 ms).
-  // Two groups, from 56 fits (measured, ms per call at 1 / 2 / 3 groups: 48 fits 0.77 / 0.83 / 0.83, 64 fits 0.99 / 0.92 / 1.48,
-  // 96 fits 1.24 / 1.17 / 1.66).
-  // Since round 5 the engine takes that split by itself (cgp_set_streams(0), the default): every caller of a 56 ... 96-fit fp32
-  // call -- cgp_sweep_*, a plain C host -- gets the 0.90 ms, not only a caller that knew to ask; cgp_set_streams(1) keeps one group.
-  if (latency || (mid && sizeof(T) == 8)) G = 1;
-  TuneStep tune;
-  if (mid && sizeof(T) == 4 && (G > 1 || auto_groups)) {
-    G = batch >= 56 && batch / 2 > lat_fits<T>(a.NT) ? 2 : 1;
-    if (G == 2 && auto_groups && in_rows && !c->prof) {   // the default does not assume that two groups run side by side: it measures
-      tune = tune_groups(c, batch, a.NT, s);
-      G = tune.groups;
-    }
-  }
-  if (c->prof || !in_rows) G = 1;  // per-kernel timing wants isolated launches
-  if (tune.ev0) HIP_TRY(c, hipEventRecord(tune.ev0, s));
-  const bool fused64 = sw.fused_diag || batch < FUSED64_BELOW;
-  const bool split_diag = sw.split_diag || !in_rows || (sizeof(T) == 8 && !fused64);
-  // Mid-size calls: the extra rows (test points and y: M + 1 of them against N - 128 (k + 1) matrix rows, i.e. most of
-  // the update work) do not feed the factorisation, only their own next block column.  They get launches of their own on
-  // a second stream -- E(k), after the launch that finished diagonal tile k -- so the chain-bound factorisation launches
-  // A(k) (few workgroups, long chains) run beside the MFMA-bound extra-row launches instead of in lock-step with them:
-  //     s :  diag(0)  A(0)  A(1)  A(2) ...            A(k): matrix tiles of step k + kinds A / B / C
-  //     sE:           E(0)  E(1)  E(2) ...            E(k) waits for A(k - 1) (W_k, row panel k) and follows E(k - 1)
-  // Measured (tools/r3_xsplit.sh, same box, variant without the split): fp64 N = 2048 48 fits 5.58 -> 4.99 ms, 32 fits 4.03 ->
-  // 3.92, 24 fits 3.48 -> 3.51, 12 fits 2.62 -> 3.45 (the call is one chain then: nothing to run beside it); fp32 N = 1024
-  // 64 fits 0.99 -> 1.01, 32 fits 0.69 -> 0.76: its launches last as long as kind A's chain at every k, so the extra rows'
-  // last launches only queue up behind it, and two contexts overlap worse (0.76 -> 0.96 ms per call).  fp64 from 28 fits.
-  // (not under cgp_profile_enable: per-launch events of two concurrent streams would overlap in time and their sum overstate the kernel)
-  // fp32: the extra rows go to the second stream as 64-row tiles (k_rows64) from XSPLIT32_FITS fits per call
-  int x32 = XSPLIT32_FITS;
-  if constexpr (kAbBuild) {   // measurement: CGP_XSPLIT32=<min fits> moves the threshold (0: never)
-    static const int x32env = [] { const char *e = getenv("CGP_XSPLIT32"); return e ? atoi(e) : -1; }();
-    if (x32env >= 0) x32 = x32env;
-  }
-  const bool xsplit_on = sizeof(T) == 8 ? batch * a.NT >= XSPLIT64_WORK : (x32 > 0 && batch >= x32);
-  const bool xsplit = mid && !latency && xsplit_on && in_rows && !split_diag && G == 1 && a.ET > 0 && !kNoExtraSplit && !c->prof;
-  constexpr bool own_main = false;   // (both halves of a concurrent call on the context's own streams: measured worse, docs/negatives.md round 5)
-  std::vector<FitArgs> ga(G);
-  std::vector<int> gb(G);
-  std::vector<hipStream_t> gs(G);
-  for (int g = 0, g0 = 0; g < G; ++g) {
-    gb[g] = batch / G + (g < batch % G ? 1 : 0);
-    if constexpr (kAbBuild) {   // measurement: CGP_GROUP0 = fits of group 0 of two (uneven halves run out of step with each other)
-      const char *e = getenv("CGP_GROUP0");
-      if (e && G == 2 && atoi(e) > 0 && atoi(e) < batch) gb[g] = g == 0 ? atoi(e) : batch - atoi(e);
-    }
-    ga[g] = group_view<T>(a, g0);
-    // group 0 stays on the caller's stream, the others go to worker streams: the workers live in another priority pool
-    // (cgp_create), so they never share a hardware queue with the caller's stream -- two WORKER streams may share one
-    // (the pool has few queues and every context creates eight streams: a 64-fit call as two groups on two workers ran
-    // 1.37 instead of 0.92 ms whenever other contexts existed in the process)
-    gs[g] = g == 0 ? s : c->wstream[g - 1];
-    g0 += gb[g];
-  }
-  hipLaunchKernelGGL(k_prep, dim3(cdiv(batch, 64)), dim3(64), 0, s, a, batch, c->dprep, in_rows ? 1 : 0,
-                     (latency && in_rows) ? c->dwready : nullptr);
-  if (G > 1 || own_main) {
-    HIP_TRY(c, hipEventRecord(c->ev_fork, s));
-    for (int g = 0; g < G; ++g)
-      if (gs[g] != s) HIP_TRY(c, hipStreamWaitEvent(gs[g], c->ev_fork, 0));
-  }
-  std::vector<Launcher> L;
-  for (int g = 0; g < G; ++g) L.push_back(Launcher{c, gs[g]});
-  // throughput schedule: the predictive sums V z and |V|^2 accumulate inside k_panel (block column
-  // k - 1 while it streams through the row fragments of step k); k_finalize then only adds the last
-  // block column instead of reading all of V.
-  // (No memset of the sums: block step 1 -- the first that has a finished block column behind it -- WRITES them, later steps add;
-  // the two fill launches were 10 us at the head of every call.  A window of one block step has nothing to accumulate.)
-  const bool use_acc = !latency && !sw.acc_off && a.M > 0 && !a.xid && a.NT >= 2;
-  if (use_acc) {
-    const size_t half = (size_t)batch * a.M;
-    for (int g = 0, g0 = 0; g < G; g0 += gb[g], ++g) {
-      ga[g].macc = c->dmacc + (size_t)g0 * a.M;
-      ga[g].vacc = c->dmacc + half + (size_t)g0 * a.M;
-    }
-  }
-  const int panel_lds = panel_lds_bytes<T>();
-  if (mid && !latency && in_rows && !c->prof && a.NT >= 2 && sched_enabled() && !k_is_matern(a.kernel_id) && !sw.split_diag && !sw.overlap) {
-    launch_diag<T>(ga[0], batch, 0, sw.fat_diag, s, true);   // diagonal tile 0: nothing to run beside it yet
-    int rc = run_sched<T>(c, ga[0], batch, s);
-    if (rc != CGP_OK) return rc;
-    launch_epilogue<T, 64>(c, L[0], ga[0], ep, batch, 0);
-    HIP_TRY(c, hipGetLastError());
-    return CGP_OK;
-  }
-#ifdef CGP_AB
-  if (sw.overlap && in_rows && G == 1 && !c->prof && a.NT >= 2) {
-    // Look-ahead schedule on two streams: the panel launch of step k is cut into P1 = the tile right
-    // below the diagonal (the only one the next diagonal tile needs) and P2 = all the others, and
-    //     sA:  P1(k) -> diag(k+1)            sB:  P2(k)
-    // run concurrently; events carry the cross dependencies.  Measured: no gain.
-    // sA = the context's HIGH-priority stream (the chain P1 -> diag must be dispatched ahead of the bulk P2 queued on the
-    // caller's stream; round 1-3 ran both on equal-priority worker streams, which may even have shared a hardware queue)
-    hipStream_t sA = c->hstream, sB = s;
-    auto ev = [&](int i) { return c->ev_look[i]; };
-    HIP_TRY(c, hipEventRecord(c->ev_fork, s));
-    HIP_TRY(c, hipStreamWaitEvent(sA, c->ev_fork, 0));
-    FitArgs a1 = ga[0], a2 = ga[0];
-    a1.tile_off = 0;
-    a2.tile_off = 1;
-    const int B = gb[0], NT = a.NT;
-    launch_diag<T>(ga[0], B, 0, sw.fat_diag, sA);
-    HIP_TRY(c, hipEventRecord(ev(0), sA));                         // evD[0]
-    for (int k = 0; k < NT; ++k) {
-      const int nin = NT - k - 1;                                  // in-matrix tiles below the diagonal
-      const bool has_p1 = nin >= 1;
-      const int n2 = (has_p1 ? nin - 1 : 0) + a.ET;                // P2: everything but the first tile
-      if (has_p1) {
-        if (k > 0) HIP_TRY(c, hipStreamWaitEvent(sA, ev(3 * (k - 1) + 2), 0));  // P2(k-1)
-        CGP_LAUNCH_GRAM(T, a1, (k_panel<T, false>), (k_panel<T, false, true, false, true>), dim3(1, B), dim3(256), panel_lds, sA, a1, k);
-        HIP_TRY(c, hipEventRecord(ev(3 * k + 1), sA));             // evP1[k]
-      }
-      HIP_TRY(c, hipStreamWaitEvent(sB, ev(3 * k), 0));            // diag(k)
-      if (k > 0 && NT - k >= 1) HIP_TRY(c, hipStreamWaitEvent(sB, ev(3 * (k - 1) + 1), 0));  // P1(k-1)
-      FitArgs ap = has_p1 ? a2 : a1;
-      CGP_LAUNCH_GRAM(T, ap, (k_panel<T, false>), (k_panel<T, false, true, false, true>), dim3(n2, B), dim3(256), panel_lds, sB, ap, k);
-      HIP_TRY(c, hipEventRecord(ev(3 * k + 2), sB));               // evP2[k]
-      if (k + 1 < NT) {
-        if (!has_p1 && k > 0) HIP_TRY(c, hipStreamWaitEvent(sA, ev(3 * (k - 1) + 2), 0));
-        launch_diag<T>(ga[0], B, k + 1, sw.fat_diag, sA);
-        HIP_TRY(c, hipEventRecord(ev(3 * (k + 1)), sA));           // evD[k+1]
-      }
-    }
-    HIP_TRY(c, hipStreamWaitEvent(sA, ev(3 * (NT - 1) + 2), 0));
-    Launcher LA{c, sA};
-    launch_epilogue<T, 64>(c, LA, ga[0], ep, B, 0);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_join[0], sA));
-    HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join[0], 0));
-    return CGP_OK;
-  }
-#endif
-  // Latency schedule for a handful of fits (k_tile_sk): the diagonal tile and
-  // the panel tiles of a step in one launch, inner dimension split over up to SK_MAX workgroups.
-  if (latency) {
-    const bool split_trmm = !sw.sk_fused_trmm;
-    // tile slots per fit of THIS call (slab and tickets are indexed with it; the tickets are zero between launches whatever the stride)
-    const int call_slots = a.NT + a.ET + 1;
-    if ((size_t)batch * call_slots > c->lat_units || (a.NT >= 3 && batch > c->lat_img_fits)) return CGP_ECAPACITY;
-    SplitArgs q{c->dpart, c->dticket, call_slots, 1, in_rows ? 1 : 0, c->dwready, c->dlatimg, split_trmm ? 0 : 1};
-    for (int k = 0; k < a.NT; ++k) {
-      const int tiles = (in_rows ? a.NT - k - 1 : 0) + a.ET;
-      const int nslots = tiles + (in_rows ? 1 : 0);
-      // >= 8 chunks of 16 columns per range; a function of k only, so a fit's result does not
-      // depend on how many fits share the call (the partial sums are added in range order)
-      const int sk = std::max(1, std::min(SK_MAX, k));
-      q.sk = sk;
-      L[0].begin(0, panel_flops(a.N, a.M, a.d, k, in_rows, batch) + (in_rows ? diag_flops(a.N, a.d, k, batch) : 0.0), k);
-      // z also carries the pre-update workgroups of the NEXT diagonal tile (1 + images of tile k + 1)
-      const int gz = in_rows ? std::max(sk, 1 + (k + 1 < a.NT ? lat_images(k + 1) : 0)) : sk;
-      CGP_LAUNCH_GRAM(T, ga[0], (k_tile_sk<T>), (k_tile_sk<T, true>), dim3(nslots, batch, gz), dim3(256), in_rows ? tile_lds : upd_lds, s, ga[0], q, k);
-      L[0].end();
-      if (split_trmm) {
-        L[0].begin(2, trsm_flops(a.N, a.M, k, in_rows, batch));
-        hipLaunchKernelGGL(k_trmm_sk<T>, dim3(tiles * TRMM_SPLIT, batch), dim3(64 * TRMM_WAVES), upd_lds, s, ga[0], k);
-        L[0].end();
-      }
-    }
-    launch_epilogue<T, 8>(c, L[0], ga[0], ep, batch, 0);
-    HIP_TRY(c, hipGetLastError());
-    return CGP_OK;
-  }
-  // Fit launches: the diagonal tile k + 1 is finished inside the panel launch of step k and tile k + 2 is
-  // pre-updated there (k_panel<T, true>, diag_next), so only tile 0 has a launch of its own: NT + 1
-  // launches per fit schedule instead of 2 NT, and no launch in which one workgroup per fit factors a tile
-  // while the rest of the chip waits.  -DCGP_AB, CGP_SCHED=splitdiag: one k_diag_lean launch per step.
-  // Measured (same box, alternating libraries): fp32 N = 1024 +2.6 % fits/s, fp64 N = 2048 -0.7 % -- in fp64
-  // the diagonal launches are already MFMA-bound in their syrk part and two workgroups per CU leave the
-  // finisher's factorisation chain nothing to hide behind -- so at the bench batch fp64 keeps one k_diag_lean
-  // launch per step (CGP_SCHED=fuseddiag in a -DCGP_AB build selects the fused form there too).
-  // fp64: a diagonal launch is one workgroup per fit on a latency chain whose length does not depend on the
-  // batch (3.3 ms per N = 2048 schedule), so below FUSED64_BELOW fits per call the fused form wins there too
-  // (batch 32 +26 %, 64 +15 %, 128 +6 %, 256 +0.2 %, 512 -0.7 %).
-  // (fused64 / split_diag / xsplit are decided above, with the stream groups)
-  hipStream_t sE = c->wstream[0];
-  Launcher LE{c, sE};
-  for (int k = 0; k < a.NT; ++k) {
-    const int gx_t = (in_rows ? a.NT - k - 1 : 0) + (xsplit ? 0 : a.ET);
-    for (int g = 0; g < G; ++g) {
-      if (in_rows && (split_diag || k == 0)) {
-        L[g].begin(1, diag_flops(a.N, a.d, k, gb[g]));
-        launch_diag<T>(ga[g], gb[g], k, sw.fat_diag, gs[g], mid && !split_diag);
-        L[g].end();
-      }
-      if (xsplit) {
-        // E(k) needs W_k and the row panel k: diag(0) for k = 0, else everything up to A(k - 1), the last thing queued on s
-        HIP_TRY(c, hipEventRecord(c->ev_look[k], gs[g]));
-        HIP_TRY(c, hipStreamWaitEvent(sE, c->ev_look[k], 0));
-        FitArgs ae = ga[g];
-        ae.rows_from_extra = 1;
-        LE.begin(0, panel_flops(a.N, a.M, a.d, k, false, gb[g]), k);
-        if constexpr (sizeof(T) == 8) launch_panel_rows<T>(dim3(a.ET, gb[g]), sE, ae, k);
-        else hipLaunchKernelGGL(k_rows64<T>, dim3(cdiv(a.M + 1, HR), gb[g]), dim3(256), panel_lds_bytes<T>(), sE, ae, k);
-        LE.end();
-      }
-      if (split_diag) {
-        L[g].begin(0, panel_flops(a.N, a.M, a.d, k, in_rows, gb[g]), k);
-        CGP_LAUNCH_GRAM(T, ga[g], (k_panel<T, false>), (k_panel<T, false, true, false, true>), dim3(gx_t, gb[g]), dim3(256), panel_lds, gs[g], ga[g], k);
-        L[g].end();
-        continue;
-      }
-      const bool hasA = k + 1 < a.NT, hasB = k + 2 < a.NT && k >= 1;
-      const bool hasC = mid && k + 2 < a.NT, imgA = mid && hasA && k >= 1;  // launch k - 1 had a kind C iff k + 1 < NT
-      FitArgs ak = ga[g];
-      ak.diag_slots = (hasA ? 1 : 0) | (hasB ? 2 : 0) | (hasC ? 4 : 0) | (imgA ? 8 : 0);
-      ak.diag_stride = sizeof(T) == 8 || mid ? 2 : (CGP_F32_FULL_DEEP ? 3 : F32_FULL_OCC);  // workgroups per CU of k_panel<T, true> (LDS / VGPR bound)
-      const int gx = gx_t + (hasB ? 1 : 0) + (hasC ? 1 : 0);  // gx_t already counts row tile k + 1 (kind A)
-      // algorithmic flops of THIS launch: kind C does the part of tile (k + 2, k + 1) that kind A of launch k + 1 no longer does
-      double fl = panel_flops(a.N, a.M, a.d, k, true, gb[g]) + (hasA ? diag_flops(a.N, a.d, k + 1, gb[g]) : 0.0);
-      if (xsplit) fl -= panel_flops(a.N, a.M, a.d, k, false, gb[g]);
-      auto tile_part = [&](int kc, int ncols) {  // Gram + `ncols` inner columns of one 128-row tile of block column kc, all fits
-        const double w = std::min(TS, a.N - kc * TS), rows = std::min(TS, a.N - (kc + 1) * TS);
-        return gb[g] * rows * w * (2.0 * ncols + (3.0 * a.d + 2.0));
-      };
-      if (imgA) fl -= tile_part(k, (k - 1) * TS);
-      if (hasC) fl += tile_part(k + 1, k * TS);
-      if (gx < 1) continue;  // (mid-size call, last block step: the extra rows are all that is left)
-      L[g].begin(0, fl, k);
-      launch_panel_diag<T>(mid, dim3(gx, gb[g]), gs[g], ak, k);
-      L[g].end();
-    }
-  }
-  if (xsplit) {  // join: k_finalize reads the extra rows
-    HIP_TRY(c, hipEventRecord(c->ev_join[0], sE));
-    HIP_TRY(c, hipStreamWaitEvent(gs[0], c->ev_join[0], 0));
-  }
-  for (int g = 0, g0 = 0; g < G; g0 += gb[g], ++g) launch_epilogue<T, 64>(c, L[g], ga[g], ep, gb[g], g0);
-  HIP_TRY(c, hipGetLastError());
-  for (int g = 0; g < G; ++g) {
-    if (gs[g] == s) continue;   // ran on the caller's stream itself
-    hipEvent_t ej = c->ev_join[(g + 1) % cgp_ctx::kMaxStreams];   // ([0] is the extra rows' join)
-    HIP_TRY(c, hipEventRecord(ej, gs[g]));
-    HIP_TRY(c, hipStreamWaitEvent(s, ej, 0));
-  }
-  if (tune.ev1) HIP_TRY(c, hipEventRecord(tune.ev1, s));
-  if (tune.entry) ++tune.entry->state;
-  return CGP_OK;
-}
-
-int run(cgp_ctx *c, const FitArgs &a, int batch, bool in_rows, bool want_alpha, hipStream_t s) {
-  return c->dtype == CGP_F64 ? run_schedule<double>(c, a, batch, in_rows, want_alpha, s)
-                             : run_schedule<float>(c, a, batch, in_rows, want_alpha, s);
-}
+namespace {
 
 FitArgs base_args(cgp_ctx *c, int N, int d, int M, int kid, int include_noise) {
   FitArgs a{};
@@ -1466,28 +818,27 @@ cgp_ctx *cgp_create_ex(int device, int max_n, int max_m, int max_d, int max_batc
   ok = ok && hipMalloc((void **)&c->dtheta, B * CGP_MAX_THETA * sizeof(double)) == hipSuccess;
   ok = ok && hipMalloc((void **)&c->djitter, B * sizeof(double)) == hipSuccess;
   ok = ok && hipMalloc((void **)&c->dgpart, (B * c->NTmax * (c->NTmax + 1) / 2 * GRAD_N + 2) * sizeof(double)) == hipSuccess;  // + logML, info of a single evaluation
-  c->sk_slots = c->NTmax + c->ETmax + 1;
-  c->lat_cap = std::min(LAT_FITS_ALLOC, max_batch);
+  LatBufs &lat = c->lat;
+  lat.sk_slots = c->NTmax + c->ETmax + 1;
+  lat.lat_cap = std::min(LAT_FITS_ALLOC, max_batch);
   // partial-tile slab: the latency schedule takes MORE fits the fewer block steps a window has (lat_fits_by_steps), and a
   // call of NT block steps uses NT + ET + 1 tile slots per fit, so the slab is sized for the largest fits x slots product over
   // the block-step counts this context can see (a max_n = 2048 fp64 context: 11 fits x 22 slots, not 32 x 22) and a call
   // indexes it with its OWN slot count (SplitArgs::slots)
-  size_t lat_units = 0;
   for (int nt = 1; nt <= c->NTmax; ++nt) {
-    const int fits = std::min(c->lat_cap, kAbBuild ? LAT_FITS_ALLOC : lat_fits_by_steps(dtype == CGP_F64, nt));
-    lat_units = std::max(lat_units, (size_t)fits * (nt + c->ETmax + 1));
+    const int fits = std::min(lat.lat_cap, kAbBuild ? LAT_FITS_ALLOC : lat_fits_by_steps(dtype == CGP_F64, nt));
+    lat.lat_units = std::max(lat.lat_units, (size_t)fits * (nt + c->ETmax + 1));
   }
-  c->lat_units = lat_units;
-  ok = ok && hipMalloc(&c->dpart, lat_units * SK_MAX * TS * TS * c->esz) == hipSuccess;
-  ok = ok && hipMalloc((void **)&c->dticket, sizeof(int) * c->lat_cap * c->sk_slots) == hipSuccess;
-  ok = ok && hipMemset(c->dticket, 0, sizeof(int) * c->lat_cap * c->sk_slots) == hipSuccess;
-  ok = ok && hipMalloc((void **)&c->dwready, sizeof(int) * c->lat_cap) == hipSuccess;
+  ok = ok && hipMalloc(&lat.dpart, lat.part_bytes(c->esz)) == hipSuccess;
+  ok = ok && hipMalloc((void **)&lat.dticket, sizeof(int) * lat.lat_cap * lat.sk_slots) == hipSuccess;
+  ok = ok && hipMemset(lat.dticket, 0, sizeof(int) * lat.lat_cap * lat.sk_slots) == hipSuccess;
+  ok = ok && hipMalloc((void **)&lat.dwready, sizeof(int) * lat.lat_cap) == hipSuccess;
   // pre-update images exist from three block steps on (lat_images): sized for the most fits the latency schedule takes there
   int img_fits = 1;
   for (int nt = 3; nt <= std::max(3, c->NTmax); ++nt)
-    img_fits = std::max(img_fits, std::min(c->lat_cap, kAbBuild ? LAT_FITS_ALLOC : lat_fits_by_steps(dtype == CGP_F64, nt)));
-  c->lat_img_fits = c->NTmax >= 3 ? img_fits : 1;
-  ok = ok && hipMalloc(&c->dlatimg, (size_t)c->lat_img_fits * 2 * LAT_IMG_MAX * DPART * c->esz) == hipSuccess;
+    img_fits = std::max(img_fits, std::min(lat.lat_cap, kAbBuild ? LAT_FITS_ALLOC : lat_fits_by_steps(dtype == CGP_F64, nt)));
+  lat.lat_img_fits = c->NTmax >= 3 ? img_fits : 1;
+  ok = ok && hipMalloc(&lat.dlatimg, lat.img_bytes(c->esz)) == hipSuccess;
   ok = ok && hipMalloc((void **)&c->dmacc, sizeof(double) * 2 * B * std::max(c->max_m, 1)) == hipSuccess;
   ok = ok && hipMalloc(&c->ddiagimg, B * 2 * DPART * c->esz) == hipSuccess;
   c->mid_cap = std::min(MID_FITS_ALLOC, max_batch);
@@ -1534,9 +885,14 @@ void cgp_destroy(cgp_ctx *c) {
     (void)hipEventDestroy(r.b);
   }
   for (auto e : c->pool) (void)hipEventDestroy(e);
-  void *bufs[] = {c->Lw, c->Winv, c->dX, c->dXs, c->dy, c->dmean, c->dvar, c->dalpha, c->dtheta, c->djitter, c->dlogml, c->dinfo, c->dprep, c->ddbg, c->dgpart, c->dpart, c->dticket, c->dwready, c->dlatimg, c->la_buf, c->la_ibuf, c->dmacc, c->ddiagimg, c->dpanimg, c->dsmall, c->dsmdeal, c->dsmdone, c->dref_r, c->dref_a, c->dref_flag, c->Lp};
+  void *bufs[] = {c->Lw, c->Winv, c->dX, c->dXs, c->dy, c->dmean, c->dvar, c->dalpha, c->dtheta, c->djitter, c->dlogml, c->dinfo, c->dprep, c->ddbg, c->dgpart, c->la_buf, c->la_ibuf, c->dmacc, c->ddiagimg, c->dpanimg, c->dsmall, c->dsmdeal, c->dsmdone, c->dref_r, c->dref_a, c->dref_flag, c->Lp};
   for (void *p : bufs)
     if (p) (void)hipFree(p);
+  auto drop = [](auto *p) {
+    if (p) (void)hipFree(p);
+  };
+  c->lat.each(drop);
+  c->ol.each(drop);
   for (int i = 0; i < cgp_ctx::kMaxStreams; ++i) {
     if (c->wstream[i]) {
       (void)hipStreamSynchronize(c->wstream[i]);
@@ -1565,8 +921,6 @@ void cgp_destroy(cgp_ctx *c) {
   if (c->pin_in) (void)hipHostFree(c->pin_in);
   if (c->pin_out) (void)hipHostFree(c->pin_out);
   if (c->draw) (void)hipFree(c->draw);
-  for (void *sb : {c->dsched_tasks, c->dsched_flags, c->dsched_bimg, c->dsched_cimg})
-    if (sb) (void)hipFree(sb);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1584,15 +938,15 @@ int cgp_debug_read(cgp_ctx *c, long long out[CGP_DEBUG_SLOTS]) {
 int cgp_debug_buffers(cgp_ctx *c, unsigned long long out[2 * CGP_DEBUG_BUFFERS]) {
   if (!c || !out) return CGP_EINVAL;
   const size_t B = c->max_batch;
-  const void *p[CGP_DEBUG_BUFFERS] = {c->Lw, c->Winv, c->ddiagimg, c->dpanimg, c->dX, c->dmacc, c->dpart, c->dlatimg};
+  const void *p[CGP_DEBUG_BUFFERS] = {c->Lw, c->Winv, c->ddiagimg, c->dpanimg, c->dX, c->dmacc, c->lat.dpart, c->lat.dlatimg};
   const size_t n[CGP_DEBUG_BUFFERS] = {B * c->lw_stride * c->esz,
                                        B * c->winv_stride * c->esz,
                                        B * 2 * DPART * c->esz,
                                        (size_t)c->mid_cap * 2 * DPART * c->esz,
                                        B * c->max_d * c->max_n * c->esz,
                                        sizeof(double) * 2 * B * std::max(c->max_m, 1),
-                                       c->lat_units * SK_MAX * TS * TS * c->esz,
-                                       (size_t)c->lat_img_fits * 2 * LAT_IMG_MAX * DPART * c->esz};
+                                       c->lat.part_bytes(c->esz),
+                                       c->lat.img_bytes(c->esz)};
   for (int i = 0; i < CGP_DEBUG_BUFFERS; ++i) {
     out[2 * i] = (unsigned long long)(uintptr_t)p[i];
     out[2 * i + 1] = n[i];

@@ -17,7 +17,7 @@ between two 64 KiB guards, and asserts
 Which schedule a fit case reaches is ASSERTED (test_fit_cases_reach_the_schedules_named, with cgp_profile_enable /
 cgp_profile_read: the one-launch short-window kernel records no launch, the latency schedule records k_trmm_sk launches and no
 potf2 launch, the mid-size and throughput schedules a potf2 launch and no trmm launch).  What is expected there, from
-fit_predict_device, small_batch_predict_ok and run_schedule of csrc/cgp_engine.hip as they stand:
+fit_predict_device, small_batch_predict_ok of csrc/cgp_engine.hip and sched_plan of csrc/cgp_sched_plan.hpp as they stand:
   - cgp_fit_predict_batch_device and the sweep in fp64, SE and RBF x Brownian kernels: N <= 144 for any d, N <= 160 at d <= 2
     (SM_MAX_NB = 10 blocks of 16 and the LDS bound) and M > 0 run k_small_predict -- (3, 15, 20) AND (3, 129, 17).  The issue's
     "tiled, two block steps, latency schedule" is therefore reached in fp64 by (3, 161, 17) -- the shortest window that is tiled at

@@ -8,7 +8,7 @@ info == p + 1, the healthy fits of a call BITWISE those of a control call withou
 call.  Shape: N = 264 = 128 + 128 + 8 (three block steps, the last 16-block partial), d = 3, M = 20; positions in the first
 block, on a 16-block boundary, on the tile boundary, inside tile 1, at the first pivot of the partial tile and in the last row.
 
-Which schedule a call of B fits takes at three block steps, from run_schedule of csrc/cgp_engine.hip as its constants stand:
+Which schedule a call of B fits takes at three block steps, from sched_plan of csrc/cgp_sched_plan.hpp as its constants stand:
     latency     B <= lat_fits_by_steps(fp64, 3) = 28 (fp64) / 24 (fp32)      k_tile_sk / k_trmm_sk: potf2_tile, the pivot merged through *flag
     mid-size    B <= mid_fits(3) = MID_FITS_F64 = 48 / MID_FITS_F32 = 96     k_diag_lean for tile 0, tiles 1 and 2 inside k_panel (diag_next) from pre-update
                                                                              images; fp32 factors the diagonal tile in the fat form here (potf2_tile)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Guards the engine's schedule table (csrc/cgp_engine.hip: lat_fits_by_steps, mid_fits, FUSED64_BELOW): the crossovers were
+"""Guards the engine's schedule table (csrc/cgp_sched_plan.hpp: lat_fits_by_steps, mid_fits, FUSED64_BELOW): the crossovers were
 measured on single boxes while box-to-box spread is several per cent, so nothing but a re-measurement says the shipped
 choice is still the faster one.  For points either side of every switch this times the SAME call three ways through the
 measurement library (libcorenav_gp_ab.so, same kernels; its environment overrides force a schedule) -- the shipped choice
