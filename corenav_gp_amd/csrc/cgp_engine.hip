@@ -16,6 +16,7 @@
 #include "cgp_joint.hpp"
 #include "cgp_multi.hpp"
 #include "cgp_multi_grad.hpp"
+#include "cgp_trend.hpp"
 #include "cgp_pgrad.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
@@ -115,6 +116,11 @@ struct WinMultiGradBufs {   // cgp_window_multi_grad_reserve: the A scratch [nwi
   double *am = nullptr, *colval = nullptr;   // per-column values [nwin][P] a call without a logml buffer writes
   template <class F> void each(F &&f) { f(am); f(colval); }
 };
+struct WinTrendBufs {   // cgp_window_trend_reserve: the contraction of all P columns [nwin][P][max_m] | their evidence [nwin][P],
+  double *mean0 = nullptr, *sl = nullptr;   // and S [nwin][P up to 16][16] | L_A^-1 [nwin][16][16] (cgp_trend.hpp)
+  int q = 0, max_m = 0;                     // the reservation's basis columns and test points; 0 = none
+  template <class F> void each(F &&f) { f(mean0); f(sl); }
+};
 struct WinLooGradBufs {   // cgp_window_loo_grad_reserve: Ky^-1 of every window [nwin][NP][NP], NP = N rounded up to 64 (null = none),
   double *kinv = nullptr, *blk = nullptr;   // and one block of per-sample vectors, partial sums and per-window values (WindowLooGradPlan)
   template <class F> void each(F &&f) { f(kinv); f(blk); }
@@ -182,12 +188,13 @@ struct cgp_ctx {
   int nwin = 0;
   int win_o = 0, win_n = 0;   // origin / size of the windows (they advance in lock-step), mirrored on the host to cut a push into launches
   // their buffers and the four reservations' (the records above name every member and its shape).  Lifetimes, as window_drop
-  // states them: the windows go -> every reservation goes; the multi-target reservation goes -> its objective's scratch goes;
+  // states them: the windows go -> every reservation goes; the multi-target reservation goes -> its objective's and its trend's scratch go;
   // the joint forecast's and the leave-one-out objective's scratch go alone.
   WinBufs wb;            // cgp_window_init (win points into it)
   WinJointBufs wj;       // joint forecast: cgp_window_joint_reserve
   WinMultiBufs wm;       // multi-target windows: cgp_window_multi_reserve
   WinMultiGradBufs wg;   // their summed objective: cgp_window_multi_grad_reserve
+  WinTrendBufs wt;       // explicit basis functions on the multi-target windows: cgp_window_trend_reserve
   WinLooGradBufs wl;     // leave-one-out objective: cgp_window_loo_grad_reserve
   // joint forecast after batch / single fits (cgp_joint_reserve): the posterior covariance or its factor [max_batch][(mt * 16)^2],
   // then the factorisations' failure words [max_batch]; staging of the host sampling calls [xi | out]
@@ -196,6 +203,11 @@ struct cgp_ctx {
   // staging of the host call [Y | mean | logml]
   Scratch mz;
   int mz_form = 0;   // cgp_multi_set_form: 0 = the engine picks the solve's tile height, 64 / 128 = as told (tests)
+  // explicit basis functions after the multi-target fits (cgp_trend_reserve): per fit the contraction and the evidence of the
+  // max_dim + 16 packed columns, S = G^T [Z | G] and L_A^-1 (cgp_trend_host.hpp, trend_layout); staging of the host call
+  // [Y | H | Hs | mean | beta | logml | tinfo]
+  Scratch tr;
+  int tr_max_m = 0;
   // multi-target objective (cgp_multi_grad_reserve): A = Ky^-1 Y of up to max_batch fits x max_dim targets, [fit][P padded to 16][NT 128],
   // then (max_batch, max_dim) logml; staging of the host calls [Y | nll | grad | logml]
   Scratch ma;
@@ -384,7 +396,7 @@ int node_callback_small(cgp_ctx *c, const double *time_array, const double *slip
                         double *mean, double *sigma, int cap, int *m_out);
 bool grow_pinned(void *&p, size_t &cap, size_t bytes);
 bool grow_device(void *&p, size_t &cap, size_t bytes);
-enum class WinDrop { Windows, Multi, MultiGrad, Joint, LooGrad };
+enum class WinDrop { Windows, Multi, MultiGrad, Trend, Joint, LooGrad };
 void window_drop(cgp_ctx *c, WinDrop what);   // cgp_window_host.hpp: frees what goes with `what`
 // What a batch entry point with more than mean / variance to compute (joint, multi-target, predictive-gradient calls) enqueues on s
 // for the `nfit` fits whose panels are slabs slab, slab + 1, ... into the slots slot, slot + 1, ... of its own arrays, while the
@@ -914,7 +926,7 @@ void cgp_destroy(cgp_ctx *c) {
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
   window_drop(c, WinDrop::Windows);
-  for (Scratch *r : {&c->fj, &c->mz, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
+  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -1958,6 +1970,8 @@ extern "C" int cgp_slip_node_callback_opt(cgp_ctx *c, const double *time_array, 
 #include "cgp_joint_host.hpp"
 // multi-target fits: cgp_multi_reserve ... cgp_fit_predict_multi_batch_device
 #include "cgp_multi_host.hpp"
+// explicit basis functions (trend) after the multi-target fits: cgp_trend_reserve ... cgp_fit_predict_trend_batch_device
+#include "cgp_trend_host.hpp"
 
 struct cgp_recorder {
   corenav::SlipWindowRecorder r;

@@ -312,6 +312,7 @@ void window_drop(cgp_ctx *c, WinDrop what) {   // (declared in cgp_engine.hip fo
   if (all) window_release(c->wb);
   if (all || what == WinDrop::Multi) window_release(c->wm);
   if (all || what == WinDrop::Multi || what == WinDrop::MultiGrad) window_release(c->wg);
+  if (all || what == WinDrop::Multi || what == WinDrop::Trend) window_release(c->wt);
   if (all || what == WinDrop::LooGrad) window_release(c->wl);
   if (all || what == WinDrop::Joint) window_release(c->wj);
 }
@@ -740,6 +741,98 @@ extern "C" int cgp_window_predict_multi(cgp_ctx *c, int M, int P, const double *
   memcpy(mean, h + nx, nm * 8);
   memcpy(var, h + nx + nm, nv * 8);
   if (logml) memcpy(logml, h + nx + nm + nv, nl * 8);
+  return rc;
+}
+
+// ---- explicit basis functions on the multi-target windows (cgp_trend.hpp): the last q of the P columns are the basis ----------
+namespace {
+// the checks the two calls start with, before anything is enqueued
+int window_trend_check(const cgp_ctx *c, int M, int P, int q, bool args_ok) {
+  if (!c) return CGP_ESTATE;
+  if (c->dtype != CGP_F64) return CGP_EINVAL;
+  if (c->nwin < 1 || c->wm.P < 1 || c->wt.q < 1) return CGP_ESTATE;
+  if (P != c->wm.P || q != c->wt.q || M < 1 || !args_ok) return CGP_EINVAL;
+  if (M > c->wt.max_m) return CGP_ECAPACITY;
+  return CGP_OK;
+}
+}  // namespace
+
+extern "C" int cgp_window_trend_reserve(cgp_ctx *c, int q, int max_m) {
+  if (!c) return CGP_ESTATE;
+  if (c->dtype != CGP_F64) return CGP_EINVAL;
+  if (c->nwin < 1 || c->wm.P < 1) return CGP_ESTATE;
+  if (q < 1 || q > TR_MAX || q >= c->wm.P || max_m < 1) return CGP_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());   // an earlier reservation's buffers are idle
+  window_drop(c, WinDrop::Trend);
+  const size_t W = c->nwin, P = c->wm.P, ncol = (size_t)cdiv(c->wm.P, TR_MAX) * TR_MAX;
+  const WinSlot slots[] = {slot(c->wt.mean0, W * (P * max_m + P) * 8), slot(c->wt.sl, W * (ncol + TR_MAX) * TR_MAX * 8)};
+  if (window_alloc(c, WinDrop::Trend, slots) != CGP_OK) return CGP_ENOMEM;
+  c->wt.q = q;
+  c->wt.max_m = max_m;
+  return CGP_OK;
+}
+
+// cgp_window_predict_multi_device's three launches over all P columns into the reservation's scratch, then the three trend launches
+// (gram over the Z scratch, solve, apply).  Reads the windows and writes the two scratches only.
+extern "C" int cgp_window_predict_trend_device(cgp_ctx *c, int M, int P, int q, const double *dxs, const double *dHs, int include_noise,
+                                               double *dmean, double *dvar, double *dbeta, double *dlogml, int *dtinfo,
+                                               void *hip_stream) {
+  int rc = window_trend_check(c, M, P, q, dxs && dHs && dmean && dvar && dbeta && dlogml && dtinfo);
+  if (rc != CGP_OK) return rc;
+  const size_t W = c->nwin;
+  double *mean0 = c->wt.mean0, *logml0 = mean0 + W * P * M;
+  if ((rc = cgp_window_predict_multi_device(c, M, P, dxs, include_noise, mean0, dvar, logml0, hip_stream)) != CGP_OK) return rc;
+  hipStream_t ws = pick_stream(c, hip_stream);
+  TrendArgs a{};
+  a.N = c->win.N; a.M = M; a.P = P - q; a.q = q; a.nfit = c->nwin;
+  a.ncol = cdiv(P, TR_MAX) * TR_MAX;
+  a.S = c->wt.sl;
+  a.Linv = a.S + W * a.ncol * TR_MAX;
+  a.mean0 = mean0;
+  a.logml0 = logml0;
+  a.Hs = dHs;
+  a.mean = dmean; a.var = dvar; a.beta = dbeta; a.logml = dlogml;
+  a.info = c->win.state + 2;
+  a.info_stride = 4;
+  a.tinfo = dtinfo;
+  a.zs = c->wm.zs;
+  a.state = c->win.state;
+  a.pt = cdiv(P, WPB);
+  a.nrow = cdiv(c->win.N, WPB) * WPB;
+  hipLaunchKernelGGL(k_trend_gram<true>, dim3(a.ncol / TR_MAX, a.nfit), dim3(TG_WAVES * 64), 0, ws, a);
+  hipLaunchKernelGGL(k_trend_solve, dim3(a.nfit), dim3(64), 0, ws, a);
+  hipLaunchKernelGGL(k_trend_apply, dim3(cdiv(M, TA_THREADS), cdiv(a.P, TA_PCH), a.nfit), dim3(TA_THREADS), 0, ws, a);
+  if (!hip_ok(c, hipGetLastError(), "window trend launches")) return CGP_EHIP;
+  return CGP_OK;
+}
+
+extern "C" int cgp_window_predict_trend(cgp_ctx *c, int M, int P, int q, const double *xs, const double *Hs, int include_noise,
+                                        double *mean, double *var, double *beta, double *logml, int *tinfo) {
+  int rc = window_trend_check(c, M, P, q, xs && Hs && mean && var);
+  if (rc != CGP_OK) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  // one pinned block [xs | Hs | mean | var | beta | logml | tinfo (as doubles' room) | state] and its device twin
+  const size_t W = c->nwin, Pt = P - q, nx = W * M * c->win.d, nh = W * q * M, nm = W * Pt * M, nv = W * M, nb = W * Pt * q, nl = W * Pt,
+               nt = (W + 1) / 2, nin = nx + nh;
+  double *h;
+  rc = window_staged_call(c, nin, nm + nv + nb + nl + nt, nm + nv + nb + nl + nt, false, h,
+                          [&](double *hx) {
+                            memcpy(hx, xs, nx * 8);
+                            memcpy(hx + nx, Hs, nh * 8);
+                          },
+                          [&](double *io, hipStream_t s) {
+                            double *o = io + nin;
+                            return cgp_window_predict_trend_device(c, M, P, q, io, io + nx, include_noise, o, o + nm, o + nm + nv,
+                                                                   o + nm + nv + nb, reinterpret_cast<int *>(o + nm + nv + nb + nl), s);
+                          });
+  if (rc < 0) return rc;
+  const double *o = h + nin;
+  memcpy(mean, o, nm * 8);
+  memcpy(var, o + nm, nv * 8);
+  if (beta) memcpy(beta, o + nm + nv, nb * 8);
+  if (logml) memcpy(logml, o + nm + nv + nb, nl * 8);
+  if (tinfo) memcpy(tinfo, o + nm + nv + nb + nl, W * sizeof(int));
   return rc;
 }
 

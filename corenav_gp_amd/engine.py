@@ -105,6 +105,10 @@ _SIGS = {
                                                                                 ctypes.c_int, _dp, _dp, _dp, _ip]),
     "cgp_fit_predict_multi_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp, _vp, _vp, _vp, _vp,
                                                                                        ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "cgp_trend_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "cgp_fit_predict_trend_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_dp] * 6 + [ctypes.c_int, ctypes.c_int,
+                                                                                          _dp, _dp, _dp, _dp, _ip, _ip]),
+    "cgp_fit_predict_trend_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp] * 7 + [ctypes.c_int] + [_vp] * 7),
     "cgp_multi_grad_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
     "cgp_multi_nll_grad_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp, _dp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int,
                                                                              _dp, _ip]),
@@ -139,6 +143,11 @@ _SIGS = {
     "cgp_window_loo": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "cgp_window_loo_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cgp_window_optimize": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, ctypes.c_int, _dp, _ip]),
+    "cgp_window_trend_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "cgp_window_predict_trend": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                                _dp, _dp, _dp, _dp, _ip]),
+    "cgp_window_predict_trend_device": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int]
+                                        + [_vp] * 6),
     "cgp_window_multi_grad_reserve": (ctypes.c_int, [_vp]),
     "cgp_window_multi_nll_grad": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp]),
     "cgp_window_multi_nll_grad_device": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp]),
@@ -594,6 +603,34 @@ class Context:
                                                                      djitter or None, int(include_noise), dmean, dvar,
                                                                      dlogml, dinfo, ctypes.c_void_p(stream)))
 
+    # -- explicit basis functions (a trend with a vague prior) after the multi-target fits (fp64 contexts) -----
+    def trend_reserve(self, max_batch, max_p, max_m):
+        """Scratch for the two calls below; needs a multi_reserve that covers (max_batch, max_p + 16)."""
+        return self._chk(self.lib.cgp_trend_reserve(self.h, int(max_batch), int(max_p), int(max_m)))
+
+    def fit_predict_trend_batch(self, X, Y, H, Xs, Hs, theta, kernel_id, include_noise=True):
+        """X (B, N, d), Y (B, P, N), H (B, q, N) -- the basis at the samples --, Xs (B, M, d), Hs (B, q, M), theta (B, nth) ->
+        (rc, mean (B, P, M), var (B, M), beta (B, P, q), logml (B, P), info (B,), tinfo (B,)).  A fit whose info stays
+        non-zero, or whose q x q normal equations fail the rank rule (tinfo = the 1-based pivot), has NaN outputs."""
+        X, Y, H, Xs, Hs, theta = _d(X), _d(Y), _d(H), _d(Xs), _d(Hs), _d(theta)
+        B, N, d = X.shape
+        P, M, q = Y.shape[1], Xs.shape[1], H.shape[1]
+        assert Y.shape == (B, P, N) and H.shape == (B, q, N) and Hs.shape == (B, q, M)
+        mean, var, beta = np.empty((B, P, M)), np.empty((B, M)), np.empty((B, P, q))
+        logml, info, tinfo = np.empty((B, P)), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_fit_predict_trend_batch(self.h, B, N, d, M, P, q, kernel_id, _p(X), _p(Y), _p(H), _p(Xs),
+                                                            _p(Hs), _p(theta), theta.shape[1], int(include_noise), _p(mean),
+                                                            _p(var), _p(beta), _p(logml), info.ctypes.data_as(_ip),
+                                                            tinfo.ctypes.data_as(_ip)))
+        return rc, mean, var, beta, logml, info, tinfo
+
+    def fit_predict_trend_batch_device(self, B, N, d, M, P, q, kernel_id, dX, dY, dH, dXs, dHs, dtheta, djitter,
+                                       include_noise, dmean, dvar, dbeta, dlogml, dinfo, dtinfo, stream=0):
+        """Device pointers as fit_predict_multi_batch_device; dH (B, q, N), dHs (B, q, M), dbeta (B, P, q), dtinfo (B,) int32."""
+        return self._chk(self.lib.cgp_fit_predict_trend_batch_device(self.h, B, N, d, M, P, q, kernel_id, dX, dY, dH, dXs, dHs,
+                                                                     dtheta, djitter or None, int(include_noise), dmean, dvar,
+                                                                     dbeta, dlogml, dinfo, dtinfo, ctypes.c_void_p(stream)))
+
     # -- multi-target fits: gradient and optimiser of the summed logML (fp64 contexts) ------------------------
     def multi_grad_reserve(self, max_batch, max_p):
         """Scratch for the three calls below (A = Ky^-1 Y); needs a multi_reserve that covers it."""
@@ -668,6 +705,7 @@ class Context:
         self._win_nth = ntheta(kernel_id, d)
         self._win_n = N
         self._win_p = 0   # (a multi-target reservation goes with the windows it was made for)
+        self._win_q = 0
         self._chk(self.lib.cgp_window_init(self.h, nwin, N, d, kernel_id, _p(theta), theta.shape[1]))
 
     def window_push(self, xs, ys, include_noise=True, check=True):
@@ -742,6 +780,7 @@ class Context:
         window_init, while the windows are empty.  From here on the windows are fed with window_push_multi."""
         rc = self._chk(self.lib.cgp_window_multi_reserve(self.h, int(P)))
         self._win_p = int(P)
+        self._win_q = 0   # (a trend reservation goes with the multi-target one)
         return rc
 
     def window_push_multi(self, xs, Ys, include_noise=True, check=True):
@@ -785,6 +824,37 @@ class Context:
         """Device pointers (ints; dlogml 0 / None = not wanted)."""
         return self._chk(self.lib.cgp_window_predict_multi_device(self.h, M, P, dxs, int(include_noise), dmean, dvar,
                                                                   dlogml or None, ctypes.c_void_p(stream)))
+
+    def window_trend_reserve(self, q, max_m):
+        """Explicit basis functions on the multi-target windows: the last q of the P pushed columns are the basis at the
+        samples (1 <= q < P, q <= 16); scratch for forecasts of up to max_m test points.  After window_multi_reserve."""
+        rc = self._chk(self.lib.cgp_window_trend_reserve(self.h, int(q), int(max_m)))
+        self._win_q = int(q)
+        return rc
+
+    def window_predict_trend(self, xs, Hs, include_noise=True, check=True):
+        """xs (nwin, M, d), Hs (nwin, q, M) -> mean (nwin, P - q, M), var (nwin, M), beta (nwin, P - q, q), logml (nwin, P - q),
+        tinfo (nwin,).  A failed window raises CgpError (check=False: the code is returned last); a window whose normal
+        equations fail the rank rule has NaN outputs and its 1-based pivot in tinfo."""
+        nwin, d = self._win
+        P, q = self._win_p, self._win_q
+        xs = _d(xs).reshape(nwin, -1, d)
+        M = xs.shape[1]
+        Hs = _d(Hs).reshape(nwin, q, M)
+        mean, var = np.empty((nwin, P - q, M)), np.empty((nwin, M))
+        beta, logml, tinfo = np.empty((nwin, P - q, q)), np.empty((nwin, P - q)), np.zeros(nwin, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_window_predict_trend(self.h, M, P, q, _p(xs), _p(Hs), int(include_noise), _p(mean), _p(var),
+                                                         _p(beta), _p(logml), tinfo.ctypes.data_as(_ip)))
+        if not check:
+            return mean, var, beta, logml, tinfo, rc
+        if rc > 0:
+            raise CgpError(rc)
+        return mean, var, beta, logml, tinfo
+
+    def window_predict_trend_device(self, M, P, q, dxs, dHs, include_noise, dmean, dvar, dbeta, dlogml, dtinfo, stream=0):
+        """Device pointers (ints), all required."""
+        return self._chk(self.lib.cgp_window_predict_trend_device(self.h, M, P, q, dxs, dHs, int(include_noise), dmean, dvar,
+                                                                  dbeta, dlogml, dtinfo, ctypes.c_void_p(stream)))
 
     def window_joint_reserve(self, max_m):
         """Scratch for joint forecasts (window_predict_cov / window_sample) of up to max_m test points per window; once

@@ -503,6 +503,72 @@ int cgp_fit_predict_multi_batch_device(cgp_ctx *ctx, int batch, int N, int d, in
  * (batch, P) only).  The two forms agree bitwise per element; anything else is CGP_EINVAL. */
 int cgp_multi_set_form(cgp_ctx *ctx, int rows);
 
+/* ---- explicit basis functions (a trend) after the multi-target fits ----------------------------------------
+ * Every model above has a zero prior mean: a forecast a few length-scales past the last sample returns to 0.  This section fits
+ * f(x) = g(x) + h(x)^T beta, g the zero-mean GP and beta the coefficients of q basis functions the CALLER evaluates (a constant, a
+ * linear term, a commanded-speed regressor), integrated out under a vague prior (Rasmussen & Williams 2.7, eqs. 2.41, 2.42, 2.45).
+ * Per fit, with Ky = K + (sigma_n^2 + 1e-8 [+ jitter]) I = L L^T, Y (N x P) the targets, H (N x q) the basis at the samples, Hs
+ * (M x q) the basis at the test points:
+ *   Z = L^-1 Y        G = L^-1 H        V = L^-1 K(X, Xs)
+ *   A = G^T G (q x q) = L_A L_A^T      B = G^T Z (q x P)      beta[:, p] = A^-1 B[:, p]
+ *   R = Hs^T - G^T V   (q x M)
+ *   mean[p, m] = sum_i V[i, m] Z[i, p] + sum_r R[r, m] beta[r, p]
+ *   var[m]     = max(k(xs_m, xs_m) - sum_i V[i, m]^2, 1e-15) (+ sigma_n^2 when include_noise) + |L_A^-1 R[:, m]|^2
+ *   logml[p]   = -1/2 sum_i Z[i, p]^2 + 1/2 B[:, p]^T beta[:, p] - sum_i log L_ii - sum_r log (L_A)_rr - (N - q)/2 log 2 pi
+ * The first term of var (with its noise term) is the fit's own variance, by the same code and to the same bits as
+ * cgp_fit_predict_multi_batch's var; the last term is the price of not knowing beta and is >= 0.
+ *
+ * Rank rule.  A is factored by an unpivoted Cholesky in index order.  Pivot r fails when it is not > 1e-10 A[r][r], A[r][r] the
+ * entry before elimination; NaN and negative pivots fail the same test.  Then tinfo of that fit takes the 1-based r, all of its
+ * trend outputs (mean, var, beta, logml) are NaN and its neighbours are untouched.  q <= N is not required: the rule answers.  A fit
+ * whose own info is non-zero has NaN outputs and tinfo = 0.
+ *
+ * How it runs.  [Y | H] are packed as P + q columns of the multi-target machinery (column 0 = target 0, so the fit schedule sees
+ * what it sees in cgp_fit_predict_multi_batch): L^-1 H and G^T V come out of the multi-target solve and contraction on q more
+ * columns.  Three more launches follow: S = G^T [Z | G] on the fp64 matrix cores, the q x q factorisation with beta and the
+ * evidence terms (one wave per fit), and the correction of mean and var.  CGP_F64 contexts only: CGP_EINVAL in a CGP_F32 context
+ * before anything is enqueued.  All five kernel ids.
+ *
+ * Layouts.  X, Y, Xs, theta, mean, var, logml, info as in the multi-target section; H (batch, q, N) and Hs (batch, q, M), laid out
+ * like Y (each basis function contiguous over the samples / the test points); beta (batch, P, q); tinfo (batch).  Device variant:
+ * dX / dXs / dtheta / djitter as cgp_fit_predict_batch_device.
+ *
+ * Determinism.  A column's mean row, beta row and logml are a function of its own data, of the basis and of the schedule the
+ * call's number of fits selects: never of p, P, the other target columns, the fit's slot or the neighbours.  Permuting the target
+ * columns permutes mean, beta and logml bitwise; the first columns of a wide call are bitwise the same columns run alone.  No
+ * atomics; every sum runs in a fixed order over the REAL N samples.  Host form, device form and a replayed graph agree bitwise.  A
+ * trend call leaves a following multi-target call bitwise what it is without it.  Between two schedules results agree to 1e-9.
+ *
+ * cgp_trend_reserve: scratch for the contraction and the evidence of the packed columns, S and L_A^-1: about max_batch x (max_p +
+ * 16) x (max_m + 17) doubles.  It needs a cgp_multi_reserve that covers (max_batch, max_p + CGP_MAX_TREND), else CGP_ESTATE.  1 <=
+ * max_batch <= the context's, 1 <= max_p <= 4096 - 16, 1 <= max_m <= the context's, else CGP_EINVAL; CGP_ENOMEM leaves no
+ * reservation; calling it again replaces the reservation.  Blocks.  cgp_destroy frees it.
+ *
+ * Status of the two calls, in this order: CGP_EINVAL in a CGP_F32 context, for M < 1, P < 1 or q outside 1 .. CGP_MAX_TREND;
+ * without a trend reservation CGP_ESTATE; batch, P or M beyond it CGP_ECAPACITY; a multi-target reservation that no longer
+ * covers (batch, P + q) CGP_ESTATE / CGP_ECAPACITY; a NULL required pointer or theta_stride < ntheta CGP_EINVAL; shape errors
+ * otherwise as cgp_fit_predict_batch.
+ *
+ * Not provided: theta-gradients and an optimiser of the trend evidence; joint covariance, leave-one-out and predictive gradients
+ * with a trend; a single-fit form; fp32 contexts; a cgp_sweep_* form. */
+#define CGP_MAX_TREND 16
+int cgp_trend_reserve(cgp_ctx *ctx, int max_batch, int max_p, int max_m);
+/* cgp_fit_predict_trend_batch: blocks; the jitter ladder per fit exactly as cgp_fit_predict_multi_batch runs it (a retried fit's
+ * trend is computed right after its retry, into its own slot).  beta, logml, info and tinfo may be NULL.  Returns a negative
+ * error, else 0 or the first non-zero per-fit info (a failed rank rule is reported in tinfo only). */
+int cgp_fit_predict_trend_batch(cgp_ctx *ctx, int batch, int N, int d, int M, int P, int q, int kernel_id,
+                                const double *X, const double *Y, const double *H, const double *Xs, const double *Hs,
+                                const double *theta, int theta_stride, int include_noise,
+                                double *mean, double *var, double *beta, double *logml, int *info, int *tinfo);
+/* Device-resident variant: cgp_fit_predict_multi_batch_device's launches (with a pack of its own) plus three; no allocation, no
+ * synchronisation, no jitter ladder (capturable into a hipGraph).  Every output pointer is required.  The extent contract at
+ * cgp_fit_predict_batch_device applies. */
+int cgp_fit_predict_trend_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, int P, int q, int kernel_id,
+                                       const double *dX, const double *dY, const double *dH, const double *dXs,
+                                       const double *dHs, const double *dtheta, const double *djitter, int include_noise,
+                                       double *dmean, double *dvar, double *dbeta, double *dlogml, int *dinfo, int *dtinfo,
+                                       void *hip_stream);
+
 /* ---- multi-target fits: gradient and optimiser of the summed logML ------------------------------------
  * m.optimize() of the multi-column model (gp_slip_node.py:36 with Y (N, P)): ONE theta per fit maximises
  *   sum_p logml[p] = -P/2 log|Ky| - 1/2 tr(Y^T Ky^-1 Y) - N P / 2 log 2 pi.
@@ -795,6 +861,37 @@ int cgp_window_predict_multi(cgp_ctx *ctx, int M, int P, const double *xs, int i
  * outputs and cgp_window_state do. */
 int cgp_window_predict_multi_device(cgp_ctx *ctx, int M, int P, const double *dxs, int include_noise,
                                     double *dmean, double *dvar, double *dlogml, void *hip_stream);
+
+/* ---- explicit basis functions (a trend) on the multi-target windows ------------------------------------------
+ * The window form of the trend section above (its formulas, its rank rule, on the window's n samples).  The basis at the samples
+ * is what the caller pushed as the LAST q COLUMNS of a multi-target context (cgp_window_push_multi with P = targets + q): basis
+ * values travel through the target store like any column and the push path is not touched.  The first P - q columns are the
+ * targets.  Needs cgp_window_multi_reserve's P and 1 <= q < P, q <= CGP_MAX_TREND.
+ *
+ * cgp_window_trend_reserve: after cgp_window_multi_reserve, at any fill state of the windows (CGP_ESTATE without windows or
+ * without that reservation; CGP_EINVAL in a CGP_F32 context, for q outside 1 .. min(P - 1, CGP_MAX_TREND) or max_m < 1): nwin x
+ * (P (max_m + 1) + 16 (P rounded up to 16) + 256) doubles.  CGP_ENOMEM leaves no reservation; calling it again replaces it;
+ * cgp_window_multi_reserve, cgp_window_init and cgp_destroy drop it.  Blocks.
+ *
+ * cgp_window_predict_trend: xs (nwin, M, d), Hs (nwin, q, M); mean (nwin, P - q, M), var (nwin, M), beta (nwin, P - q, q), logml
+ * (nwin, P - q), tinfo (nwin); beta, logml and tinfo may be NULL.  A window with n < q samples, the empty window included, has a
+ * rank-deficient A and answers by the rank rule: NaN, tinfo = n + 1 for a basis in general position (a vague prior has no forecast
+ * to give there).  A window that lost positive definiteness answers NaN with tinfo = 0; cgp_window_set_theta revives it with no
+ * further call.  Read-only on the windows: a push after the call is bitwise the push without it.  Status: CGP_EINVAL in a CGP_F32
+ * context; CGP_ESTATE without windows or with either reservation missing; CGP_EINVAL for a P or q that is not the
+ * reservations', M < 1 or a NULL required pointer; CGP_ECAPACITY for M > max_m; else 0 or, like cgp_window_predict, the 1-based
+ * tick at which a window failed.  Blocks.  Host form, device form, a replayed graph and a window's slot do not change a bit of a
+ * window's outputs.  Stream exclusion as cgp_window_predict_multi (the scratch of the diagonal blocks' inverses and the Z scratch
+ * are shared with it).  What the trend section does not provide is not provided here either. */
+int cgp_window_trend_reserve(cgp_ctx *ctx, int q, int max_m);
+int cgp_window_predict_trend(cgp_ctx *ctx, int M, int P, int q, const double *xs, const double *Hs, int include_noise,
+                             double *mean, double *var, double *beta, double *logml, int *tinfo);
+/* Device-resident variant: device pointers, all required; cgp_window_predict_multi_device's three launches and three more on
+ * hip_stream, without allocation, attribute call or synchronisation (capturable).  Nothing outside the documented extents is
+ * written, every documented element is written. */
+int cgp_window_predict_trend_device(cgp_ctx *ctx, int M, int P, int q, const double *dxs, const double *dHs, int include_noise,
+                                    double *dmean, double *dvar, double *dbeta, double *dlogml, int *dtinfo,
+                                    void *hip_stream);
 
 /* ---- hyper-parameters of the resident windows, replaced and re-estimated in place ----------------
  * The reference re-estimates its hyper-parameters on every window (gp_slip_node.py:36, m.optimize()); cgp_window_init fixes
