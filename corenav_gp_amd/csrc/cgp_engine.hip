@@ -17,6 +17,7 @@
 #include "cgp_multi.hpp"
 #include "cgp_multi_grad.hpp"
 #include "cgp_trend.hpp"
+#include "cgp_sparse.hpp"
 #include "cgp_pgrad.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
@@ -208,6 +209,10 @@ struct cgp_ctx {
   // [Y | H | Hs | mean | beta | logml | tinfo]
   Scratch tr;
   int tr_max_m = 0;
+  // sparse (inducing-point) fits (cgp_sparse_reserve): all the scratch of the sparse calls, for up to max_batch fits of max_dim
+  // inducing inputs and sp_max_n samples (cgp_sparse_host.hpp, sparse_layout); staging of the host call
+  Scratch sp;
+  int sp_max_n = 0, sp_max_m = 0;
   // multi-target objective (cgp_multi_grad_reserve): A = Ky^-1 Y of up to max_batch fits x max_dim targets, [fit][P padded to 16][NT 128],
   // then (max_batch, max_dim) logml; staging of the host calls [Y | nll | grad | logml]
   Scratch ma;
@@ -926,7 +931,7 @@ void cgp_destroy(cgp_ctx *c) {
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
   window_drop(c, WinDrop::Windows);
-  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
+  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->sp, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -1972,6 +1977,8 @@ extern "C" int cgp_slip_node_callback_opt(cgp_ctx *c, const double *time_array, 
 #include "cgp_multi_host.hpp"
 // explicit basis functions (trend) after the multi-target fits: cgp_trend_reserve ... cgp_fit_predict_trend_batch_device
 #include "cgp_trend_host.hpp"
+// sparse (inducing-point) fits: cgp_sparse_reserve ... cgp_fit_predict_sparse_batch_device
+#include "cgp_sparse_host.hpp"
 
 struct cgp_recorder {
   corenav::SlipWindowRecorder r;

@@ -106,6 +106,11 @@ _SIGS = {
     "cgp_fit_predict_multi_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp, _vp, _vp, _vp, _vp,
                                                                                        ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cgp_trend_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "cgp_sparse_chunk": (ctypes.c_int, []),
+    "cgp_sparse_reserve": (ctypes.c_int, [_vp] + [ctypes.c_int] * 4),
+    "cgp_fit_predict_sparse_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_dp] * 5 + [ctypes.c_int, ctypes.c_int,
+                                                                                             _dp, _dp, _dp, _ip]),
+    "cgp_fit_predict_sparse_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp] * 6 + [ctypes.c_int] + [_vp] * 5),
     "cgp_fit_predict_trend_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_dp] * 6 + [ctypes.c_int, ctypes.c_int,
                                                                                           _dp, _dp, _dp, _dp, _ip, _ip]),
     "cgp_fit_predict_trend_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp] * 7 + [ctypes.c_int] + [_vp] * 7),
@@ -630,6 +635,38 @@ class Context:
         return self._chk(self.lib.cgp_fit_predict_trend_batch_device(self.h, B, N, d, M, P, q, kernel_id, dX, dY, dH, dXs, dHs,
                                                                      dtheta, djitter or None, int(include_noise), dmean, dvar,
                                                                      dbeta, dlogml, dinfo, dtinfo, ctypes.c_void_p(stream)))
+
+    # -- sparse (inducing-point) fits: the collapsed variational bound and its forecast (fp64 contexts) -----------
+    def sparse_reserve(self, max_batch, max_n, max_m_ind, max_m):
+        """Scratch for the two calls below: up to max_batch fits of max_n samples -- NOT bounded by the context's max_n --
+        max_m_ind <= 512 inducing inputs and max_m test points."""
+        return self._chk(self.lib.cgp_sparse_reserve(self.h, int(max_batch), int(max_n), int(max_m_ind), int(max_m)))
+
+    def fit_predict_sparse_batch(self, X, y, Z, Xs, theta, kernel_id, include_noise=True):
+        """X (B, N, d), y (B, N), Z (B, m, d) -- every fit's own inducing inputs --, Xs (B, M, d) or None (M = 0: the bound
+        only), theta (B, nth) -> (rc, mean (B, M), var (B, M), bound (B,), info (B,)).  info: 0, the failing pivot k of K_uu
+        (after the jitter ladder) or m + k for a pivot of B; such a fit has NaN outputs."""
+        X, y, Z, theta = _d(X), _d(y), _d(Z), _d(theta)
+        B, N, d = X.shape
+        m = Z.shape[1]
+        assert y.shape == (B, N) and Z.shape == (B, m, d)
+        M = 0 if Xs is None else np.shape(Xs)[1]
+        Xs = _d(Xs) if M > 0 else None
+        mean, var = np.empty((B, M)), np.empty((B, M))
+        logml, info = np.empty(B), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_fit_predict_sparse_batch(self.h, B, N, d, M, m, kernel_id, _p(X), _p(y), _p(Z),
+                                                             _p(Xs) if M > 0 else None, _p(theta), theta.shape[1],
+                                                             int(include_noise), _p(mean) if M > 0 else None,
+                                                             _p(var) if M > 0 else None, _p(logml), info.ctypes.data_as(_ip)))
+        return rc, mean, var, logml, info
+
+    def fit_predict_sparse_batch_device(self, B, N, d, M, m, kernel_id, dX, dy, dZ, dXs, dtheta, djitter, include_noise,
+                                        dmean, dvar, dlogml, dinfo, stream=0):
+        """Device pointers as fit_predict_batch_device (fp64, SoA): dX (B, d, N), dy (B, N), dZ (B, d, m), dXs (B, d, M),
+        dtheta (B, MAX_THETA), djitter (B) or 0; dmean / dvar (B, M) -- may be 0 when M = 0 --, dlogml (B), dinfo (B) int32."""
+        return self._chk(self.lib.cgp_fit_predict_sparse_batch_device(self.h, B, N, d, M, m, kernel_id, dX, dy, dZ, dXs or None,
+                                                                      dtheta, djitter or None, int(include_noise), dmean or None,
+                                                                      dvar or None, dlogml, dinfo, ctypes.c_void_p(stream)))
 
     # -- multi-target fits: gradient and optimiser of the summed logML (fp64 contexts) ------------------------
     def multi_grad_reserve(self, max_batch, max_p):

@@ -569,6 +569,70 @@ int cgp_fit_predict_trend_batch_device(cgp_ctx *ctx, int batch, int N, int d, in
                                        double *dmean, double *dvar, double *dbeta, double *dlogml, int *dinfo, int *dtinfo,
                                        void *hip_stream);
 
+/* ---- sparse (inducing-point) fits: the collapsed variational bound and its forecast ---------------------------
+ * Every fit above is a dense Cholesky of an N x N Gram matrix, sized by the context's max_n.  This section is the model of the family
+ * that is not: GPy.models.SparseGPRegression -- m inducing inputs Z, the collapsed variational bound of Titsias (2009), GPy's
+ * VarDTC -- at N m^2 + m^3 flops with no N x N object anywhere, so a whole recorded history can be fed instead of a window.  N is
+ * bounded by the sparse reservation alone, NOT by the context's max_n.  Per fit, with X (N x d), y (N), Z (m x d), Xs (M x d):
+ *   sigma2 = sigma_n^2 + 1e-8 (the dense path's diagonal)            eps = 1e-8 + the fit's jitter
+ *   K_uu = K(Z, Z) + eps I = L_u L_u^T
+ *   Phi = K_uf K_fu (m x m)      b = K_uf y (m)      yty = y^T y      t = sum_i k(x_i, x_i)   (RBF x Brownian: k(x, x) = s_r^2 s_b^2 |x|)
+ *   A = L_u^-1 Phi L_u^-T / sigma2      B = I + A = L_B L_B^T      c = L_B^-1 L_u^-1 b / sigma2
+ *   logml = -N/2 log 2 pi - N/2 log sigma2 - sum log diag(L_B) - yty / (2 sigma2) + c^T c / 2 - t / (2 sigma2) + tr(A) / 2
+ *   V1 = L_u^-1 K(Z, Xs)      V2 = L_B^-1 V1
+ *   mean = V2^T c      var = max(k(xs, xs) - colsum(V1^2) + colsum(V2^2), 1e-15) (+ sigma_n^2 when include_noise)
+ * `logml` is the BOUND: it is <= the exact log marginal likelihood of the same data and does not decrease when an inducing input
+ * is added.  With Z = X it is the exact fit up to eps (4e-6 relative on the bound at N = 200, sigma_n^2 = 1e-3): not a parity
+ * statement.  All five kernel ids (RBF x Brownian needs d = 1); CGP_F64 contexts only.
+ *
+ * info[b]: 0 the fit succeeded; k in 1 .. m the 1-based failing pivot of K_uu; m + k the failing pivot of B.  A failed fit has NaN
+ * in mean, var and logml; its neighbours are untouched.  Non-positive pivots are repaired in flight, so nothing faults.
+ *
+ * Layouts.  Host form: X (batch, N, d), y (batch, N), Z (batch, m, d) -- every fit has inducing inputs of its own --, Xs (batch, M,
+ * d), theta (batch, theta_stride), mean / var (batch, M), logml / info (batch).  Device form: fp64 SoA as
+ * cgp_fit_predict_batch_device -- dX (batch, d, N), dy (batch, N), dZ (batch, d, m), dXs (batch, d, M), dtheta (batch,
+ * CGP_MAX_THETA), djitter (batch) or NULL.  M = 0 gives the bound only: Xs, mean and var may then be NULL.
+ *
+ * Determinism.  A fit's outputs are a function of its own data and of (N, m, M, d, kernel) only: bitwise independent of the batch
+ * size, the slot and the neighbours.  The sum over N is cut into min(ceil(N / cgp_sparse_chunk()), 16) chunks of equal length
+ * (rounded up to 16 samples) whose partial sums are added in chunk order; no floating-point atomics.  Host form (for a fit that
+ * needed no ladder step), device form and a replayed graph agree bitwise.
+ *
+ * cgp_sparse_reserve: ALL the scratch of the sparse calls -- the dense schedules' buffers are not used.  With mt = ceil((max_m_ind
+ * + 1) / 16), LD = 16 mt and C = min(ceil(max_n / 512), 16) it allocates
+ *   8 max_batch (16 + 128 C mt (mt + 1) + 3 LD^2 + 512 mt + 4 LD + 8) bytes
+ * (max_n = 65 536, max_m_ind = 256: 6.9 MB per fit; max_m_ind = 512: 25 MB per fit).  1 <= max_batch <= the context's, 1 <= max_n <=
+ * 2^24, 1 <= max_m_ind <= 512, max_m >= 0, else CGP_EINVAL; max_n and max_m are independent of the context's.  CGP_ENOMEM leaves no
+ * reservation; calling it again replaces the reservation.  Blocks.  cgp_destroy frees it.
+ *
+ * Status of the two calls, in this order: CGP_EINVAL in a CGP_F32 context, for batch, N, d or m < 1, m > 512, M < 0, an unknown
+ * kernel id or RBF x Brownian with d != 1; without a reservation CGP_ESTATE; batch, N, m or M beyond it, d beyond the context's
+ * max_d or batch beyond the context's CGP_ECAPACITY; a NULL required pointer or theta_stride < ntheta CGP_EINVAL.  All of these
+ * return before anything is enqueued.  N >= 1 with no relation to m required.
+ *
+ * cgp_profile_*: the launches of a sparse call are recorded under 0 k_sparse_phi (flops = N (m + 1)(m + 2) per fit), 1
+ * k_sparse_algebra, 2 k_sparse_reduce, 3 k_sparse_predict, 4 k_sparse_prep.
+ *
+ * Not provided: gradients of the bound and an optimiser over theta or Z; FITC; several target columns; the resident windows; fp32
+ * contexts; a cgp_sweep_* form. */
+int cgp_sparse_reserve(cgp_ctx *ctx, int max_batch, int max_n, int max_m_ind, int max_m);
+/* Samples of the shortest chunk of the sum over N (512): the split above, for tests that sit on its edges. */
+int cgp_sparse_chunk(void);
+/* cgp_fit_predict_sparse_batch: host buffers, blocks.  A fit whose K_uu fails climbs the jitter ladder of cgp_fit_predict_batch
+ * (the same function: jitter = 1e-6 10^k of mean(diag K(Z, Z)) + sigma_n^2 + 1e-8, k = 0 .. 4), re-submitted alone into its slot;
+ * a failing pivot of B is reported as it is.  logml and info may be NULL.  Returns a negative error, else 0 or the first non-zero
+ * per-fit info. */
+int cgp_fit_predict_sparse_batch(cgp_ctx *ctx, int batch, int N, int d, int M, int m, int kernel_id,
+                                 const double *X, const double *y, const double *Z, const double *Xs, const double *theta,
+                                 int theta_stride, int include_noise, double *mean, double *var, double *logml, int *info);
+/* Device-resident variant: five launches (four when M = 0) in a linear chain on hip_stream (NULL = legacy default stream,
+ * CGP_STREAM_CTX = the context's own); no allocation, no synchronisation, no jitter ladder (capturable into a hipGraph with default
+ * settings).  dlogml and dinfo are required.  The extent contract at cgp_fit_predict_batch_device applies. */
+int cgp_fit_predict_sparse_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, int m, int kernel_id,
+                                        const double *dX, const double *dy, const double *dZ, const double *dXs,
+                                        const double *dtheta, const double *djitter, int include_noise,
+                                        double *dmean, double *dvar, double *dlogml, int *dinfo, void *hip_stream);
+
 /* ---- multi-target fits: gradient and optimiser of the summed logML ------------------------------------
  * m.optimize() of the multi-column model (gp_slip_node.py:36 with Y (N, P)): ONE theta per fit maximises
  *   sum_p logml[p] = -P/2 log|Ky| - 1/2 tr(Y^T Ky^-1 Y) - N P / 2 log 2 pi.
