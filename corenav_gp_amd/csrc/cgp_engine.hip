@@ -18,6 +18,7 @@
 #include "cgp_multi_grad.hpp"
 #include "cgp_trend.hpp"
 #include "cgp_sparse.hpp"
+#include "cgp_sparse_grad.hpp"
 #include "cgp_pgrad.hpp"
 #include "cgp_lookahead.hpp"
 #include "cgp_small.hpp"
@@ -213,6 +214,10 @@ struct cgp_ctx {
   // inducing inputs and sp_max_n samples (cgp_sparse_host.hpp, sparse_layout); staging of the host call
   Scratch sp;
   int sp_max_n = 0, sp_max_m = 0;
+  // the sparse fits' objective (cgp_sparse_grad_reserve): A, T and G_uu of up to max_batch fits of max_dim inducing inputs and the
+  // partial sums of sg_max_n samples (cgp_sparse_grad_host.hpp, sparse_grad_layout); staging of the host calls
+  Scratch sg;
+  int sg_max_n = 0;
   // multi-target objective (cgp_multi_grad_reserve): A = Ky^-1 Y of up to max_batch fits x max_dim targets, [fit][P padded to 16][NT 128],
   // then (max_batch, max_dim) logml; staging of the host calls [Y | nll | grad | logml]
   Scratch ma;
@@ -931,7 +936,7 @@ void cgp_destroy(cgp_ctx *c) {
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
   window_drop(c, WinDrop::Windows);
-  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->sp, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
+  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->sp, &c->sg, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -2392,3 +2397,5 @@ extern "C" int cgp_loo(cgp_ctx *c, const double *X, const double *y, int N, int 
 // leave-one-out objective: cgp_loo_grad_reserve ... cgp_optimize_loo_batch
 #include "cgp_loo_grad_host.hpp"
 #include "cgp_pgrad_host.hpp"
+// the sparse fits' objective: cgp_sparse_grad_reserve ... cgp_optimize_sparse_batch
+#include "cgp_sparse_grad_host.hpp"

@@ -96,6 +96,7 @@ struct SparseArgs {
   double *dinv;    // [fit][2][mt][256] inverses of the diagonal blocks of L_u, L_B: element (row i, column k) at k * 16 + i
   double *vec;     // [fit][4][LD] b, c, diag(A)
   double *scal;    // [fit][8] yty
+  double *Acp;     // [fit][LD][LD] or null: a copy of A, row-major, for the gradient call (cgp_sparse_grad.hpp)
   int N, d, M, m, kid, include_noise, nfit;
   SparseShape sh;
 };
@@ -445,6 +446,7 @@ __global__ __launch_bounds__(SPA_THREADS) void k_sparse_algebra(SparseArgs p) {
     const int i = e / LD, j = e - i * LD;
     const double a = F[e] / sigma2;
     if (i == j) da[i] = a;
+    if (p.Acp) p.Acp[(size_t)f * LD * LD + e] = a;
     F[e] = i == j ? 1.0 + a : a;
   }
   __syncthreads();

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <memory>
 #include <cstddef>
 #include <vector>
 
@@ -22,33 +23,45 @@ struct LbfgsResult {
 };
 
 // vector-facing wrapper of LbfgsCore (lbfgs_core.hpp: the state machine itself, shared with the device optimiser)
+constexpr int LB_NBIG = 4112;   // parameters of a problem with free coordinates: CGP_MAX_THETA + 512 inducing inputs x 8 dimensions
 class LbfgsStepper {
  public:
   LbfgsStepper(const std::vector<double> &x0, int max_evals, double pgtol, double factr) : xn_(x0), x_(x0) {
-    c_.init(x0.data(), (int)x0.size(), max_evals, pgtol, factr);
+    if ((int)x0.size() > LB_N) {
+      big_.reset(new LbfgsCoreT<LB_NBIG>());
+      big_->init(x0.data(), (int)x0.size(), max_evals, pgtol, factr);
+    } else {
+      c_.init(x0.data(), (int)x0.size(), max_evals, pgtol, factr);
+    }
   }
 
-  bool done() const { return c_.done(); }
+  bool done() const { return big_ ? big_->done() : c_.done(); }
   const std::vector<double> &trial() const { return xn_; }  // the point to evaluate next
   const std::vector<double> &best() const { return x_; }
-  LbfgsResult result() const {
-    LbfgsResult r;
-    r.f = c_.f;
-    r.evals = c_.evals;
-    r.iters = c_.iters;
-    r.status = c_.status;
-    return r;
-  }
+  LbfgsResult result() const { return big_ ? result_of(*big_) : result_of(c_); }
 
   // Feed f(trial()) and its gradient.  Non-finite f marks an infeasible point.
   void tell(double fv, const std::vector<double> &gv) {
-    c_.tell(fv, gv.data());
-    std::copy(c_.xn, c_.xn + c_.n, xn_.begin());
-    std::copy(c_.x, c_.x + c_.n, x_.begin());
+    if (big_) tell_to(*big_, fv, gv);
+    else tell_to(c_, fv, gv);
   }
 
  private:
+  template <class C> static LbfgsResult result_of(const C &c) {
+    LbfgsResult r;
+    r.f = c.f;
+    r.evals = c.evals;
+    r.iters = c.iters;
+    r.status = c.status;
+    return r;
+  }
+  template <class C> void tell_to(C &c, double fv, const std::vector<double> &gv) {
+    c.tell(fv, gv.data());
+    std::copy(c.xn, c.xn + c.n, xn_.begin());
+    std::copy(c.x, c.x + c.n, x_.begin());
+  }
   LbfgsCore c_;
+  std::unique_ptr<LbfgsCoreT<LB_NBIG>> big_;   // more than LB_N parameters
   std::vector<double> xn_, x_;
 };
 
@@ -87,19 +100,22 @@ struct LbfgsBatchResult {
 // for the active problems only.  Returns 0, or a code that ends the run.
 using LbfgsBatchEval = std::function<int(const double *theta, const char *active, double *f, double *grad, char *feasible)>;
 
-// n independent minimisations over theta > 0 (nth parameters each, Logexp-transformed; pgtol 1e-5, factr 1e7) that share one
+// n independent minimisations over theta > 0 (npos parameters each, Logexp-transformed; pgtol 1e-5, factr 1e7) that share one
 // evaluation per round: each selected problem is the lbfgs_minimize run of its own transformed objective, where an infeasible
 // point counts as +inf.  select == nullptr selects every problem; theta0 of a selected problem must be positive.  Ends when
 // no problem is active, after max_evals + 40 rounds at the latest (max_evals <= 0: 1000).  Returns 0 or eval's code.
-inline int lbfgs_minimize_logexp_batch(int n, int nth, const double *theta0, size_t theta_stride, const unsigned char *select,
-                                       int max_evals, const LbfgsBatchEval &eval, LbfgsBatchResult &out) {
+// nfree > 0: every problem has nfree further coordinates after the positive ones that are optimised as they stand (the inducing
+// inputs of cgp_optimize_sparse_batch); theta, the gradient and out.theta then hold npos + nfree entries per problem.
+inline int lbfgs_minimize_logexp_batch(int n, int npos, const double *theta0, size_t theta_stride, const unsigned char *select,
+                                       int max_evals, const LbfgsBatchEval &eval, LbfgsBatchResult &out, int nfree = 0) {
   const int cap = max_evals > 0 ? max_evals : 1000;
+  const int nth = npos + nfree;   // coordinates of a problem: npos positive ones, then nfree untransformed ones
   auto sel = [&](int b) { return !select || select[b] != 0; };
   std::vector<LbfgsStepper> st;
   st.reserve(n);
   std::vector<double> x0(nth);
   for (int b = 0; b < n; ++b) {
-    for (int i = 0; i < nth; ++i) x0[i] = sel(b) ? logexp_x(theta0[b * theta_stride + i]) : 0.0;
+    for (int i = 0; i < nth; ++i) x0[i] = !sel(b) ? 0.0 : (i < npos ? logexp_x(theta0[b * theta_stride + i]) : theta0[b * theta_stride + i]);
     st.emplace_back(x0, cap, 1e-5, 1e7);
   }
   const size_t nt = (size_t)n * nth;
@@ -113,7 +129,8 @@ inline int lbfgs_minimize_logexp_batch(int n, int nth, const double *theta0, siz
       active[b] = sel(b) && !st[b].done();
       any = any || active[b];
       const std::vector<double> &xx = active[b] ? st[b].trial() : st[b].best();
-      for (int i = 0; i < nth; ++i) th[(size_t)b * nth + i] = sel(b) ? logexp_theta_eval(xx[i]) : theta0[b * theta_stride + i];
+      for (int i = 0; i < nth; ++i)
+        th[(size_t)b * nth + i] = !sel(b) ? theta0[b * theta_stride + i] : (i < npos ? logexp_theta_eval(xx[i]) : xx[i]);
     }
     if (!any) break;
     const int rc = eval(th.data(), active.data(), f.data(), g.data(), feasible.data());
@@ -125,7 +142,7 @@ inline int lbfgs_minimize_logexp_batch(int n, int nth, const double *theta0, siz
       const double *tb = th.data() + (size_t)b * nth, *gb = g.data() + (size_t)b * nth;
       double fv = INFINITY;   // tell() gives an infeasible point a zero gradient itself
       if (feasible[b]) {
-        for (int i = 0; i < nth; ++i) gx[i] = gb[i] * logexp_dtheta_dx(xt[i], tb[i]);
+        for (int i = 0; i < nth; ++i) gx[i] = i < npos ? gb[i] * logexp_dtheta_dx(xt[i], tb[i]) : gb[i];
         fv = f[b];
       }
       st[b].tell(fv, gx);
@@ -138,7 +155,8 @@ inline int lbfgs_minimize_logexp_batch(int n, int nth, const double *theta0, siz
   out.status.assign(n, 0);
   for (int b = 0; b < n; ++b) {
     const std::vector<double> &xb = st[b].best();
-    for (int i = 0; i < nth; ++i) out.theta[(size_t)b * nth + i] = sel(b) ? logexp_theta(xb[i]) : theta0[b * theta_stride + i];
+    for (int i = 0; i < nth; ++i)
+      out.theta[(size_t)b * nth + i] = !sel(b) ? theta0[b * theta_stride + i] : (i < npos ? logexp_theta(xb[i]) : xb[i]);
     if (!sel(b)) continue;
     const LbfgsResult r = st[b].result();
     out.f[b] = r.f;

@@ -168,13 +168,15 @@ struct MtSearch {
   }
 };
 
-struct LbfgsCore {
+// NMAX: the most parameters an instance holds.  LbfgsCore (LB_N) is the one every theta-only optimiser and the device run;
+// LbfgsStepper takes a larger instance from the heap for problems with free coordinates (the inducing inputs of a sparse fit).
+template <int NMAX> struct LbfgsCoreT {
   int n, max_evals, hist, ls, evals, iters, status;  // status: 0 converged (gradient), 1 converged (function decrease), 2 max evals, 3 line search failed
   int first, finished;
   double pgtol, ftol;
-  double x[LB_N], g[LB_N], xn[LB_N], gn[LB_N], dir[LB_N];
-  double S[LB_M][LB_N], Y[LB_M][LB_N], rho[LB_M];
-  double wa[LB_M], ws[LB_N], wy[LB_N];  // work vectors (members, so that on the device they live with the state in LDS, not in scratch memory)
+  double x[NMAX], g[NMAX], xn[NMAX], gn[NMAX], dir[NMAX];
+  double S[LB_M][NMAX], Y[LB_M][NMAX], rho[LB_M];
+  double wa[LB_M], ws[NMAX], wy[NMAX];  // work vectors (members, so that on the device they live with the state in LDS, not in scratch memory)
   double f, fn, dg0, t;
   MtSearch mt;
 
@@ -188,7 +190,7 @@ struct LbfgsCore {
     first = 1;
     f = fn = dg0 = t = 0.0;
     mt.start(0.0, 0.0, 0.0);
-    for (int i = 0; i < LB_N; ++i) {
+    for (int i = 0; i < NMAX; ++i) {
       x[i] = xn[i] = i < n ? x0[i] : 0.0;
       g[i] = gn[i] = dir[i] = 0.0;
     }
@@ -319,5 +321,6 @@ struct LbfgsCore {
     start_iteration();
   }
 };
+using LbfgsCore = LbfgsCoreT<LB_N>;
 
 }  // namespace corenav

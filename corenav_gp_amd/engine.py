@@ -111,6 +111,11 @@ _SIGS = {
     "cgp_fit_predict_sparse_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_dp] * 5 + [ctypes.c_int, ctypes.c_int,
                                                                                              _dp, _dp, _dp, _ip]),
     "cgp_fit_predict_sparse_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp] * 6 + [ctypes.c_int] + [_vp] * 5),
+    "cgp_sparse_grad_reserve": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "cgp_sparse_nll_grad_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp] * 4 + [ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                                                              _dp, _ip]),
+    "cgp_sparse_nll_grad_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp] * 7 + [ctypes.c_int, _vp, _vp, _vp]),
+    "cgp_optimize_sparse_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp] * 4 + [ctypes.c_int] * 3 + [_dp, _ip]),
     "cgp_fit_predict_trend_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_dp] * 6 + [ctypes.c_int, ctypes.c_int,
                                                                                           _dp, _dp, _dp, _dp, _ip, _ip]),
     "cgp_fit_predict_trend_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp] * 7 + [ctypes.c_int] + [_vp] * 7),
@@ -667,6 +672,52 @@ class Context:
         return self._chk(self.lib.cgp_fit_predict_sparse_batch_device(self.h, B, N, d, M, m, kernel_id, dX, dy, dZ, dXs or None,
                                                                       dtheta, djitter or None, int(include_noise), dmean or None,
                                                                       dvar or None, dlogml, dinfo, ctypes.c_void_p(stream)))
+
+    # -- sparse fits: gradient of the bound in theta and Z, and optimiser (fp64 contexts) -----------------------------
+    def sparse_grad_reserve(self, max_batch):
+        """Scratch for the three calls below; needs a sparse_reserve that covers it and is sized by it."""
+        return self._chk(self.lib.cgp_sparse_grad_reserve(self.h, int(max_batch)))
+
+    def sparse_nll_grad_batch(self, X, y, Z, theta, kernel_id, want_grad_z=True):
+        """X (B, N, d), y (B, N), Z (B, m, d), theta (B, nth) -> (rc, nll (B,), grad (B, nth), gradZ (B, m, d) or None, info (B,)):
+        nll = -bound of each fit, its gradient in theta (natural parameters) and in the inducing inputs.  A fit whose info stays
+        non-zero after the jitter ladder on K_uu has NaN outputs."""
+        X, y, Z, theta = _d(X), _d(y), _d(Z), _d(theta)
+        B, N, d = X.shape
+        m, nth = Z.shape[1], theta.shape[1]
+        assert y.shape == (B, N) and Z.shape == (B, m, d)
+        nll, grad = np.empty(B), np.empty((B, nth))
+        gz, info = (np.empty((B, m, d)) if want_grad_z else None), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_sparse_nll_grad_batch(self.h, B, N, d, m, kernel_id, _p(X), _p(y), _p(Z), _p(theta), nth,
+                                                          _p(nll), _p(grad), nth, _p(gz) if want_grad_z else None,
+                                                          info.ctypes.data_as(_ip)))
+        return rc, nll, grad, gz, info
+
+    def sparse_nll_grad_batch_device(self, B, N, d, m, kernel_id, dX, dy, dZ, dtheta, djitter, dnll, dgrad, grad_stride, dgradZ,
+                                     dinfo, stream=0):
+        """Device pointers as fit_predict_sparse_batch_device; dnll (B,), dgrad (B, grad_stride), dgradZ (B, d, m) or 0."""
+        return self._chk(self.lib.cgp_sparse_nll_grad_batch_device(self.h, B, N, d, m, kernel_id, dX, dy, dZ, dtheta,
+                                                                   djitter or None, dnll, dgrad, int(grad_stride),
+                                                                   dgradZ or None, dinfo, ctypes.c_void_p(stream)))
+
+    def optimize_sparse_batch(self, X, y, Z0, theta0, kernel_id, optimize_z=True, max_evals=1000):
+        """SparseGPRegression(...).optimize(): X (B, N, d), y (B, N), Z0 (B, m, d), theta0 (B, nth) or (nth,) ->
+        (theta_opt (B, nth), Z_opt (B, m, d), bound (B,), n_evals (B,)); optimize_z=False keeps Z0."""
+        X, y = _d(X), _d(y)
+        B, N, d = X.shape
+        Z = np.array(Z0, dtype=np.float64, order="C")
+        m = Z.shape[1]
+        theta = np.array(theta0, dtype=np.float64)
+        if theta.ndim == 1:
+            theta = np.tile(theta, (B, 1))
+        theta = np.ascontiguousarray(theta)
+        bound, nev = np.empty(B), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_optimize_sparse_batch(self.h, B, N, d, m, kernel_id, _p(X), _p(y), _p(Z), _p(theta),
+                                                          theta.shape[1], int(bool(optimize_z)), int(max_evals), _p(bound),
+                                                          nev.ctypes.data_as(_ip)))
+        if rc > 0:
+            raise CgpError(rc)
+        return theta, Z, bound, nev
 
     # -- multi-target fits: gradient and optimiser of the summed logML (fp64 contexts) ------------------------
     def multi_grad_reserve(self, max_batch, max_p):

@@ -613,8 +613,8 @@ int cgp_fit_predict_trend_batch_device(cgp_ctx *ctx, int batch, int N, int d, in
  * cgp_profile_*: the launches of a sparse call are recorded under 0 k_sparse_phi (flops = N (m + 1)(m + 2) per fit), 1
  * k_sparse_algebra, 2 k_sparse_reduce, 3 k_sparse_predict, 4 k_sparse_prep.
  *
- * Not provided: gradients of the bound and an optimiser over theta or Z; FITC; several target columns; the resident windows; fp32
- * contexts; a cgp_sweep_* form. */
+ * The gradient of the bound in theta and Z and the optimiser over them are the next section's.  Not provided: FITC; several target
+ * columns; the resident windows; fp32 contexts; a cgp_sweep_* form. */
 int cgp_sparse_reserve(cgp_ctx *ctx, int max_batch, int max_n, int max_m_ind, int max_m);
 /* Samples of the shortest chunk of the sum over N (512): the split above, for tests that sit on its edges. */
 int cgp_sparse_chunk(void);
@@ -632,6 +632,65 @@ int cgp_fit_predict_sparse_batch_device(cgp_ctx *ctx, int batch, int N, int d, i
                                         const double *dX, const double *dy, const double *dZ, const double *dXs,
                                         const double *dtheta, const double *djitter, int include_noise,
                                         double *dmean, double *dvar, double *dlogml, int *dinfo, void *hip_stream);
+
+/* ---- sparse fits: gradient of the bound in theta and Z, and optimiser ------------------------------------
+ * SparseGPRegression(...).optimize() chooses theta AND the inducing inputs Z by maximising the bound above.  With the quantities of
+ * the sparse section and F the bound:
+ *   chat = L_B^-T c      Q = I - B^-1 - chat chat^T      mu = L_u^-T chat
+ *   T = L_u^-T Q L_u^-1 / (2 sigma2) = dF/dPhi      G_uu = 1/2 L_u^-T (Q - A) L_u^-1 = dF/dK_uu      R = 2 T K_uf + mu y^T / sigma2 = dF/dK_uf
+ *   dF/dtheta_p  = sum_rs G_uu[r,s] dk(z_r,z_s)/dtheta_p + sum_ri R[r,i] dk(z_r,x_i)/dtheta_p - sum_i dk(x_i,x_i)/dtheta_p / (2 sigma2)
+ *   dF/dsigma_n2 = (-N + (yty + t) / sigma2 - tr A + m - tr B^-1 - c^T c - chat^T chat) / (2 sigma2)
+ *   dF/dz_rq     = sum_i R[r,i] dk(z_r,x_i)/dz_rq + 2 sum_{s != r} G_uu[r,s] dk(z_r,z_s)/dz_rq + G_uu[r,r] dk(z_r,z_r)/dz_rq
+ * eps (the 1e-8 and any jitter) is a constant of the evaluation, as in every other gradient call.  RBF x Brownian: the derivative of
+ * min(|z|, |x|) in z is taken for |z| < |x| only (the tie convention of the predictive gradients), and d k(z, z) / dz = s_r^2 s_b^2
+ * sign z.  Outputs: nll = -F, grad = d nll / d theta in natural parameters (cgp_nll_grad's order), gradZ = d nll / d Z.  The cost
+ * on top of the forward chain is a second pass over N of the same N m^2 size (R is never stored) and six m x m block solves.
+ *
+ * Promises.  nll is bitwise -logml of cgp_fit_predict_sparse_batch_device on the same inputs, for any M: the same launches produce
+ * it.  A fit's outputs are a function of its own data and of (N, m, d, kernel, whether gradZ was asked) only: bitwise independent of
+ * the batch size, the slot and the neighbours; no floating-point atomics, every sum in a fixed order.  Host form (for a fit that
+ * needed no ladder step), device form and a replayed graph agree bitwise.  grad is bitwise the same whether or not gradZ is asked.
+ * A gradient call leaves a following cgp_fit_predict_sparse_batch bitwise what it is without it.  info is the sparse section's; a
+ * fit whose info is not 0 has NaN in nll, grad and gradZ, and its neighbours are untouched.
+ *
+ * cgp_sparse_grad_reserve: needs a cgp_sparse_reserve that covers it (max_batch within it), else CGP_ESTATE, and is sized by that
+ * reservation's max_n and max_m_ind as they stand at the call: with mt = ceil((max_m_ind + 1) / 16), LD = 16 mt, mr =
+ * ceil(max_m_ind / 16) and C = min(ceil(max_n / 512), 16) it allocates
+ *   8 max_batch (3 LD^2 + 12 C mr + 8 C LD + 12 mr + 8 LD + 5) bytes
+ * (max_n = 65 536, max_m_ind = 512: 7.3 MB per fit).  1 <= max_batch <= the context's, else CGP_EINVAL; CGP_ENOMEM leaves no reservation; calling
+ * it again replaces the reservation.  A later cgp_sparse_reserve does not widen it: N and m of a call must fit both.  Blocks.
+ *
+ * Status of the calls below, in this order: CGP_EINVAL in a CGP_F32 context, for batch, N, d or m < 1, m > 512, an unknown kernel id
+ * or RBF x Brownian with d != 1; without either reservation CGP_ESTATE; batch, N or m beyond either, d beyond the context's max_d
+ * CGP_ECAPACITY; a NULL required pointer, theta_stride or grad_stride < ntheta CGP_EINVAL; the optimiser also CGP_EINVAL for a theta
+ * <= 0.  All of these return before anything is enqueued.
+ *
+ * cgp_profile_*: CGP_PROF_KERNELS stays 5.  In a gradient call slot 0 is k_sparse_phi, slot 1 both algebra kernels (k_sparse_algebra,
+ * k_sparse_grad_algebra), slot 2 k_sparse_reduce + k_sparse_grad_uu + k_sparse_grad_finish, slot 3 k_sparse_grad_panel (the predict
+ * kernel never runs at M = 0; flops = 2 N (m + 1) LD per fit), slot 4 k_sparse_prep.
+ *
+ * Not provided: FITC; several target columns; the resident windows; fp32 contexts; a cgp_sweep_* form. */
+int cgp_sparse_grad_reserve(cgp_ctx *ctx, int max_batch);
+/* Host buffers, blocks; layouts as cgp_fit_predict_sparse_batch, grad (batch, grad_stride), gradZ (batch, m, d) or NULL, info
+ * (batch) or NULL.  A fit whose K_uu fails climbs the jitter ladder of cgp_fit_predict_sparse_batch, re-submitted alone into its
+ * slot; the gradient is then that of the bound at that jitter.  Returns a negative error, else 0 or the first non-zero info. */
+int cgp_sparse_nll_grad_batch(cgp_ctx *ctx, int batch, int N, int d, int m, int kernel_id, const double *X, const double *y,
+                              const double *Z, const double *theta, int theta_stride, double *nll, double *grad, int grad_stride,
+                              double *gradZ, int *info);
+/* Device-resident variant: the forward chain's four launches, then four more, one linear chain on hip_stream; no allocation, no
+ * synchronisation, no jitter ladder (capturable into a hipGraph with default settings).  Layouts as
+ * cgp_fit_predict_sparse_batch_device; dgradZ (batch, d, m) -- the layout of dZ -- or NULL.  dnll, dgrad and dinfo are required. */
+int cgp_sparse_nll_grad_batch_device(cgp_ctx *ctx, int batch, int N, int d, int m, int kernel_id, const double *dX,
+                                     const double *dy, const double *dZ, const double *dtheta, const double *djitter,
+                                     double *dnll, double *dgrad, int grad_stride, double *dgradZ, int *dinfo, void *hip_stream);
+/* L-BFGS (cgp_optimize_batch's: Logexp on theta, pgtol 1e-5, factr 1e7, max_evals <= 0: 1000) on nll from theta_inout and Z_inout
+ * (batch, m, d).  optimize_z = 0: over theta with Z fixed; 1: over [theta | Z row-major] jointly, Z unconstrained.  A trial point
+ * whose K_uu fails climbs the ladder; one that stays infeasible (K_uu or B) counts as +inf.  X and y are uploaded once, theta and Z
+ * per round.  logml (or NULL): the bound at the returned point, from one evaluation more -- bitwise what
+ * cgp_fit_predict_sparse_batch returns there when no ladder step was needed; n_evals (or NULL): evaluations of each fit. */
+int cgp_optimize_sparse_batch(cgp_ctx *ctx, int batch, int N, int d, int m, int kernel_id, const double *X, const double *y,
+                              double *Z_inout, double *theta_inout, int theta_stride, int optimize_z, int max_evals,
+                              double *logml, int *n_evals);
 
 /* ---- multi-target fits: gradient and optimiser of the summed logML ------------------------------------
  * m.optimize() of the multi-column model (gp_slip_node.py:36 with Y (N, P)): ONE theta per fit maximises
