@@ -218,6 +218,11 @@ struct cgp_ctx {
   // partial sums of sg_max_n samples (cgp_sparse_grad_host.hpp, sparse_grad_layout); staging of the host calls
   Scratch sg;
   int sg_max_n = 0;
+  // several target columns on one sparse fit (cgp_sparse_multi_reserve): what up to max_dim columns add to the sparse scratch of up
+  // to max_batch fits of sm_max_ind inducing inputs and sm_max_n samples (cgp_sparse_multi_host.hpp, sparse_multi_layout); staging
+  // of the host call
+  Scratch sm;
+  int sm_max_n = 0, sm_max_ind = 0;
   // multi-target objective (cgp_multi_grad_reserve): A = Ky^-1 Y of up to max_batch fits x max_dim targets, [fit][P padded to 16][NT 128],
   // then (max_batch, max_dim) logml; staging of the host calls [Y | nll | grad | logml]
   Scratch ma;
@@ -936,7 +941,7 @@ void cgp_destroy(cgp_ctx *c) {
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
   window_drop(c, WinDrop::Windows);
-  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->sp, &c->sg, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
+  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->sp, &c->sg, &c->sm, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -2399,3 +2404,6 @@ extern "C" int cgp_loo(cgp_ctx *c, const double *X, const double *y, int N, int 
 #include "cgp_pgrad_host.hpp"
 // the sparse fits' objective: cgp_sparse_grad_reserve ... cgp_optimize_sparse_batch
 #include "cgp_sparse_grad_host.hpp"
+
+// sparse fits with several target columns: cgp_sparse_multi_reserve ... cgp_fit_predict_sparse_multi_batch_device
+#include "cgp_sparse_multi_host.hpp"

@@ -48,13 +48,16 @@ constexpr int SPA_WAVES = SPA_THREADS / 64;
 constexpr int SPA_TPW = 9;                      // tiles of a wave per block column / block row: ceil(33 / 4)
 constexpr int SPP_WAVES = 4;                    // k_sparse_predict: waves (column tiles) of a workgroup, fewer when LDS is short
 constexpr int SP_LDMAX = ((SP_MAX_IND + 1 + 15) / 16) * 16;
+constexpr int SP_MAX_P = 64;                    // target columns of a fit (cgp_sparse_multi.hpp's calls; the other calls have one)
+constexpr int SPV_COLS = 8;                     // target columns of one pass of sparse_vec_solve
 static_assert(SPA_TPW * SPA_WAVES * 16 >= SP_LDMAX, "a wave holds every tile of its share");
 // the fit's record: PREP_N doubles in the prep record's layout ([0..7] 1 / ell_q, [9] amp, [10] amp_b), then
 constexpr int SP_R_SIGMA2 = 11, SP_R_EPS = 12, SP_R_NOISE = 13;   // sigma_n^2 + 1e-8, 1e-8 + jitter, sigma_n^2
 
 // what follows from a call's (N, m, d) alone
 struct SparseShape {
-  int mt, LD, ntile;      // tiles per side of the augmented matrix, 16 mt, tiles of its lower triangle
+  int mt, LD, nt0;        // tiles per side of the m x m objects (m + 1 rounded up), 16 mt, tiles of their lower triangle
+  int mta, LDa, ntile;    // the same of the augmented matrix of m + P rows (P target rows; at P = 1 they are the three above)
   int nch, clen;          // chunks of the sum over N, samples per chunk (a multiple of 16)
   int ngrp, tpg;          // tile groups (workgroups per chunk), tiles per group
   int S, ldr;             // samples of a sub-panel, row stride of the LDS panel
@@ -64,17 +67,20 @@ __host__ __device__ inline int sparse_chunks(int N) {
   return n < SP_MAX_CHUNKS ? n : SP_MAX_CHUNKS;
 }
 inline size_t sparse_phi_lds(int d, int LD, int S, int ldr) { return ((size_t)d * LD + (size_t)2 * S * ldr) * sizeof(double); }
-inline SparseShape sparse_shape(int N, int m, int d) {
+inline SparseShape sparse_shape(int N, int m, int d, int P = 1) {
   SparseShape s{};
   s.mt = (m + 1 + 15) / 16;
   s.LD = s.mt * 16;
-  s.ntile = s.mt * (s.mt + 1) / 2;
+  s.nt0 = s.mt * (s.mt + 1) / 2;
+  s.mta = (m + P + 15) / 16;
+  s.LDa = s.mta * 16;
+  s.ntile = s.mta * (s.mta + 1) / 2;
   s.nch = sparse_chunks(N);
   s.clen = (((N + s.nch - 1) / s.nch) + 15) / 16 * 16;
   s.ngrp = (s.ntile + SP_GROUP - 1) / SP_GROUP;
   s.tpg = (s.ntile + s.ngrp - 1) / s.ngrp;
-  s.ldr = 16 * (s.mt | 1);
-  s.S = sparse_phi_lds(d, s.LD, 16, s.ldr) <= (size_t)160 * 1024 ? 16 : 8;
+  s.ldr = 16 * (s.mta | 1);
+  s.S = sparse_phi_lds(d, s.LDa, 16, s.ldr) <= (size_t)160 * 1024 ? 16 : 8;
   return s;
 }
 inline int sparse_predict_waves(int LD) {
@@ -84,18 +90,24 @@ inline int sparse_predict_waves(int LD) {
 
 struct SparseArgs {
   // the call's arrays, at its first fit: X (fit, d, N), y (fit, N), Z (fit, d, m), Xs (fit, d, M), theta (fit, MAX_THETA)
+  // the P target columns of a fit: y (fit, P, N), mean (fit, P, M), logml (fit, P); P = 1 in every call but the multi-column ones
   const double *X, *y, *Z, *Xs, *theta, *jitter;   // jitter (fit) or null
-  double *mean, *var, *logml;                      // (fit, M), (fit, M), (fit)
+  double *mean, *var, *logml;                      // (fit, P, M), (fit, M), (fit, P)
   int *info;                                       // (fit)
   // the reservation's scratch, at the call's first fit, strided by the call's own shape
   double *rec;     // [fit][PREP_N]
-  double *part;    // [fit][nch][ntile][256] a chunk's tiles, element (row lq + 4 r, column l15) of a tile at r * 64 + lane
+  double *part;    // [fit][nch][nt0][256] a chunk's tiles, element (row lq + 4 r, column l15) of a tile at r * 64 + lane
+  double *partx;   // [fit][nch][ntile - nt0][256] the tiles of the tile rows that P > 1 targets add (the multi reservation's)
   double *U;       // [fit][LD][LD] K_uu, then L_u: column-major lower triangle
   double *F;       // [fit][LD][LD] Phi, then L_u^-1 W^T, then B and L_B
   double *W;       // [fit][LD][LD] W = L_u^-1 Phi, row-major
   double *dinv;    // [fit][2][mt][256] inverses of the diagonal blocks of L_u, L_B: element (row i, column k) at k * 16 + i
   double *vec;     // [fit][4][LD] b, c, diag(A)
   double *scal;    // [fit][8] yty
+  // the targets' vectors, column p of fit f: b at bm + f bcs + p LD, c at cm + f bcs + p LD, yty at yty[f ytys + p].  One column:
+  // the b and c of vec and scal[0] (what the gradient kernels read); several: the multi reservation's [fit][2][P][LD] and [fit][P]
+  double *bm, *cm, *yty;
+  int bcs, ytys, P;
   double *Acp;     // [fit][LD][LD] or null: a copy of A, row-major, for the gradient call (cgp_sparse_grad.hpp)
   int N, d, M, m, kid, include_noise, nfit;
   SparseShape sh;
@@ -136,11 +148,11 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_phi(SparseArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int N = p.N, m = p.m, d = p.d, kid = p.kid;
-  const int LD = p.sh.LD, S = p.sh.S, ldr = p.sh.ldr, ntile = p.sh.ntile, tpg = p.sh.tpg;
+  const int LD = p.sh.LDa, S = p.sh.S, ldr = p.sh.ldr, ntile = p.sh.ntile, nt0 = p.sh.nt0, tpg = p.sh.tpg, mP = m + p.P;
   double *Zl = reinterpret_cast<double *>(smem_raw);   // [d][LD] the inducing inputs, zero in the padding
   double *P = Zl + (size_t)d * LD;                     // [2][S][ldr] the panel: row r of sample s at s * ldr + r
   const double *pr = p.rec + (size_t)f * PREP_N;
-  const double *X = p.X + (size_t)f * d * N, *y = p.y + (size_t)f * N, *Z = p.Z + (size_t)f * d * m;
+  const double *X = p.X + (size_t)f * d * N, *y = p.y + (size_t)f * p.P * N, *Z = p.Z + (size_t)f * d * m;
   // the group's tiles; wave w holds tiles w, w + SP_WAVES, ... of the group
   const int first = g * tpg;
   const int last = (first + tpg < ntile ? first + tpg : ntile) - 1;
@@ -169,7 +181,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_phi(SparseArgs p) {
   const int n1 = n0 + p.sh.clen < N ? n0 + p.sh.clen : N;
   const int nsp = n1 > n0 ? (n1 - n0 + S - 1) / S : 0;
   __syncthreads();
-  // sub-panel sp into buffer `buf`: K(z_r, x_i) for r < m, y_i in row m, zero in the padding and past the chunk
+  // sub-panel sp into buffer `buf`: K(z_r, x_i) for r < m, target column q of x_i in row m + q, zero in the padding and past the chunk
   auto eval = [&](int sp, int buf) {
     double *Pb = P + (size_t)buf * S * ldr;
     const int tot = nrows * S;
@@ -179,7 +191,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_phi(SparseArgs p) {
       double v = 0.0;
       if (i < n1) {
         if (r < m) v = win_cov(kid, d, pr, Zl + r, LD, X + i, N, false);
-        else if (r == m) v = y[i];
+        else if (r < mP) v = y[(size_t)(r - m) * N + i];
       }
       Pb[s * ldr + r] = v;
     }
@@ -202,36 +214,42 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_phi(SparseArgs p) {
     }
     __syncthreads();
   }
-  double *out = p.part + (((size_t)f * p.sh.nch + ch) * ntile + first) * 256 + lane;
+  // tiles of the m x m objects' tile rows to the partial buffer, those of the tile rows further targets add to theirs
+  const size_t fc = (size_t)f * p.sh.nch + ch;
 #pragma unroll
   for (int t = 0; t < SP_TPW; ++t)
     if (live >> t & 1u) {
-      double *o = out + (size_t)(wave + SP_WAVES * t) * 256;
+      const int u = first + wave + SP_WAVES * t;
+      double *o = (u < nt0 ? p.part + (fc * nt0 + u) * 256 : p.partx + (fc * (ntile - nt0) + (u - nt0)) * 256) + lane;
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r * 64] = acc[t][r];
     }
 }
 
-// One workgroup per (tile, fit): the chunks' tiles summed in chunk order, unpacked into Phi, b and yty.
+// One workgroup per (tile, fit): the chunks' tiles summed in chunk order, unpacked into Phi (in the m x m objects' layout, whatever
+// P is), the b of every target column and its yty.
 __global__ __launch_bounds__(256) void k_sparse_reduce(SparseArgs p) {
   const int idx = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
-  const int m = p.m, LD = p.sh.LD, ntile = p.sh.ntile, nch = p.sh.nch;
+  const int m = p.m, LD = p.sh.LD, ntile = p.sh.ntile, nt0 = p.sh.nt0, nch = p.sh.nch;
   int I, J;
   sparse_tile(idx, I, J);
   const int lane = tid & 63, r = tid >> 6;
   const int i = I * WPB + (lane >> 4) + 4 * r, j = J * WPB + (lane & 15);
-  const double *src = p.part + ((size_t)f * nch * ntile + idx) * 256 + tid;
+  const int nt = idx < nt0 ? nt0 : ntile - nt0;   // tiles of a chunk in the buffer that holds this one
+  const double *src = (idx < nt0 ? p.part + ((size_t)f * nch * nt + idx) * 256 : p.partx + ((size_t)f * nch * nt + (idx - nt0)) * 256) + tid;
   double v = 0.0;
-  for (int c = 0; c < nch; ++c) v += src[(size_t)c * ntile * 256];
-  double *F = p.F + (size_t)f * LD * LD;
-  const double phi = (i < m && j < m) ? v : 0.0;
-  F[(size_t)i * LD + j] = phi;
-  if (I != J) F[(size_t)j * LD + i] = phi;   // (a diagonal tile holds both of its triangles itself)
-  if (i == m) {   // the y row: its tiles cover every column of the padded matrix
-    double *b = p.vec + (size_t)f * 4 * LD;
-    b[j] = j < m ? v : 0.0;
-    if (j == m) p.scal[(size_t)f * 8] = v;
+  for (int c = 0; c < nch; ++c) v += src[(size_t)c * nt * 256];
+  if (i < LD && j < LD) {
+    double *F = p.F + (size_t)f * LD * LD;
+    const double phi = (i < m && j < m) ? v : 0.0;
+    F[(size_t)i * LD + j] = phi;
+    if (I != J) F[(size_t)j * LD + i] = phi;   // (a diagonal tile holds both of its triangles itself)
   }
+  if (i >= m && i < m + p.P && j < LD) {   // a target's row: its tiles cover every column of the padded m x m objects
+    double *b = p.bm + (size_t)f * p.bcs + (size_t)(i - m) * LD;
+    b[j] = j < m ? v : 0.0;
+  }
+  if (i >= m && i < m + p.P && j == i) p.yty[(size_t)f * p.ytys + (i - m)] = v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -370,25 +388,35 @@ __device__ __forceinline__ void sparse_trsm(const double *L, const double *dinv,
   }
 }
 
-// x = L^-1 x for the vector x[ld] in LDS, block row by block row: sixteen partial sums per row in a fixed order, then the block's inverse
-__device__ __forceinline__ void sparse_vec_solve(const double *L, const double *dinv, double *x, double *red, double *rr, int ld, int mt,
-                                                 int tid) {
+// x = L^-1 x for the nq <= SPV_COLS vectors x[q][SP_LDMAX] in LDS, block row by block row: sixteen partial sums per row and vector in
+// a fixed order, then the block's inverse.  Each vector's arithmetic is its own and the same whatever nq is; L is read once for all.
+__device__ __forceinline__ void sparse_vec_solve(const double *L, const double *dinv, double *x, int nq, double *red, double *rr, int ld,
+                                                 int mt, int tid) {
   const int i = tid & 15, part = tid >> 4;
   for (int I = 0; I < mt; ++I) {
-    double s = 0.0;
-    for (int k = part; k < I * WPB; k += SPA_THREADS / 16) s = __builtin_fma(L[(size_t)k * ld + I * WPB + i], x[k], s);
-    red[part * WPB + i] = s;
+    double s[SPV_COLS];
+#pragma unroll
+    for (int q = 0; q < SPV_COLS; ++q) s[q] = 0.0;
+    for (int k = part; k < I * WPB; k += SPA_THREADS / 16) {
+      const double l = L[(size_t)k * ld + I * WPB + i];
+#pragma unroll
+      for (int q = 0; q < SPV_COLS; ++q)
+        if (q < nq) s[q] = __builtin_fma(l, x[q * SP_LDMAX + k], s[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < SPV_COLS; ++q)
+      if (q < nq) red[q * SPA_THREADS + part * WPB + i] = s[q];
     __syncthreads();
-    if (tid < WPB) {
-      double r = x[I * WPB + tid];
-      for (int q = 0; q < SPA_THREADS / 16; ++q) r -= red[q * WPB + tid];
+    if (tid < WPB * nq) {
+      double r = x[part * SP_LDMAX + I * WPB + i];
+      for (int q = 0; q < SPA_THREADS / 16; ++q) r -= red[part * SPA_THREADS + q * WPB + i];
       rr[tid] = r;
     }
     __syncthreads();
-    if (tid < WPB) {
+    if (tid < WPB * nq) {
       double v = 0.0;
-      for (int j = 0; j <= tid; ++j) v = __builtin_fma(dinv[I * (WPB * WPB) + j * WPB + tid], rr[j], v);
-      x[I * WPB + tid] = v;
+      for (int j = 0; j <= i; ++j) v = __builtin_fma(dinv[I * (WPB * WPB) + j * WPB + i], rr[part * WPB + j], v);
+      x[part * SP_LDMAX + I * WPB + i] = v;
     }
     __syncthreads();
   }
@@ -409,7 +437,7 @@ __device__ __forceinline__ double sparse_block_sum(double v, double *red, int ti
 }
 
 __global__ __launch_bounds__(SPA_THREADS) void k_sparse_algebra(SparseArgs p) {
-  __shared__ double tile[WPB * WPB], winv[WPB * WPB], red[SPA_THREADS], rr[WPB], xv[SP_LDMAX];
+  __shared__ double tile[WPB * WPB], winv[WPB * WPB], red[SPV_COLS * SPA_THREADS], rr[SPV_COLS * WPB], xv[SPV_COLS * SP_LDMAX];
   __shared__ int sbad;
   const int f = blockIdx.x, tid = threadIdx.x;
   const int N = p.N, m = p.m, d = p.d, kid = p.kid, LD = p.sh.LD, mt = p.sh.mt;
@@ -418,7 +446,10 @@ __global__ __launch_bounds__(SPA_THREADS) void k_sparse_algebra(SparseArgs p) {
   const double *Z = p.Z + (size_t)f * d * m, *X = p.X + (size_t)f * d * N;
   double *U = p.U + (size_t)f * LD * LD, *F = p.F + (size_t)f * LD * LD, *W = p.W + (size_t)f * LD * LD;
   double *dU = p.dinv + (size_t)f * 2 * mt * (WPB * WPB), *dB = dU + (size_t)mt * (WPB * WPB);
-  double *bv = p.vec + (size_t)f * 4 * LD, *cv = bv + LD, *da = cv + LD;
+  double *da = p.vec + (size_t)f * 4 * LD + 2 * LD;
+  const double *bm = p.bm + (size_t)f * p.bcs;
+  double *cm = p.cm + (size_t)f * p.bcs, *logml = p.logml + (size_t)f * p.P;
+  const int P = p.P;
   const double nan = __builtin_nan("");
   // K_uu + eps I, lower triangle (zero above the diagonal), identity in the padding
   for (int e = tid; e < LD * LD; e += SPA_THREADS) {
@@ -433,10 +464,8 @@ __global__ __launch_bounds__(SPA_THREADS) void k_sparse_algebra(SparseArgs p) {
   __syncthreads();
   int bad = sparse_chol(U, LD, mt, dU, tile, winv, &sbad, tid);
   if (bad != 0) {
-    if (tid == 0) {
-      p.info[f] = bad;
-      p.logml[f] = nan;
-    }
+    if (tid == 0) p.info[f] = bad;
+    if (tid < P) logml[tid] = nan;
     return;
   }
   sparse_trsm<false>(U, dU, F, W, LD, mt, tid);   // W = L_u^-1 Phi
@@ -452,41 +481,50 @@ __global__ __launch_bounds__(SPA_THREADS) void k_sparse_algebra(SparseArgs p) {
   __syncthreads();
   bad = sparse_chol(F, LD, mt, dB, tile, winv, &sbad, tid);
   if (bad != 0) {
-    if (tid == 0) {
-      p.info[f] = m + bad;
-      p.logml[f] = nan;
-    }
+    if (tid == 0) p.info[f] = m + bad;
+    if (tid < P) logml[tid] = nan;
     return;
   }
-  // c = L_B^-1 (L_u^-1 b) / sigma2
-  for (int i = tid; i < LD; i += SPA_THREADS) xv[i] = bv[i];
-  __syncthreads();
-  sparse_vec_solve(U, dU, xv, red, rr, LD, mt, tid);
-  for (int i = tid; i < LD; i += SPA_THREADS) xv[i] = xv[i] / sigma2;
-  __syncthreads();
-  sparse_vec_solve(F, dB, xv, red, rr, LD, mt, tid);
-  double s_ld = 0.0, s_cc = 0.0, s_tr = 0.0, s_t = 0.0;
-  for (int i = tid; i < LD; i += SPA_THREADS) {
-    const double c = xv[i];
-    cv[i] = c;
+  // the terms every target column shares
+  double s_ld = 0.0, s_tr = 0.0, s_t = 0.0;
+  for (int i = tid; i < LD; i += SPA_THREADS)
     if (i < m) {
       s_ld += log(F[(size_t)i * LD + i]);
-      s_cc += c * c;
       s_tr += da[i];
     }
-  }
   const WaCov kc = WaCov::from_prep(kid, d, pr);
   for (int i = tid; i < N; i += SPA_THREADS) s_t += kc.kss(X[i]);
   s_ld = sparse_block_sum(s_ld, red, tid);
-  s_cc = sparse_block_sum(s_cc, red, tid);
   s_tr = sparse_block_sum(s_tr, red, tid);
   s_t = sparse_block_sum(s_t, red, tid);
-  if (tid == 0) {
-    const double yty = p.scal[(size_t)f * 8];
-    const double LOG_2PI = 1.8378770664093454836;
-    p.logml[f] = -0.5 * N * LOG_2PI - 0.5 * N * log(sigma2) - s_ld - yty / (2.0 * sigma2) + 0.5 * s_cc - s_t / (2.0 * sigma2) + 0.5 * s_tr;
-    p.info[f] = 0;
+  // c = L_B^-1 (L_u^-1 b) / sigma2 and the bound, SPV_COLS target columns per pass over the block rows
+  for (int q0 = 0; q0 < P; q0 += SPV_COLS) {
+    const int nq = P - q0 < SPV_COLS ? P - q0 : SPV_COLS;
+    __syncthreads();
+    for (int q = 0; q < nq; ++q)
+      for (int i = tid; i < LD; i += SPA_THREADS) xv[q * SP_LDMAX + i] = bm[(size_t)(q0 + q) * LD + i];
+    __syncthreads();
+    sparse_vec_solve(U, dU, xv, nq, red, rr, LD, mt, tid);
+    for (int q = 0; q < nq; ++q)
+      for (int i = tid; i < LD; i += SPA_THREADS) xv[q * SP_LDMAX + i] = xv[q * SP_LDMAX + i] / sigma2;
+    __syncthreads();
+    sparse_vec_solve(F, dB, xv, nq, red, rr, LD, mt, tid);
+    for (int q = 0; q < nq; ++q) {
+      double s_cc = 0.0;
+      for (int i = tid; i < LD; i += SPA_THREADS) {
+        const double c = xv[q * SP_LDMAX + i];
+        cm[(size_t)(q0 + q) * LD + i] = c;
+        if (i < m) s_cc += c * c;
+      }
+      s_cc = sparse_block_sum(s_cc, red, tid);
+      if (tid == 0) {
+        const double yty = p.yty[(size_t)f * p.ytys + q0 + q];
+        const double LOG_2PI = 1.8378770664093454836;
+        logml[q0 + q] = -0.5 * N * LOG_2PI - 0.5 * N * log(sigma2) - s_ld - yty / (2.0 * sigma2) + 0.5 * s_cc - s_t / (2.0 * sigma2) + 0.5 * s_tr;
+      }
+    }
   }
+  if (tid == 0) p.info[f] = 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -500,9 +538,12 @@ __global__ __launch_bounds__(SPP_WAVES * 64) void k_sparse_predict(SparseArgs p)
   if (ct * WPB >= M) return;
   const int col = ct * WPB + l15;
   const bool colok = col < M;
-  double *mean = p.mean + (size_t)f * M, *var = p.var + (size_t)f * M;
-  if (p.info[f] != 0) {   // a failed fit: NaN
-    if (lq == 0 && colok) mean[col] = var[col] = __builtin_nan("");
+  double *mean = p.mean + (size_t)f * p.P * M, *var = p.var + (size_t)f * M;
+  if (p.info[f] != 0) {   // a failed fit: NaN in the variance and in every column's mean
+    if (lq == 0 && colok) {
+      var[col] = __builtin_nan("");
+      for (int q = 0; q < p.P; ++q) mean[(size_t)q * M + col] = __builtin_nan("");
+    }
     return;
   }
   double *V = reinterpret_cast<double *>(smem_raw) + (size_t)wave * LD * WPB;   // [LD][16] the tile, solved in place
@@ -511,8 +552,7 @@ __global__ __launch_bounds__(SPP_WAVES * 64) void k_sparse_predict(SparseArgs p)
   for (int row = lq; row < LD; row += 4)
     V[row * WPB + l15] = (row < m && colok) ? win_cov(kid, d, pr, Z + row, m, Xs + col, M, false) : 0.0;
   sparse_wave_sync();
-  const double *cvec = p.vec + (size_t)f * 4 * LD + LD;
-  double s1 = 0.0, s2 = 0.0, mu = 0.0;
+  double s1 = 0.0, s2 = 0.0;
   // V = L^-1 V, block row by block row; the next L block is requested before this one's MFMAs
   auto solve = [&](const double *L, const double *dinv, bool second) {
     for (int I = 0; I < mt; ++I) {
@@ -545,12 +585,8 @@ __global__ __launch_bounds__(SPP_WAVES * 64) void k_sparse_predict(SparseArgs p)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         V[(I * WPB + lq + 4 * r) * WPB + l15] = v[r];   // (the lane's own four elements of the block row)
-        if (second) {
-          s2 = __builtin_fma(v[r], v[r], s2);
-          mu = __builtin_fma(v[r], cvec[I * WPB + lq + 4 * r], mu);
-        } else {
-          s1 = __builtin_fma(v[r], v[r], s1);
-        }
+        if (second) s2 = __builtin_fma(v[r], v[r], s2);
+        else s1 = __builtin_fma(v[r], v[r], s1);
       }
       sparse_wave_sync();
     }
@@ -564,14 +600,23 @@ __global__ __launch_bounds__(SPP_WAVES * 64) void k_sparse_predict(SparseArgs p)
   s1 += __shfl_xor(s1, 32);
   s2 += __shfl_xor(s2, 16);
   s2 += __shfl_xor(s2, 32);
-  mu += __shfl_xor(mu, 16);
-  mu += __shfl_xor(mu, 32);
   if (lq == 0 && colok) {
     const WaCov kc = WaCov::from_prep(kid, d, pr);
     double v = kc.kss(Xs[col]) - s1 + s2;
     v = v < 1e-15 ? 1e-15 : v;
-    mean[col] = mu;
     var[col] = p.include_noise ? v + pr[SP_R_NOISE] : v;
+  }
+  // mean = V2^T c, column by column from the finished tile: one fma chain down the lane's rows, as the rows were finished
+  for (int q = 0; q < p.P; ++q) {
+    const double *cvec = p.cm + (size_t)f * p.bcs + (size_t)q * LD;
+    double mu = 0.0;
+    for (int I = 0; I < mt; ++I) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mu = __builtin_fma(V[(I * WPB + lq + 4 * r) * WPB + l15], cvec[I * WPB + lq + 4 * r], mu);
+    }
+    mu += __shfl_xor(mu, 16);
+    mu += __shfl_xor(mu, 32);
+    if (lq == 0 && colok) mean[(size_t)q * M + col] = mu;
   }
 }
 

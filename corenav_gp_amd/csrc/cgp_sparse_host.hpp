@@ -36,6 +36,7 @@ struct SparseCall {   // the call's arrays (device, the call's first fit) and sh
   const double *X, *y, *Z, *Xs, *theta, *jitter;
   double *mean, *var, *logml;
   int *info;
+  int P = 1;   // target columns: y (fit, P, N), mean (fit, P, M), logml (fit, P); more than one in cgp_sparse_multi_host.hpp's calls only
 };
 
 // the argument record of the launches for the `nfit` fits in slots slot, slot + 1, ... of the call's arrays and of the scratch
@@ -44,26 +45,33 @@ SparseArgs sparse_args(const cgp_ctx *c, const SparseCall &k, int slot, int nfit
   double *buf = static_cast<double *>(c->sp.buf);
   const size_t s = slot;
   SparseArgs a{};
-  a.sh = sparse_shape(k.N, k.m, k.d);
+  a.sh = sparse_shape(k.N, k.m, k.d, k.P);
   const size_t LD = a.sh.LD, LD2 = LD * LD;
   a.X = k.X + s * k.d * k.N;
-  a.y = k.y + s * k.N;
+  a.y = k.y + s * k.P * k.N;
   a.Z = k.Z + s * k.d * k.m;
   a.Xs = k.Xs ? k.Xs + s * k.d * k.M : nullptr;
   a.theta = k.theta + s * MAX_THETA;
   a.jitter = k.jitter ? k.jitter + s : nullptr;
-  a.mean = k.mean ? k.mean + s * k.M : nullptr;
+  a.mean = k.mean ? k.mean + s * k.P * k.M : nullptr;
   a.var = k.var ? k.var + s * k.M : nullptr;
-  a.logml = k.logml + s;
+  a.logml = k.logml + s * k.P;
   a.info = k.info + s;
   a.rec = buf + l.rec + s * PREP_N;
-  a.part = buf + l.part + s * a.sh.nch * a.sh.ntile * 256;
+  a.part = buf + l.part + s * a.sh.nch * a.sh.nt0 * 256;
   a.U = buf + l.U + s * LD2;
   a.F = buf + l.F + s * LD2;
   a.W = buf + l.W + s * LD2;
   a.dinv = buf + l.dinv + s * 2 * a.sh.mt * 256;
   a.vec = buf + l.vec + s * 4 * LD;
   a.scal = buf + l.scal + s * 8;
+  // one target column: b, c and yty where the gradient kernels read them (sparse_multi_args points several elsewhere)
+  a.bm = a.vec;
+  a.cm = a.vec + LD;
+  a.yty = a.scal;
+  a.bcs = (int)(4 * LD);
+  a.ytys = 8;
+  a.P = k.P;
   a.N = k.N; a.d = k.d; a.M = k.M; a.m = k.m; a.kid = k.kid; a.include_noise = k.include_noise; a.nfit = nfit;
   return a;
 }
@@ -77,8 +85,8 @@ int sparse_enqueue(cgp_ctx *c, const SparseArgs &a, hipStream_t s) {
   L.begin(4, 0.0);
   hipLaunchKernelGGL(k_sparse_prep, dim3(cdiv(a.nfit, 64)), dim3(64), 0, s, a);
   L.end();
-  L.begin(0, fits * a.N * (mm + 1) * (mm + 2));
-  hipLaunchKernelGGL(k_sparse_phi, dim3(sh.ngrp, sh.nch, a.nfit), dim3(SP_THREADS), sparse_phi_lds(a.d, sh.LD, sh.S, sh.ldr), s, a);
+  L.begin(0, fits * a.N * (mm + a.P) * (mm + a.P + 1));
+  hipLaunchKernelGGL(k_sparse_phi, dim3(sh.ngrp, sh.nch, a.nfit), dim3(SP_THREADS), sparse_phi_lds(a.d, sh.LDa, sh.S, sh.ldr), s, a);
   L.end();
   L.begin(2, fits * sh.nch * sh.ntile * 256);
   hipLaunchKernelGGL(k_sparse_reduce, dim3(sh.ntile, a.nfit), dim3(256), 0, s, a);

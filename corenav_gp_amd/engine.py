@@ -116,6 +116,10 @@ _SIGS = {
                                                                               _dp, _ip]),
     "cgp_sparse_nll_grad_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_vp] * 7 + [ctypes.c_int, _vp, _vp, _vp]),
     "cgp_optimize_sparse_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 5 + [_dp] * 4 + [ctypes.c_int] * 3 + [_dp, _ip]),
+    "cgp_sparse_multi_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "cgp_fit_predict_sparse_multi_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_dp] * 5 + [ctypes.c_int, ctypes.c_int,
+                                                                                                   _dp, _dp, _dp, _ip]),
+    "cgp_fit_predict_sparse_multi_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp] * 6 + [ctypes.c_int] + [_vp] * 5),
     "cgp_fit_predict_trend_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_dp] * 6 + [ctypes.c_int, ctypes.c_int,
                                                                                           _dp, _dp, _dp, _dp, _ip, _ip]),
     "cgp_fit_predict_trend_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp] * 7 + [ctypes.c_int] + [_vp] * 7),
@@ -718,6 +722,38 @@ class Context:
         if rc > 0:
             raise CgpError(rc)
         return theta, Z, bound, nev
+
+    # -- sparse fits: P target columns share one inducing-point fit (fp64 contexts) -----------------------------------
+    def sparse_multi_reserve(self, max_batch, max_p):
+        """What up to max_p <= 64 target columns add to the sparse scratch; needs a sparse_reserve that covers max_batch and is
+        sized by it."""
+        return self._chk(self.lib.cgp_sparse_multi_reserve(self.h, int(max_batch), int(max_p)))
+
+    def fit_predict_sparse_multi_batch(self, X, Y, Z, Xs, theta, kernel_id, include_noise=True):
+        """X (B, N, d), Y (B, P, N), Z (B, m, d), Xs (B, M, d) or None (M = 0: the bounds only), theta (B, nth) ->
+        (rc, mean (B, P, M), var (B, M), bound (B, P), info (B,)): one Phi, one pair of factors and one variance per fit;
+        bound[b, p] is what fit_predict_sparse_batch returns for y = Y[b, p].  A failed fit has NaN in all its outputs."""
+        X, Y, Z, theta = _d(X), _d(Y), _d(Z), _d(theta)
+        B, N, d = X.shape
+        m, P = Z.shape[1], Y.shape[1]
+        assert Y.shape == (B, P, N) and Z.shape == (B, m, d)
+        M = 0 if Xs is None else np.shape(Xs)[1]
+        Xs = _d(Xs) if M > 0 else None
+        mean, var = np.empty((B, P, M)), np.empty((B, M))
+        logml, info = np.empty((B, P)), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_fit_predict_sparse_multi_batch(self.h, B, N, d, M, P, m, kernel_id, _p(X), _p(Y), _p(Z),
+                                                                   _p(Xs) if M > 0 else None, _p(theta), theta.shape[1],
+                                                                   int(include_noise), _p(mean) if M > 0 else None,
+                                                                   _p(var) if M > 0 else None, _p(logml), info.ctypes.data_as(_ip)))
+        return rc, mean, var, logml, info
+
+    def fit_predict_sparse_multi_batch_device(self, B, N, d, M, P, m, kernel_id, dX, dY, dZ, dXs, dtheta, djitter, include_noise,
+                                              dmean, dvar, dlogml, dinfo, stream=0):
+        """Device pointers as fit_predict_sparse_batch_device with dY (B, P, N), dmean (B, P, M), dvar (B, M), dlogml (B, P)."""
+        return self._chk(self.lib.cgp_fit_predict_sparse_multi_batch_device(self.h, B, N, d, M, P, m, kernel_id, dX, dY, dZ,
+                                                                            dXs or None, dtheta, djitter or None,
+                                                                            int(include_noise), dmean or None, dvar or None,
+                                                                            dlogml, dinfo, ctypes.c_void_p(stream)))
 
     # -- multi-target fits: gradient and optimiser of the summed logML (fp64 contexts) ------------------------
     def multi_grad_reserve(self, max_batch, max_p):

@@ -613,8 +613,9 @@ int cgp_fit_predict_trend_batch_device(cgp_ctx *ctx, int batch, int N, int d, in
  * cgp_profile_*: the launches of a sparse call are recorded under 0 k_sparse_phi (flops = N (m + 1)(m + 2) per fit), 1
  * k_sparse_algebra, 2 k_sparse_reduce, 3 k_sparse_predict, 4 k_sparse_prep.
  *
- * The gradient of the bound in theta and Z and the optimiser over them are the next section's.  Not provided: FITC; several target
- * columns; the resident windows; fp32 contexts; a cgp_sweep_* form. */
+ * The gradient of the bound in theta and Z and the optimiser over them are the next section's; several target columns on one fit
+ * are the section after it (cgp_fit_predict_sparse_multi_batch).  Not provided: FITC; the resident windows; fp32 contexts; a
+ * cgp_sweep_* form. */
 int cgp_sparse_reserve(cgp_ctx *ctx, int max_batch, int max_n, int max_m_ind, int max_m);
 /* Samples of the shortest chunk of the sum over N (512): the split above, for tests that sit on its edges. */
 int cgp_sparse_chunk(void);
@@ -669,7 +670,8 @@ int cgp_fit_predict_sparse_batch_device(cgp_ctx *ctx, int batch, int N, int d, i
  * k_sparse_grad_algebra), slot 2 k_sparse_reduce + k_sparse_grad_uu + k_sparse_grad_finish, slot 3 k_sparse_grad_panel (the predict
  * kernel never runs at M = 0; flops = 2 N (m + 1) LD per fit), slot 4 k_sparse_prep.
  *
- * Not provided: FITC; several target columns; the resident windows; fp32 contexts; a cgp_sweep_* form. */
+ * Not provided: FITC; the gradient of several target columns' summed bound (the forward half is the section after this one); the
+ * resident windows; fp32 contexts; a cgp_sweep_* form. */
 int cgp_sparse_grad_reserve(cgp_ctx *ctx, int max_batch);
 /* Host buffers, blocks; layouts as cgp_fit_predict_sparse_batch, grad (batch, grad_stride), gradZ (batch, m, d) or NULL, info
  * (batch) or NULL.  A fit whose K_uu fails climbs the jitter ladder of cgp_fit_predict_sparse_batch, re-submitted alone into its
@@ -691,6 +693,69 @@ int cgp_sparse_nll_grad_batch_device(cgp_ctx *ctx, int batch, int N, int d, int 
 int cgp_optimize_sparse_batch(cgp_ctx *ctx, int batch, int N, int d, int m, int kernel_id, const double *X, const double *y,
                               double *Z_inout, double *theta_inout, int theta_stride, int optimize_z, int max_evals,
                               double *logml, int *n_evals);
+
+/* ---- sparse fits: P target columns share one inducing-point fit ------------------------------------------
+ * GPy's SparseGPRegression(X, Y, Z=Z) with Y (N, P) -- four wheels' slip over one recorded history: Phi = K_uf K_fu, both m x m
+ * factors and the variance do not depend on the targets, so they are computed ONCE per (X, Z, theta).  With the sparse section's
+ * quantities, b, yty and c per column p:
+ *   b_p = K_uf y_p      yty_p = y_p^T y_p      c_p = L_B^-1 L_u^-1 b_p / sigma2
+ *   logml[p] = -N/2 log 2 pi - N/2 log sigma2 - sum log diag(L_B) - yty_p / (2 sigma2) + c_p^T c_p / 2 - t / (2 sigma2) + tr(A) / 2
+ *   mean[p] = V2^T c_p      var = the single-column call's, shared by the P columns
+ * logml[p] is what cgp_fit_predict_sparse_batch returns for y = Y[p]; GPy's objective for the model is sum_p logml[p]
+ * (cgp_fit_predict_multi_batch's convention).  info is per fit; a failed fit has NaN in all P means, in var and in all P bounds.
+ * The targets ride as rows m .. m + P - 1 of the augmented matrix whose row m carries y in a single-column call: K(Z, x_i) is
+ * evaluated once and Phi accumulated once whatever P is, and the launches are the single-column call's (which IS this chain at P =
+ * 1): five, four at M = 0.  For P <= 16 ceil((m + 1) / 16) - m the augmented matrix has no more 16-row tiles than at P = 1.
+ *
+ * Layouts.  Host form: as cgp_fit_predict_sparse_batch with Y (batch, P, N), mean (batch, P, M), var (batch, M), logml (batch, P),
+ * info (batch).  Device form: cgp_fit_predict_sparse_batch_device's SoA layouts with dY (batch, P, N), dmean (batch, P, M), dvar
+ * (batch, M), dlogml (batch, P), dinfo (batch).  M = 0 gives the P bounds only.
+ *
+ * Promises.
+ *  1. The sparse calls above, the gradient and the optimiser are bitwise what they were before this section existed.
+ *  2. var and info are bitwise cgp_fit_predict_sparse_batch[_device]'s for the same (X, Z, theta, Xs), for every P.
+ *  3. A column's mean row and logml are a function of that column's targets and of the fit's (X, Z, theta, Xs, N, m, M, d, kernel):
+ *     bitwise independent of P, of the column's position p and of the other columns (a NaN among another column's targets included),
+ *     of the batch size, the slot and the neighbouring fits.  Permuting the columns permutes the outputs; the first columns of a
+ *     wide call are the same columns of a narrower call.  No atomics; every sum runs in a fixed order over the real N.
+ *  4. A column's mean row and logml are BITWISE cgp_fit_predict_sparse_batch[_device]'s on y = Y[p] (not merely within the 1e-9
+ *     that two schedules of the dense multi call keep): every element of the augmented product is its own accumulator chain in
+ *     sample order, c_p is solved by the single-column call's per-column arithmetic and the mean by its fma chain.
+ *  5. Host form (for a fit that needed no ladder step), device form and a replayed graph agree bitwise.
+ *
+ * cgp_sparse_multi_reserve: what P columns add to the sparse scratch.  Needs a cgp_sparse_reserve that covers it (max_batch within
+ * it), else CGP_ESTATE, and is sized by that reservation's max_n and max_m_ind as they stand at the call: with mt = ceil((max_m_ind
+ * + 1) / 16), LD = 16 mt, C = min(ceil(max_n / 512), 16) and k = ceil((max_p - 1) / 16) -- the 16-row tile rows that the targets of
+ * a call within it can add -- it allocates
+ *   8 max_batch (128 C k (2 mt + k + 1) + 2 max_p LD + max_p) bytes
+ * (max_n = 65 536, max_m_ind = 256: max_p = 4 0.61 MB, max_p = 16 0.66 MB, max_p = 64 2.8 MB per fit).  1 <= max_batch <=
+ * the context's and 1 <= max_p <= CGP_SPARSE_MAX_P, else CGP_EINVAL; CGP_ENOMEM leaves no reservation; calling it again replaces the
+ * reservation.  A later cgp_sparse_reserve does not widen it: batch, N and m of a call must fit both.  Blocks.  cgp_destroy frees it.
+ *
+ * Status of the two calls, in this order: CGP_EINVAL in a CGP_F32 context, for batch, N, d, P or m < 1, P > CGP_SPARSE_MAX_P, m >
+ * 512, M < 0, an unknown kernel id or RBF x Brownian with d != 1; without either reservation CGP_ESTATE; batch, N, m, M or P beyond
+ * them, d beyond the context's max_d CGP_ECAPACITY; a NULL required pointer or theta_stride < ntheta CGP_EINVAL.  All of these return
+ * before anything is enqueued.
+ *
+ * cgp_profile_*: the slots of a sparse call (flops of slot 0: N (m + P)(m + P + 1) per fit).
+ *
+ * Not provided: the gradient of the summed bound in theta and Z and its optimiser; a trend on the sparse fits; FITC; the resident
+ * windows; fp32 contexts; a cgp_sweep_* form. */
+#define CGP_SPARSE_MAX_P 64
+int cgp_sparse_multi_reserve(cgp_ctx *ctx, int max_batch, int max_p);
+/* Host buffers, blocks.  A fit whose K_uu fails climbs the jitter ladder of cgp_fit_predict_sparse_batch on K_uu, re-submitted alone
+ * into its slot with all its columns; a failing pivot of B is reported as it is.  logml and info may be NULL.  Returns a negative
+ * error, else 0 or the first non-zero per-fit info. */
+int cgp_fit_predict_sparse_multi_batch(cgp_ctx *ctx, int batch, int N, int d, int M, int P, int m, int kernel_id,
+                                       const double *X, const double *Y, const double *Z, const double *Xs, const double *theta,
+                                       int theta_stride, int include_noise, double *mean, double *var, double *logml, int *info);
+/* Device-resident variant: the single-column call's five launches (four when M = 0) in a linear chain on hip_stream; no allocation,
+ * no synchronisation, no jitter ladder (capturable into a hipGraph with default settings).  dlogml and dinfo are required.  The
+ * extent contract at cgp_fit_predict_batch_device applies. */
+int cgp_fit_predict_sparse_multi_batch_device(cgp_ctx *ctx, int batch, int N, int d, int M, int P, int m, int kernel_id,
+                                              const double *dX, const double *dY, const double *dZ, const double *dXs,
+                                              const double *dtheta, const double *djitter, int include_noise,
+                                              double *dmean, double *dvar, double *dlogml, int *dinfo, void *hip_stream);
 
 /* ---- multi-target fits: gradient and optimiser of the summed logML ------------------------------------
  * m.optimize() of the multi-column model (gp_slip_node.py:36 with Y (N, P)): ONE theta per fit maximises
