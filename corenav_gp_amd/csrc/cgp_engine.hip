@@ -223,6 +223,11 @@ struct cgp_ctx {
   // of the host call
   Scratch sm;
   int sm_max_n = 0, sm_max_ind = 0;
+  // the objective of several target columns on one sparse fit (cgp_sparse_multi_grad_reserve): the operand image of That where the
+  // targets add a tile row and the columns' bounds, for up to max_batch fits of mg_max_ind inducing inputs and max_dim columns
+  // (cgp_sparse_multi_grad_host.hpp, sparse_multi_grad_layout); staging of the host calls
+  Scratch mg;
+  int mg_max_ind = 0;
   // multi-target objective (cgp_multi_grad_reserve): A = Ky^-1 Y of up to max_batch fits x max_dim targets, [fit][P padded to 16][NT 128],
   // then (max_batch, max_dim) logml; staging of the host calls [Y | nll | grad | logml]
   Scratch ma;
@@ -941,7 +946,7 @@ void cgp_destroy(cgp_ctx *c) {
   for (auto e : c->ev_look)
     if (e) (void)hipEventDestroy(e);
   window_drop(c, WinDrop::Windows);
-  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->sp, &c->sg, &c->sm, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
+  for (Scratch *r : {&c->fj, &c->mz, &c->tr, &c->sp, &c->sg, &c->sm, &c->mg, &c->ma, &c->pg, &c->lg}) scratch_free(*r);
   if (c->win_pin) (void)hipHostFree(c->win_pin);
   if (c->opt_pin) (void)hipHostFree(c->opt_pin);
   if (c->win_dev) (void)hipFree(c->win_dev);
@@ -2407,3 +2412,6 @@ extern "C" int cgp_loo(cgp_ctx *c, const double *X, const double *y, int N, int 
 
 // sparse fits with several target columns: cgp_sparse_multi_reserve ... cgp_fit_predict_sparse_multi_batch_device
 #include "cgp_sparse_multi_host.hpp"
+
+// the objective of sparse fits with several target columns: cgp_sparse_multi_grad_reserve ... cgp_optimize_sparse_multi_batch
+#include "cgp_sparse_multi_grad_host.hpp"

@@ -34,6 +34,18 @@
 //                          fit whose info is not 0.
 // Every sum has a fixed order and every output is a function of the fit's own data and of (N, m, d, kernel, WITH_Z) only; the theta
 // sums are written with explicit fma so that the WITH_Z instantiation rounds them as the other one does.
+//
+// P target columns on one fit (SparseArgs::P; the formulas above are P = 1, and the single-column call runs these kernels at P = 1
+// on the buffers it always used): F = sum_p bound[p], C = [c_1 ... c_P],
+//   Chat = L_B^-T C      M = L_u^-T Chat      Q = P (I - B^-1) - Chat Chat^T      G_uu = 1/2 L_u^-T (Q - P A) L_u^-1
+//   R = 2 T K_uf + M Y / sigma2 = 2 That Phat,   That = [T | M / (2 sigma2)] (m x (m + P)),   Phat = [K_uf; Y] ((m + P) x N)
+//   dF/dsigma_n2 = (-N P + (sum_p yty_p + P t) / sigma2 - P tr A + P m - P tr B^-1 - ||C||^2 - ||Chat||^2) / (2 sigma2)
+// and the t-term P times.  k_sparse_grad_algebra takes the columns through the vector solves SPV_COLS at a time (sixty-four
+// vectors of length LD do not fit LDS): each pass folds its rank-nq term into Q in column order, adds to ||C||^2 and ||Chat||^2 in
+// column order and leaves its columns of M in the forward chain's spent b vectors; every vector keeps its own partial sums, order
+// and fma chain.  The image of That and the LDS panel have LDa = 16 ceil((m + P) / 16) columns / rows: k_sparse_grad_panel issues
+// LDa / 4 MFMAs per sub-panel into the same 16 x S tile.  The image is 16 mtr LDa doubles: in A's spent block while LDa = LD, in the
+// multi-gradient reservation's beyond (cgp_sparse_multi_grad_host.hpp).  nll is the columns' bounds summed in column order.
 #pragma once
 #include "cgp_sparse.hpp"
 #include "cgp_window_pgrad.hpp"
@@ -58,39 +70,51 @@ inline size_t sparse_grad_panel_lds(int d, int LD, int S) { return ((size_t)d * 
 
 struct SparseGradArgs {
   // the gradient reservation's scratch, at the call's first fit, strided by the call's own shape
-  double *A;       // [fit][LD][LD] k_sparse_algebra's copy of A, row-major; then the operand image of That: [row tile][LD / 4][64]
+  double *A;       // [fit][LD][LD] k_sparse_algebra's copy of A, row-major; then (LDa = LD) the operand image of That
   double *Th;      // [fit][LD][LD] work matrix (identity, B^-1, Q, T)
   double *G;       // [fit][LD][LD] Q - A, then G_uu, row-major
   double *tpart;   // [fit][nch][mtr][GRAD_N] the panel pass's theta sums
   double *zpart;   // [fit][nch][LD][MAXD] its Z sums (RBF x Brownian: slot 1 holds the term of min(|z|, |x|))
   double *upart;   // [fit][mtr][GRAD_N] k_sparse_grad_uu's theta sums
   double *uz;      // [fit][LD][MAXD] its Z sums
-  double *gs;      // [fit][4] dF/dsigma_n^2, -t / (2 sigma2)
-  double *nll, *grad, *gradZ;   // outputs: (fit), (fit, grad_stride), (fit, d, m) or null
+  double *gs;      // [fit][4] dF/dsigma_n^2, -P t / (2 sigma2)
+  double *Ti;      // the operand image of That, [row tile][LDa / 4][64] per fit, fits tifs doubles apart: A's block where LDa = LD (A
+  size_t tifs;     // is spent by then), the multi-gradient reservation's where the target rows add a tile row
+  double *nll, *grad, *gradZ, *lout;   // outputs: (fit), (fit, grad_stride), (fit, d, m) or null, (fit, P) or null
   int grad_stride;
   SparseGradShape gh;
 };
 
-// x = L^-T x for the vector x[ld] in LDS, from the last block row up: sparse_vec_solve's scheme on the transposed blocks
-__device__ __forceinline__ void sparse_vec_solve_t(const double *L, const double *dinv, double *x, double *red, double *rr, int ld, int mt,
-                                                   int tid) {
+// x = L^-T x for the nq <= SPV_COLS vectors x[q][SP_LDMAX] in LDS, from the last block row up: sparse_vec_solve's scheme on the
+// transposed blocks.  Each vector's arithmetic is its own and the same whatever nq is; L is read once for all.
+__device__ __forceinline__ void sparse_vec_solve_t(const double *L, const double *dinv, double *x, int nq, double *red, double *rr, int ld,
+                                                   int mt, int tid) {
   const int i = tid & 15, part = tid >> 4;
   for (int I = mt - 1; I >= 0; --I) {
     const double *col = L + (size_t)(I * WPB + i) * ld;   // column I 16 + i of L: row i of the transposed blocks
-    double s = 0.0;
-    for (int k = (I + 1) * WPB + part; k < ld; k += SPA_THREADS / 16) s = __builtin_fma(col[k], x[k], s);
-    red[part * WPB + i] = s;
+    double s[SPV_COLS];
+#pragma unroll
+    for (int q = 0; q < SPV_COLS; ++q) s[q] = 0.0;
+    for (int k = (I + 1) * WPB + part; k < ld; k += SPA_THREADS / 16) {
+      const double l = col[k];
+#pragma unroll
+      for (int q = 0; q < SPV_COLS; ++q)
+        if (q < nq) s[q] = __builtin_fma(l, x[q * SP_LDMAX + k], s[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < SPV_COLS; ++q)
+      if (q < nq) red[q * SPA_THREADS + part * WPB + i] = s[q];
     __syncthreads();
-    if (tid < WPB) {
-      double r = x[I * WPB + tid];
-      for (int q = 0; q < SPA_THREADS / 16; ++q) r -= red[q * WPB + tid];
+    if (tid < WPB * nq) {   // (here `part` is the vector)
+      double r = x[part * SP_LDMAX + I * WPB + i];
+      for (int q = 0; q < SPA_THREADS / 16; ++q) r -= red[part * SPA_THREADS + q * WPB + i];
       rr[tid] = r;
     }
     __syncthreads();
-    if (tid < WPB) {
+    if (tid < WPB * nq) {
       double v = 0.0;
-      for (int j = tid; j < WPB; ++j) v = __builtin_fma(dinv[I * (WPB * WPB) + tid * WPB + j], rr[j], v);
-      x[I * WPB + tid] = v;
+      for (int j = i; j < WPB; ++j) v = __builtin_fma(dinv[I * (WPB * WPB) + i * WPB + j], rr[part * WPB + j], v);
+      x[part * SP_LDMAX + I * WPB + i] = v;
     }
     __syncthreads();
   }
@@ -150,77 +174,100 @@ __device__ __forceinline__ void sparse_trsm_t(const double *L, const double *din
 }
 
 __global__ __launch_bounds__(SPA_THREADS) void k_sparse_grad_algebra(SparseArgs p, SparseGradArgs g) {
-  __shared__ double red[SPA_THREADS], rr[WPB], xv[SP_LDMAX], mu[SP_LDMAX];
+  __shared__ double red[SPV_COLS * SPA_THREADS], rr[SPV_COLS * WPB], xv[SPV_COLS * SP_LDMAX];
   const int f = blockIdx.x, tid = threadIdx.x;
   if (p.info[f] != 0) return;   // (k_sparse_grad_finish writes the NaNs)
-  const int N = p.N, m = p.m, d = p.d, kid = p.kid, LD = p.sh.LD, mt = p.sh.mt;
+  const int N = p.N, m = p.m, d = p.d, kid = p.kid, LD = p.sh.LD, mt = p.sh.mt, LDa = p.sh.LDa, P = p.P;
+  const double Pd = (double)P;
   const double *pr = p.rec + (size_t)f * PREP_N;
   const double sigma2 = pr[SP_R_SIGMA2];
   const double *X = p.X + (size_t)f * d * N;
   const double *U = p.U + (size_t)f * LD * LD, *F = p.F + (size_t)f * LD * LD;
   double *W = p.W + (size_t)f * LD * LD;
   const double *dU = p.dinv + (size_t)f * 2 * mt * (WPB * WPB), *dB = dU + (size_t)mt * (WPB * WPB);
-  const double *cv = p.vec + (size_t)f * 4 * LD + LD, *da = cv + LD;
+  const double *cm = p.cm + (size_t)f * p.bcs, *da = p.vec + (size_t)f * 4 * LD + 2 * LD;
+  double *mus = p.bm + (size_t)f * p.bcs;   // [P][LD] the columns of M: the b of the forward chain are spent
   double *A = g.A + (size_t)f * LD * LD, *Th = g.Th + (size_t)f * LD * LD, *G = g.G + (size_t)f * LD * LD;
-  // chat = L_B^-T c, mu = L_u^-T chat
-  for (int i = tid; i < LD; i += SPA_THREADS) xv[i] = cv[i];
-  __syncthreads();
-  sparse_vec_solve_t(F, dB, xv, red, rr, LD, mt, tid);
-  for (int i = tid; i < LD; i += SPA_THREADS) mu[i] = xv[i];
-  __syncthreads();
-  sparse_vec_solve_t(U, dU, mu, red, rr, LD, mt, tid);
   // B^-1 = L_B^-T (L_B^-1 I)
   for (int e = tid; e < LD * LD; e += SPA_THREADS) Th[e] = (e / LD == e % LD) ? 1.0 : 0.0;
   __syncthreads();
   sparse_trsm<false>(F, dB, Th, W, LD, mt, tid);
   sparse_trsm_t<false>(F, dB, W, Th, LD, mt, tid);
-  // Q = I - B^-1 - chat chat^T into Th, Q - A into G: zero in the padding
-  double s_tb = 0.0;
-  for (int e = tid; e < LD * LD; e += SPA_THREADS) {
-    const int i = e / LD, j = e - i * LD;
-    double q = 0.0, qa = 0.0;
-    if (i < m && j < m) {
-      const double bi = Th[e];
-      q = ((i == j ? 1.0 : 0.0) - bi) - xv[i] * xv[j];
-      qa = q - A[e];
-      if (i == j) s_tb += bi;
+  // SPV_COLS target columns per pass: chat = L_B^-T c, the pass's rank-nq term of Q in column order, mu = L_u^-T chat.  Q is
+  // built in Th pass by pass -- the first starts it from P (I - B^-1), the last also leaves Q - P A in G; zero in the padding --,
+  // one sweep over the matrix per pass (P <= SPV_COLS: the one sweep the single column always took)
+  double s_tb = 0.0, s_hh = 0.0, s_cc = 0.0;   // tr B^-1; ||Chat||^2 and ||C||^2, summed in column order
+  for (int q0 = 0; q0 < P; q0 += SPV_COLS) {
+    const int nq = P - q0 < SPV_COLS ? P - q0 : SPV_COLS;
+    const bool first = q0 == 0, last = q0 + SPV_COLS >= P;
+    __syncthreads();
+    for (int q = 0; q < nq; ++q)
+      for (int i = tid; i < LD; i += SPA_THREADS) xv[q * SP_LDMAX + i] = cm[(size_t)(q0 + q) * LD + i];
+    __syncthreads();
+    for (int q = 0; q < nq; ++q) {
+      double s = 0.0;
+      for (int i = tid; i < m; i += SPA_THREADS) s += xv[q * SP_LDMAX + i] * xv[q * SP_LDMAX + i];
+      s_cc += sparse_block_sum(s, red, tid);
     }
-    Th[e] = q;
-    G[e] = qa;
+    __syncthreads();
+    sparse_vec_solve_t(F, dB, xv, nq, red, rr, LD, mt, tid);
+    for (int e = tid; e < LD * LD; e += SPA_THREADS) {
+      const int i = e / LD, j = e - i * LD;
+      double q = 0.0, qa = 0.0;
+      if (i < m && j < m) {
+        q = Th[e];
+        if (first) {   // (Th holds B^-1)
+          if (i == j) s_tb += q;
+          q = Pd * ((i == j ? 1.0 : 0.0) - q);
+        }
+        for (int c = 0; c < nq; ++c) q = q - xv[c * SP_LDMAX + i] * xv[c * SP_LDMAX + j];
+        if (last) qa = q - Pd * A[e];
+      }
+      Th[e] = q;
+      if (last) G[e] = qa;
+    }
+    for (int q = 0; q < nq; ++q) {
+      double s = 0.0;
+      for (int i = tid; i < m; i += SPA_THREADS) s += xv[q * SP_LDMAX + i] * xv[q * SP_LDMAX + i];
+      s_hh += sparse_block_sum(s, red, tid);
+    }
+    __syncthreads();   // (chat is spent: the columns of M are solved in its place)
+    sparse_vec_solve_t(U, dU, xv, nq, red, rr, LD, mt, tid);
+    for (int q = 0; q < nq; ++q)
+      for (int i = tid; i < LD; i += SPA_THREADS) mus[(size_t)(q0 + q) * LD + i] = xv[q * SP_LDMAX + i];
   }
   __syncthreads();
   sparse_trsm_t<false>(U, dU, Th, W, LD, mt, tid);   // W = L_u^-T Q
   sparse_trsm_t<true>(U, dU, W, Th, LD, mt, tid);    // Th = L_u^-T W^T = L_u^-T Q L_u^-1
   sparse_trsm_t<false>(U, dU, G, W, LD, mt, tid);
-  sparse_trsm_t<true>(U, dU, W, G, LD, mt, tid);     // G = L_u^-T (Q - A) L_u^-1
-  // That = [T | mu] / (2 sigma2) as the operand image (A's block: A is spent), G_uu = G / 2
+  sparse_trsm_t<true>(U, dU, W, G, LD, mt, tid);     // G = L_u^-T (Q - P A) L_u^-1
+  // That = [T | M] / (2 sigma2) as the operand image (A is spent), G_uu = G / 2
   const double h = 0.5 / sigma2;
-  for (int e = tid; e < LD * LD; e += SPA_THREADS) {
-    const int lane = e & 63, ks = (e >> 6) % (LD / 4), rt = (e >> 6) / (LD / 4);
-    const int row = rt * WPB + (lane & 15), col = 4 * ks + (lane >> 4);
-    double v = 0.0;
-    if (row < m) v = col < m ? Th[(size_t)row * LD + col] * h : (col == m ? mu[row] * h : 0.0);
-    A[e] = v;
-    G[e] = 0.5 * G[e];
+  double *Ti = g.Ti + (size_t)f * g.tifs;
+  const int nks = LDa / 4, tot = g.gh.mtr * WPB * LDa;
+  for (int e = tid; e < tot || e < LD * LD; e += SPA_THREADS) {
+    if (e < tot) {
+      const int lane = e & 63, ks = (e >> 6) % nks, rt = (e >> 6) / nks;
+      const int row = rt * WPB + (lane & 15), col = 4 * ks + (lane >> 4);
+      double v = 0.0;
+      if (row < m) v = col < m ? Th[(size_t)row * LD + col] * h : (col < m + P ? mus[(size_t)(col - m) * LD + row] * h : 0.0);
+      Ti[e] = v;
+    }
+    if (e < LD * LD) G[e] = 0.5 * G[e];
   }
   // the noise component
-  double s_hh = 0.0, s_cc = 0.0, s_tr = 0.0, s_t = 0.0;
-  for (int i = tid; i < m; i += SPA_THREADS) {
-    s_hh += xv[i] * xv[i];
-    s_cc += cv[i] * cv[i];
-    s_tr += da[i];
-  }
+  double s_tr = 0.0, s_t = 0.0;
+  for (int i = tid; i < m; i += SPA_THREADS) s_tr += da[i];
   const WaCov kc = WaCov::from_prep(kid, d, pr);
   for (int i = tid; i < N; i += SPA_THREADS) s_t += kc.kss(X[i]);
   s_tb = sparse_block_sum(s_tb, red, tid);
-  s_hh = sparse_block_sum(s_hh, red, tid);
-  s_cc = sparse_block_sum(s_cc, red, tid);
   s_tr = sparse_block_sum(s_tr, red, tid);
   s_t = sparse_block_sum(s_t, red, tid);
   if (tid == 0) {
-    const double yty = p.scal[(size_t)f * 8];
-    g.gs[(size_t)f * 4] = h * (-(double)N + (yty + s_t) / sigma2 - s_tr + (double)m - s_tb - s_cc - s_hh);
-    g.gs[(size_t)f * 4 + 1] = -s_t * h;
+    double yty = p.yty[(size_t)f * p.ytys];
+    for (int q = 1; q < P; ++q) yty += p.yty[(size_t)f * p.ytys + q];
+    g.gs[(size_t)f * 4] = h * (-((double)N * Pd) + (yty + Pd * s_t) / sigma2 - Pd * s_tr + Pd * (double)m - Pd * s_tb - s_cc - s_hh);
+    g.gs[(size_t)f * 4 + 1] = -(Pd * s_t) * h;
   }
 }
 
@@ -253,11 +300,11 @@ __global__ __launch_bounds__(SG_THREADS) void k_sparse_grad_panel(SparseArgs p, 
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int N = p.N, m = p.m, d = p.d, kid = p.kid;
-  const int LD = p.sh.LD, S = p.sh.S, nks = LD / 4;
+  const int LD = p.sh.LDa, S = p.sh.S, nks = LD / 4, mP = m + p.P;   // (LD: the augmented panel's rows, m + P rounded up)
   double *Zl = reinterpret_cast<double *>(smem_raw);   // [d][LD] the inducing inputs, zero in the padding
   double *P = Zl + (size_t)d * LD;                     // [2][LD][S] the panel: row r of sample s at r * S + s
   const double *pr = p.rec + (size_t)f * PREP_N;
-  const double *X = p.X + (size_t)f * d * N, *y = p.y + (size_t)f * N, *Z = p.Z + (size_t)f * d * m;
+  const double *X = p.X + (size_t)f * d * N, *y = p.y + (size_t)f * p.P * N, *Z = p.Z + (size_t)f * d * m;
   const int rt = grp * SG_WAVES + wave;                // the wave's row tile
   const bool live = rt < g.gh.mtr;
   for (int e = tid; e < d * LD; e += SG_THREADS) {
@@ -268,7 +315,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_sparse_grad_panel(SparseArgs p, 
   const int n1 = n0 + p.sh.clen < N ? n0 + p.sh.clen : N;
   const int nsp = n1 > n0 ? (n1 - n0 + S - 1) / S : 0;
   __syncthreads();
-  // sub-panel sp into buffer `buf`: K(z_r, x_i) for r < m, y_i in row m, zero in the padding and past the chunk
+  // sub-panel sp into buffer `buf`: K(z_r, x_i) for r < m, target column q of x_i in row m + q, zero in the padding and past the chunk
   auto eval = [&](int sp, int buf) {
     double *Pb = P + (size_t)buf * LD * S;
     const int tot = LD * S;
@@ -278,7 +325,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_sparse_grad_panel(SparseArgs p, 
       double v = 0.0;
       if (i < n1) {
         if (r < m) v = win_cov(kid, d, pr, Zl + r, LD, X + i, N, false);
-        else if (r == m) v = y[i];
+        else if (r < mP) v = y[(size_t)(r - m) * N + i];
       }
       Pb[e] = v;
     }
@@ -297,7 +344,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_sparse_grad_panel(SparseArgs p, 
 #pragma unroll
     for (int r = 0; r < (WITH_Z ? 4 : 1); ++r) az[r][q] = 0.0;
   }
-  const double *Ti = g.A + (size_t)f * LD * LD + (size_t)rt * WPB * LD + lane;   // the tile's operand image: k-step ks at ks * 64
+  const double *Ti = g.Ti + (size_t)f * g.tifs + (size_t)rt * WPB * LD + lane;   // the tile's operand image: k-step ks at ks * 64
   const int sl = l15 & (S - 1);
   const bool scol = l15 < S;
   if (nsp > 0) eval(0, 0);
@@ -364,7 +411,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_sparse_grad_panel(SparseArgs p, 
     if (lane == 0) tp[i] = v;
   }
   if constexpr (WITH_Z) {
-    double *zp = g.zpart + ((size_t)f * p.sh.nch + ch) * LD * MAXD;
+    double *zp = g.zpart + ((size_t)f * p.sh.nch + ch) * p.sh.LD * MAXD;
     const int nz = KC == SGK_BROWN ? 2 : d;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -467,6 +514,8 @@ __global__ __launch_bounds__(256) void k_sparse_grad_finish(SparseArgs p, Sparse
     if (bad) {
       g.nll[f] = nan;
       for (int i = 0; i < nth; ++i) gr[i] = nan;
+      if (g.lout)
+        for (int q = 0; q < p.P; ++q) g.lout[(size_t)f * p.P + q] = nan;
     } else {
       double s[GRAD_N];
       for (int i = 0; i < GRAD_N; ++i) s[i] = 0.0;
@@ -481,7 +530,12 @@ __global__ __launch_bounds__(256) void k_sparse_grad_finish(SparseArgs p, Sparse
       for (int i = 0; i < 1 + MAXD; ++i) s[i] *= 2.0;
       s[9] = 2.0 * g.gs[(size_t)f * 4];
       grad_from_sums(kid, d, p.theta + (size_t)f * MAX_THETA, s, gr);
-      g.nll[f] = -p.logml[f];
+      const double *lm = p.logml + (size_t)f * p.P;
+      double bound = lm[0];   // the columns' bounds summed in column order
+      for (int q = 1; q < p.P; ++q) bound += lm[q];
+      g.nll[f] = -bound;
+      if (g.lout)
+        for (int q = 0; q < p.P; ++q) g.lout[(size_t)f * p.P + q] = lm[q];
     }
   }
   if (g.gradZ) {

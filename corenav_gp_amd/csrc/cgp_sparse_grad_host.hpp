@@ -40,19 +40,14 @@ struct SparseGradCall {   // the call's arrays (device, the call's first fit) an
   int *info;
 };
 
-// the linear chain of a gradient call for the `nfit` fits in slots slot, slot + 1, ... of the call's arrays and of both scratches:
-// the forward chain as it stands (M = 0, A kept), then algebra, panel, uu, finish.  Profile slots: 0 k_sparse_phi, 1 both algebra
-// kernels, 2 k_sparse_reduce + k_sparse_grad_uu + k_sparse_grad_finish, 3 k_sparse_grad_panel, 4 k_sparse_prep
-int sparse_grad_enqueue(cgp_ctx *c, const SparseGradCall &k, int slot, int nfit, hipStream_t s) {
+// the gradient kernels' record for the fits in slots slot, slot + 1, ... of the gradient reservation's scratch, strided by the
+// call's shape `sh`; the operand image of That in A's block (where it fits whenever the target rows add no tile row: LDa = LD)
+SparseGradArgs sparse_grad_args(const cgp_ctx *c, const SparseShape &sh, int m, int slot) {
   const SparseGradLayout l = sparse_grad_layout(c->sg.max_batch, c->sg_max_n, c->sg.max_dim);
   double *buf = static_cast<double *>(c->sg.buf);
-  const size_t sl = slot;
-  const SparseCall fk{k.N, k.d, 0, k.m, k.kid, 0, k.X, k.y, k.Z, nullptr, k.theta, k.jitter, nullptr, nullptr, buf + l.lml, k.info};
-  SparseArgs a = sparse_args(c, fk, slot, nfit);
-  const SparseShape &sh = a.sh;
-  const size_t LD = sh.LD, LD2 = LD * LD;
+  const size_t sl = slot, LD = sh.LD, LD2 = LD * LD;
   SparseGradArgs g{};
-  g.gh = sparse_grad_shape(k.m);
+  g.gh = sparse_grad_shape(m);
   g.A = buf + l.A + sl * LD2;
   g.Th = buf + l.Th + sl * LD2;
   g.G = buf + l.G + sl * LD2;
@@ -61,23 +56,30 @@ int sparse_grad_enqueue(cgp_ctx *c, const SparseGradCall &k, int slot, int nfit,
   g.upart = buf + l.upart + sl * g.gh.mtr * GRAD_N;
   g.uz = buf + l.uz + sl * LD * MAXD;
   g.gs = buf + l.gs + sl * 4;
-  g.nll = k.nll + sl;
-  g.grad = k.grad + sl * k.grad_stride;
-  g.gradZ = k.gradZ ? k.gradZ + sl * k.d * k.m : nullptr;
-  g.grad_stride = k.grad_stride;
+  g.Ti = g.A;
+  g.tifs = LD2;
+  return g;
+}
+
+// the linear chain of a gradient call on s: the forward chain as it stands (M = 0, A kept), then algebra, panel, uu, finish; `a`
+// carries the target columns (a.P), `g` the outputs.  Profile slots: 0 k_sparse_phi, 1 both algebra kernels, 2 k_sparse_reduce +
+// k_sparse_grad_uu + k_sparse_grad_finish, 3 k_sparse_grad_panel, 4 k_sparse_prep
+int sparse_grad_launch(cgp_ctx *c, SparseArgs &a, const SparseGradArgs &g, hipStream_t s) {
+  const SparseShape &sh = a.sh;
+  const int nfit = a.nfit;
   a.Acp = g.A;
   int rc = sparse_enqueue(c, a, s);
   if (rc != CGP_OK) return rc;
   Launcher L{c, s};
-  const double mm = k.m, fits = nfit;
+  const double mm = a.m, fits = nfit;
   L.begin(1, fits * 6.0 * mm * mm * mm);   // six m x m block solves
   hipLaunchKernelGGL(k_sparse_grad_algebra, dim3(nfit), dim3(SPA_THREADS), 0, s, a, g);
   L.end();
   const dim3 pg(g.gh.ngrp, sh.nch, nfit), ug(g.gh.mtr, nfit);
-  const size_t lds = sparse_grad_panel_lds(k.d, sh.LD, sh.S);
-  const int kc = k.kid == K_RBF_BROWNIAN ? SGK_BROWN : k.kid == K_MATERN32_ARD ? SGK_M32 : k.kid == K_MATERN52_ARD ? SGK_M52 : SGK_SE;
+  const size_t lds = sparse_grad_panel_lds(a.d, sh.LDa, sh.S);
+  const int kc = a.kid == K_RBF_BROWNIAN ? SGK_BROWN : a.kid == K_MATERN32_ARD ? SGK_M32 : a.kid == K_MATERN52_ARD ? SGK_M52 : SGK_SE;
   const bool wz = g.gradZ != nullptr;
-  L.begin(3, fits * 2.0 * k.N * (mm + 1) * sh.LD);
+  L.begin(3, fits * 2.0 * a.N * (mm + a.P) * sh.LDa);
 #define CGP_SG_PANEL(KC)                                                                                             \
   if (wz) hipLaunchKernelGGL((k_sparse_grad_panel<KC, true>), pg, dim3(SG_THREADS), lds, s, a, g);                   \
   else hipLaunchKernelGGL((k_sparse_grad_panel<KC, false>), pg, dim3(SG_THREADS), lds, s, a, g)
@@ -87,7 +89,7 @@ int sparse_grad_enqueue(cgp_ctx *c, const SparseGradCall &k, int slot, int nfit,
   else { CGP_SG_PANEL(SGK_SE); }
 #undef CGP_SG_PANEL
   L.end();
-  L.begin(2, fits * mm * mm * (2.0 * k.d + 2));
+  L.begin(2, fits * mm * mm * (2.0 * a.d + 2));
   if (kc == SGK_BROWN) hipLaunchKernelGGL(k_sparse_grad_uu<SGK_BROWN>, ug, dim3(SGU_THREADS), 0, s, a, g);
   else if (kc == SGK_M32) hipLaunchKernelGGL(k_sparse_grad_uu<SGK_M32>, ug, dim3(SGU_THREADS), 0, s, a, g);
   else if (kc == SGK_M52) hipLaunchKernelGGL(k_sparse_grad_uu<SGK_M52>, ug, dim3(SGU_THREADS), 0, s, a, g);
@@ -96,6 +98,21 @@ int sparse_grad_enqueue(cgp_ctx *c, const SparseGradCall &k, int slot, int nfit,
   L.end();
   if (!hip_ok(c, hipGetLastError(), "sparse gradient launches")) return CGP_EHIP;
   return CGP_OK;
+}
+
+// a single-column gradient call for the `nfit` fits in slots slot, slot + 1, ... of the call's arrays and of both scratches
+int sparse_grad_enqueue(cgp_ctx *c, const SparseGradCall &k, int slot, int nfit, hipStream_t s) {
+  const SparseGradLayout l = sparse_grad_layout(c->sg.max_batch, c->sg_max_n, c->sg.max_dim);
+  const size_t sl = slot;
+  const SparseCall fk{k.N, k.d, 0, k.m, k.kid, 0, k.X, k.y, k.Z, nullptr, k.theta, k.jitter, nullptr, nullptr,
+                      static_cast<double *>(c->sg.buf) + l.lml, k.info};
+  SparseArgs a = sparse_args(c, fk, slot, nfit);
+  SparseGradArgs g = sparse_grad_args(c, a.sh, k.m, slot);
+  g.nll = k.nll + sl;
+  g.grad = k.grad + sl * k.grad_stride;
+  g.gradZ = k.gradZ ? k.gradZ + sl * k.d * k.m : nullptr;
+  g.grad_stride = k.grad_stride;
+  return sparse_grad_launch(c, a, g, s);
 }
 
 // the checks every call of this section starts with: dtype, the two reservations, capacity, then the shape
@@ -111,15 +128,16 @@ int sparse_grad_check(const cgp_ctx *c, int batch, int N, int d, int m, int kid)
   return CGP_OK;
 }
 
-// The staging of the host calls: the caller's row-major [X | Z], then what the device form takes and returns:
-// [dX | dZ | dy | theta | nll | grad | gradZ]; X and y are uploaded once, theta and Z per evaluation.
+// The staging of the host calls (P target columns: one here, several in cgp_sparse_multi_grad_host.hpp, each in its own
+// reservation's staging block): the caller's row-major [X | Z], then what the device form takes and returns:
+// [dX | dZ | dy (fit, P, N) | theta | nll | grad | gradZ | logml (fit, P)]; X and y are uploaded once, theta and Z per evaluation.
 struct SparseGradStage {
-  double *raw, *dX, *dZ, *dy, *dth, *dnll, *dgrad, *dgz;
+  double *raw, *dX, *dZ, *dy, *dth, *dnll, *dgrad, *dgz, *dlm;
 };
-int sparse_grad_stage(cgp_ctx *c, int batch, int N, int d, int m, SparseGradStage &st) {
-  const size_t B = batch, nX = B * N * d, nZ = B * m * d, ny = B * N, nth_all = B * CGP_MAX_THETA;
-  if (!grow_device(c->sg.stage, c->sg.stage_cap, (2 * (nX + nZ) + ny + 2 * nth_all + B + nZ) * sizeof(double))) return CGP_ENOMEM;
-  st.raw = static_cast<double *>(c->sg.stage);
+int sparse_grad_stage(cgp_ctx *c, Scratch &r, int batch, int N, int d, int m, int P, SparseGradStage &st) {
+  const size_t B = batch, nX = B * N * d, nZ = B * m * d, ny = B * P * N, nth_all = B * CGP_MAX_THETA;
+  if (!grow_device(r.stage, r.stage_cap, (2 * (nX + nZ) + ny + 2 * nth_all + B + nZ + B * P) * sizeof(double))) return CGP_ENOMEM;
+  st.raw = static_cast<double *>(r.stage);
   st.dX = st.raw + nX + nZ;
   st.dZ = st.dX + nX;
   st.dy = st.dZ + nZ;
@@ -127,20 +145,25 @@ int sparse_grad_stage(cgp_ctx *c, int batch, int N, int d, int m, SparseGradStag
   st.dnll = st.dth + nth_all;
   st.dgrad = st.dnll + B;
   st.dgz = st.dgrad + nth_all;
+  st.dlm = st.dgz + nZ;
   return CGP_OK;
 }
-int sparse_grad_upload_xy(cgp_ctx *c, int batch, int N, int d, const double *X, const double *y, const SparseGradStage &st) {
+int sparse_grad_upload_xy(cgp_ctx *c, int batch, int N, int d, int P, const double *X, const double *y, const SparseGradStage &st) {
   hipStream_t s = c->stream;
   const size_t nX = (size_t)batch * N * d;
   HIP_TRY(c, hipMemcpyAsync(st.raw, X, nX * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(st.dy, y, (size_t)batch * N * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(st.dy, y, (size_t)batch * P * N * sizeof(double), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_pack_soa<double>, dim3(std::min(64, cdiv(N * d, 256)), batch), dim3(256), 0, s, st.raw, st.dX, N, d);
   return CGP_OK;
 }
 // One evaluation of the batch at host theta (batch, theta_stride) and Z (batch, m, d): upload, one batched call, the ladder on K_uu
-// for the failed fits that `skip` (or null) does not mark, results back.  hg (batch, CGP_MAX_THETA); hgz (batch, d, m) or null.
-int sparse_grad_eval_host(cgp_ctx *c, int batch, int N, int d, int m, int kid, const double *Z, const double *theta, int theta_stride,
-                          const SparseGradStage &st, const std::vector<char> *skip, double *nll, double *hg, double *hgz, int *info) {
+// for the failed fits that `skip` (or null) does not mark, results back.  enqueue(slot, nfit) is the call's chain on the staged
+// arrays (theta at CGP_MAX_THETA, jitter c->djitter, info c->dinfo, gradZ asked when hgz is).  hg (batch, CGP_MAX_THETA); hgz
+// (batch, d, m) or null; hlm (batch, P) or null.
+template <class Enqueue>
+int sparse_grad_eval_host(cgp_ctx *c, int batch, int N, int d, int m, int P, int kid, const double *Z, const double *theta, int theta_stride,
+                          const SparseGradStage &st, const std::vector<char> *skip, double *nll, double *hg, double *hgz, double *hlm,
+                          int *info, Enqueue enqueue) {
   hipStream_t s = c->stream;
   const int nth = ntheta(kid, d);
   const size_t B = batch, nX = B * N * d, nZ = B * m * d;
@@ -151,9 +174,7 @@ int sparse_grad_eval_host(cgp_ctx *c, int batch, int N, int d, int m, int kid, c
   HIP_TRY(c, hipMemcpyAsync(st.dth, hth.data(), hth.size() * sizeof(double), hipMemcpyHostToDevice, s));
   HIP_TRY(c, hipMemsetAsync(c->djitter, 0, sizeof(double) * batch, s));
   hipLaunchKernelGGL(k_pack_soa<double>, dim3(std::min(64, cdiv(m * d, 256)), batch), dim3(256), 0, s, st.raw + nX, st.dZ, m, d);
-  const SparseGradCall k{N, d, m, kid, st.dX, st.dy, st.dZ, st.dth, c->djitter, st.dnll, st.dgrad, hgz ? st.dgz : nullptr, CGP_MAX_THETA,
-                         c->dinfo};
-  int rc = sparse_grad_enqueue(c, k, 0, batch, s);
+  int rc = enqueue(0, batch);
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(info, c->dinfo, B * sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
@@ -161,13 +182,72 @@ int sparse_grad_eval_host(cgp_ctx *c, int batch, int N, int d, int m, int kid, c
   std::vector<char> sk(B, 0);
   for (size_t b = 0; b < B; ++b) sk[b] = info[b] > m || (skip && (*skip)[b]);
   std::vector<double> hjit(B, 0.0);
-  rc = jitter_ladder(c, batch, m, d, kid, theta, theta_stride, Z, info, &sk, hjit.data(), s,
-                     [&](int b) { return sparse_grad_enqueue(c, k, b, 1, s); });
+  rc = jitter_ladder(c, batch, m, d, kid, theta, theta_stride, Z, info, &sk, hjit.data(), s, [&](int b) { return enqueue(b, 1); });
   if (rc != CGP_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(nll, st.dnll, B * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(hg, st.dgrad, B * CGP_MAX_THETA * sizeof(double), hipMemcpyDeviceToHost, s));
   if (hgz) HIP_TRY(c, hipMemcpyAsync(hgz, st.dgz, nZ * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (hlm) HIP_TRY(c, hipMemcpyAsync(hlm, st.dlm, B * P * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
+  return CGP_OK;
+}
+// the staged single-column call
+SparseGradCall sparse_grad_staged_call(cgp_ctx *c, int N, int d, int m, int kid, const SparseGradStage &st, bool want_gz) {
+  return SparseGradCall{N, d, m, kid, st.dX, st.dy, st.dZ, st.dth, c->djitter, st.dnll, st.dgrad, want_gz ? st.dgz : nullptr, CGP_MAX_THETA,
+                        c->dinfo};
+}
+
+// The batched L-BFGS of the sparse objectives over [theta | Z row-major]: theta Logexp-transformed, Z as it stands (free
+// coordinates, optimize_z only).  eval(Z (batch, m, d), theta (batch, nth), skip or null, nll, hg (batch, CGP_MAX_THETA), hgz
+// (batch, d, m) or null, info) is one evaluation of the batch with the ladder.  bound (or null): -nll at the returned point, from
+// one evaluation more, not counted in n_evals.
+template <class Eval>
+int sparse_optimize_driver(int batch, int d, int m, int nth, double *Z, double *theta, int theta_stride, int optimize_z, int max_evals,
+                           double *bound, int *n_evals, Eval eval) {
+  const size_t B = batch, mz = (size_t)m * d;
+  const int nfree = optimize_z ? (int)mz : 0, nx = nth + nfree;
+  std::vector<double> x0(B * nx), hth(B * nth), hZ(Z, Z + B * mz), nl(B), hg(B * CGP_MAX_THETA), hgz(optimize_z ? B * mz : 0);
+  std::vector<int> info(B);
+  std::vector<char> skip(B, 0);
+  for (size_t b = 0; b < B; ++b) {
+    std::copy(theta + b * theta_stride, theta + b * theta_stride + nth, x0.begin() + b * nx);
+    if (optimize_z) std::copy(Z + b * mz, Z + (b + 1) * mz, x0.begin() + b * nx + nth);
+  }
+  auto eval_at = [&](const double *x, const std::vector<char> *sk) -> int {
+    for (size_t b = 0; b < B; ++b) {
+      std::copy(x + b * nx, x + b * nx + nth, hth.begin() + b * nth);
+      if (optimize_z) std::copy(x + b * nx + nth, x + (b + 1) * nx, hZ.begin() + b * mz);
+    }
+    return eval(hZ.data(), hth.data(), sk, nl.data(), hg.data(), optimize_z ? hgz.data() : nullptr, info.data());
+  };
+  auto round = [&](const double *x, const char *active, double *f, double *g, char *feasible) -> int {
+    for (int b = 0; b < batch; ++b) skip[b] = !active[b];
+    // a trial point whose K_uu is not positive definite climbs the ladder; one that stays infeasible (K_uu or B) is +inf
+    const int rc = eval_at(x, &skip);
+    if (rc != CGP_OK) return rc;
+    for (size_t b = 0; b < B; ++b) {
+      if (!active[b]) continue;
+      feasible[b] = info[b] == 0;
+      f[b] = nl[b];
+      std::copy(hg.begin() + b * CGP_MAX_THETA, hg.begin() + b * CGP_MAX_THETA + nth, g + b * nx);
+      if (optimize_z)   // the device's (d, m) into the row-major coordinates
+        for (int r = 0; r < m; ++r)
+          for (int q = 0; q < d; ++q) g[b * nx + nth + (size_t)r * d + q] = hgz[(b * d + q) * m + r];
+    }
+    return CGP_OK;
+  };
+  corenav::LbfgsBatchResult res;
+  int rc = corenav::lbfgs_minimize_logexp_batch(batch, nth, x0.data(), nx, nullptr, max_evals, round, res, nfree);
+  if (rc != CGP_OK) return rc;
+  for (size_t b = 0; b < B; ++b) {
+    std::copy(res.theta.begin() + b * nx, res.theta.begin() + b * nx + nth, theta + b * theta_stride);
+    if (optimize_z) std::copy(res.theta.begin() + b * nx + nth, res.theta.begin() + (b + 1) * nx, Z + b * mz);
+    if (n_evals) n_evals[b] = res.evals[b];
+  }
+  if (bound) {
+    if ((rc = eval_at(res.theta.data(), nullptr)) != CGP_OK) return rc;
+    for (size_t b = 0; b < B; ++b) bound[b] = -nl[b];
+  }
   return CGP_OK;
 }
 
@@ -209,13 +289,14 @@ extern "C" int cgp_sparse_nll_grad_batch(cgp_ctx *c, int batch, int N, int d, in
   if (!X || !y || !Z || !theta || !nll || !grad || theta_stride < nth || grad_stride < nth) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   SparseGradStage st{};
-  if ((rc = sparse_grad_stage(c, batch, N, d, m, st)) != CGP_OK) return rc;
-  if ((rc = sparse_grad_upload_xy(c, batch, N, d, X, y, st)) != CGP_OK) return rc;
+  if ((rc = sparse_grad_stage(c, c->sg, batch, N, d, m, 1, st)) != CGP_OK) return rc;
+  if ((rc = sparse_grad_upload_xy(c, batch, N, d, 1, X, y, st)) != CGP_OK) return rc;
   const size_t B = batch;
   std::vector<double> hg(B * CGP_MAX_THETA), hgz(gradZ ? B * m * d : 0);
   std::vector<int> hinfo(B);
-  rc = sparse_grad_eval_host(c, batch, N, d, m, kid, Z, theta, theta_stride, st, nullptr, nll, hg.data(), gradZ ? hgz.data() : nullptr,
-                             hinfo.data());
+  const SparseGradCall k = sparse_grad_staged_call(c, N, d, m, kid, st, gradZ != nullptr);
+  rc = sparse_grad_eval_host(c, batch, N, d, m, 1, kid, Z, theta, theta_stride, st, nullptr, nll, hg.data(), gradZ ? hgz.data() : nullptr,
+                             nullptr, hinfo.data(), [&](int slot, int nfit) { return sparse_grad_enqueue(c, k, slot, nfit, c->stream); });
   if (rc != CGP_OK) return rc;
   int first = 0;
   for (size_t b = 0; b < B; ++b) {
@@ -241,52 +322,15 @@ extern "C" int cgp_optimize_sparse_batch(cgp_ctx *c, int batch, int N, int d, in
       if (!(theta[(size_t)b * theta_stride + i] > 0.0)) return CGP_EINVAL;
   HIP_TRY(c, hipSetDevice(c->device));
   SparseGradStage st{};
-  if ((rc = sparse_grad_stage(c, batch, N, d, m, st)) != CGP_OK) return rc;
-  if ((rc = sparse_grad_upload_xy(c, batch, N, d, X, y, st)) != CGP_OK) return rc;
-  // the batched L-BFGS driver over [theta | Z row-major]: theta Logexp-transformed, Z as it stands
-  const size_t B = batch, mz = (size_t)m * d;
-  const int nfree = optimize_z ? (int)mz : 0, nx = nth + nfree;
-  std::vector<double> x0(B * nx), hth(B * nth), hZ(Z, Z + B * mz), nl(B), hg(B * CGP_MAX_THETA), hgz(optimize_z ? B * mz : 0);
-  std::vector<int> info(B);
-  std::vector<char> skip(B, 0);
-  for (size_t b = 0; b < B; ++b) {
-    std::copy(theta + b * theta_stride, theta + b * theta_stride + nth, x0.begin() + b * nx);
-    if (optimize_z) std::copy(Z + b * mz, Z + (b + 1) * mz, x0.begin() + b * nx + nth);
-  }
-  auto eval_at = [&](const double *x, const std::vector<char> *sk) -> int {
-    for (size_t b = 0; b < B; ++b) {
-      std::copy(x + b * nx, x + b * nx + nth, hth.begin() + b * nth);
-      if (optimize_z) std::copy(x + b * nx + nth, x + (b + 1) * nx, hZ.begin() + b * mz);
-    }
-    return sparse_grad_eval_host(c, batch, N, d, m, kid, hZ.data(), hth.data(), nth, st, sk, nl.data(), hg.data(),
-                                 optimize_z ? hgz.data() : nullptr, info.data());
-  };
-  auto round = [&](const double *x, const char *active, double *f, double *g, char *feasible) -> int {
-    for (int b = 0; b < batch; ++b) skip[b] = !active[b];
-    // a trial point whose K_uu is not positive definite climbs the ladder; one that stays infeasible (K_uu or B) is +inf
-    const int rc = eval_at(x, &skip);
-    if (rc != CGP_OK) return rc;
-    for (size_t b = 0; b < B; ++b) {
-      if (!active[b]) continue;
-      feasible[b] = info[b] == 0;
-      f[b] = nl[b];
-      std::copy(hg.begin() + b * CGP_MAX_THETA, hg.begin() + b * CGP_MAX_THETA + nth, g + b * nx);
-      if (optimize_z)   // the device's (d, m) into the row-major coordinates
-        for (int r = 0; r < m; ++r)
-          for (int q = 0; q < d; ++q) g[b * nx + nth + (size_t)r * d + q] = hgz[(b * d + q) * m + r];
-    }
-    return CGP_OK;
-  };
-  corenav::LbfgsBatchResult res;
-  if ((rc = corenav::lbfgs_minimize_logexp_batch(batch, nth, x0.data(), nx, nullptr, max_evals, round, res, nfree)) != CGP_OK) return rc;
-  for (size_t b = 0; b < B; ++b) {
-    std::copy(res.theta.begin() + b * nx, res.theta.begin() + b * nx + nth, theta + b * theta_stride);
-    if (optimize_z) std::copy(res.theta.begin() + b * nx + nth, res.theta.begin() + (b + 1) * nx, Z + b * mz);
-    if (n_evals) n_evals[b] = res.evals[b];
-  }
-  if (logml) {   // the bound AT the returned point: one evaluation more, not counted in n_evals
-    if ((rc = eval_at(res.theta.data(), nullptr)) != CGP_OK) return rc;
-    for (size_t b = 0; b < B; ++b) logml[b] = -nl[b];
-  }
-  return CGP_OK;
+  if ((rc = sparse_grad_stage(c, c->sg, batch, N, d, m, 1, st)) != CGP_OK) return rc;
+  if ((rc = sparse_grad_upload_xy(c, batch, N, d, 1, X, y, st)) != CGP_OK) return rc;
+  const SparseGradCall kz = sparse_grad_staged_call(c, N, d, m, kid, st, optimize_z != 0), k0 = sparse_grad_staged_call(c, N, d, m, kid, st, false);
+  // the bound AT the returned point comes from one evaluation more, not counted in n_evals
+  return sparse_optimize_driver(batch, d, m, nth, Z, theta, theta_stride, optimize_z, max_evals, logml, n_evals,
+                                [&](const double *hZ, const double *hth, const std::vector<char> *sk, double *nl, double *hg, double *hgz,
+                                    int *info) {
+                                  const SparseGradCall &k = hgz ? kz : k0;
+                                  return sparse_grad_eval_host(c, batch, N, d, m, 1, kid, hZ, hth, nth, st, sk, nl, hg, hgz, nullptr, info,
+                                                               [&](int slot, int nfit) { return sparse_grad_enqueue(c, k, slot, nfit, c->stream); });
+                                });
 }

@@ -120,6 +120,11 @@ _SIGS = {
     "cgp_fit_predict_sparse_multi_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_dp] * 5 + [ctypes.c_int, ctypes.c_int,
                                                                                                    _dp, _dp, _dp, _ip]),
     "cgp_fit_predict_sparse_multi_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp] * 6 + [ctypes.c_int] + [_vp] * 5),
+    "cgp_sparse_multi_grad_reserve": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "cgp_sparse_multi_nll_grad_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_dp] * 4 + [ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                                                                    _dp, _dp, _ip]),
+    "cgp_sparse_multi_nll_grad_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_vp] * 7 + [ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "cgp_optimize_sparse_multi_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 6 + [_dp] * 4 + [ctypes.c_int] * 3 + [_dp, _ip]),
     "cgp_fit_predict_trend_batch": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_dp] * 6 + [ctypes.c_int, ctypes.c_int,
                                                                                           _dp, _dp, _dp, _dp, _ip, _ip]),
     "cgp_fit_predict_trend_batch_device": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [_vp] * 7 + [ctypes.c_int] + [_vp] * 7),
@@ -754,6 +759,57 @@ class Context:
                                                                             dXs or None, dtheta, djitter or None,
                                                                             int(include_noise), dmean or None, dvar or None,
                                                                             dlogml, dinfo, ctypes.c_void_p(stream)))
+
+    # -- sparse fits: gradient and optimiser of the P columns' summed bound (fp64 contexts) --------------------------------
+    def sparse_multi_grad_reserve(self, max_batch, max_p):
+        """What up to max_p columns add to the gradient scratch; needs a sparse_reserve, a sparse_grad_reserve and a
+        sparse_multi_reserve that cover it."""
+        return self._chk(self.lib.cgp_sparse_multi_grad_reserve(self.h, int(max_batch), int(max_p)))
+
+    def sparse_multi_nll_grad_batch(self, X, Y, Z, theta, kernel_id, want_grad_z=True, want_logml=True):
+        """X (B, N, d), Y (B, P, N), Z (B, m, d), theta (B, nth) -> (rc, nll (B,), grad (B, nth), gradZ (B, m, d) or None, logml (B, P)
+        or None, info (B,)): nll = -sum_p bound[p] of each fit (summed in column order), its gradient in theta (natural parameters)
+        and in the inducing inputs, and the columns' bounds.  A fit whose info stays non-zero after the jitter ladder on K_uu has
+        NaN outputs."""
+        X, Y, Z, theta = _d(X), _d(Y), _d(Z), _d(theta)
+        B, N, d = X.shape
+        m, nth, P = Z.shape[1], theta.shape[1], Y.shape[1]
+        assert Y.shape == (B, P, N) and Z.shape == (B, m, d)
+        nll, grad = np.empty(B), np.empty((B, nth))
+        gz, info = (np.empty((B, m, d)) if want_grad_z else None), np.zeros(B, dtype=np.int32)
+        logml = np.empty((B, P)) if want_logml else None
+        rc = self._chk(self.lib.cgp_sparse_multi_nll_grad_batch(self.h, B, N, d, P, m, kernel_id, _p(X), _p(Y), _p(Z), _p(theta), nth,
+                                                                _p(nll), _p(grad), nth, _p(gz) if want_grad_z else None,
+                                                                _p(logml) if want_logml else None, info.ctypes.data_as(_ip)))
+        return rc, nll, grad, gz, logml, info
+
+    def sparse_multi_nll_grad_batch_device(self, B, N, d, P, m, kernel_id, dX, dY, dZ, dtheta, djitter, dnll, dgrad, grad_stride,
+                                           dgradZ, dlogml, dinfo, stream=0):
+        """Device pointers as sparse_nll_grad_batch_device with dY (B, P, N); dgradZ (B, d, m) or 0, dlogml (B, P) or 0."""
+        return self._chk(self.lib.cgp_sparse_multi_nll_grad_batch_device(self.h, B, N, d, P, m, kernel_id, dX, dY, dZ, dtheta,
+                                                                         djitter or None, dnll, dgrad, int(grad_stride),
+                                                                         dgradZ or None, dlogml or None, dinfo,
+                                                                         ctypes.c_void_p(stream)))
+
+    def optimize_sparse_multi_batch(self, X, Y, Z0, theta0, kernel_id, optimize_z=True, max_evals=1000):
+        """SparseGPRegression(X, Y, Z=Z).optimize() with Y (N, P): X (B, N, d), Y (B, P, N), Z0 (B, m, d), theta0 (B, nth) or (nth,)
+        -> (theta_opt (B, nth), Z_opt (B, m, d), bound_sum (B,), n_evals (B,)); optimize_z=False keeps Z0."""
+        X, Y = _d(X), _d(Y)
+        B, N, d = X.shape
+        P = Y.shape[1]
+        Z = np.array(Z0, dtype=np.float64, order="C")
+        m = Z.shape[1]
+        theta = np.array(theta0, dtype=np.float64)
+        if theta.ndim == 1:
+            theta = np.tile(theta, (B, 1))
+        theta = np.ascontiguousarray(theta)
+        bound, nev = np.empty(B), np.zeros(B, dtype=np.int32)
+        rc = self._chk(self.lib.cgp_optimize_sparse_multi_batch(self.h, B, N, d, P, m, kernel_id, _p(X), _p(Y), _p(Z), _p(theta),
+                                                                theta.shape[1], int(bool(optimize_z)), int(max_evals), _p(bound),
+                                                                nev.ctypes.data_as(_ip)))
+        if rc > 0:
+            raise CgpError(rc)
+        return theta, Z, bound, nev
 
     # -- multi-target fits: gradient and optimiser of the summed logML (fp64 contexts) ------------------------
     def multi_grad_reserve(self, max_batch, max_p):

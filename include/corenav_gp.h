@@ -614,7 +614,8 @@ int cgp_fit_predict_trend_batch_device(cgp_ctx *ctx, int batch, int N, int d, in
  * k_sparse_algebra, 2 k_sparse_reduce, 3 k_sparse_predict, 4 k_sparse_prep.
  *
  * The gradient of the bound in theta and Z and the optimiser over them are the next section's; several target columns on one fit
- * are the section after it (cgp_fit_predict_sparse_multi_batch).  Not provided: FITC; the resident windows; fp32 contexts; a
+ * are the section after it (cgp_fit_predict_sparse_multi_batch), their summed bound's gradient and optimiser the one after that
+ * (cgp_sparse_multi_nll_grad_batch).  Not provided: FITC; the resident windows; fp32 contexts; a
  * cgp_sweep_* form. */
 int cgp_sparse_reserve(cgp_ctx *ctx, int max_batch, int max_n, int max_m_ind, int max_m);
 /* Samples of the shortest chunk of the sum over N (512): the split above, for tests that sit on its edges. */
@@ -670,8 +671,8 @@ int cgp_fit_predict_sparse_batch_device(cgp_ctx *ctx, int batch, int N, int d, i
  * k_sparse_grad_algebra), slot 2 k_sparse_reduce + k_sparse_grad_uu + k_sparse_grad_finish, slot 3 k_sparse_grad_panel (the predict
  * kernel never runs at M = 0; flops = 2 N (m + 1) LD per fit), slot 4 k_sparse_prep.
  *
- * Not provided: FITC; the gradient of several target columns' summed bound (the forward half is the section after this one); the
- * resident windows; fp32 contexts; a cgp_sweep_* form. */
+ * Several target columns on one fit: the forward half is the section after this one, the gradient of their summed bound and its
+ * optimiser the one after that.  Not provided: FITC; the resident windows; fp32 contexts; a cgp_sweep_* form. */
 int cgp_sparse_grad_reserve(cgp_ctx *ctx, int max_batch);
 /* Host buffers, blocks; layouts as cgp_fit_predict_sparse_batch, grad (batch, grad_stride), gradZ (batch, m, d) or NULL, info
  * (batch) or NULL.  A fit whose K_uu fails climbs the jitter ladder of cgp_fit_predict_sparse_batch, re-submitted alone into its
@@ -739,8 +740,8 @@ int cgp_optimize_sparse_batch(cgp_ctx *ctx, int batch, int N, int d, int m, int 
  *
  * cgp_profile_*: the slots of a sparse call (flops of slot 0: N (m + P)(m + P + 1) per fit).
  *
- * Not provided: the gradient of the summed bound in theta and Z and its optimiser; a trend on the sparse fits; FITC; the resident
- * windows; fp32 contexts; a cgp_sweep_* form. */
+ * The gradient of the summed bound in theta and Z and its optimiser are the next section's.  Not provided: a trend on the sparse
+ * fits; FITC; the resident windows; fp32 contexts; a cgp_sweep_* form. */
 #define CGP_SPARSE_MAX_P 64
 int cgp_sparse_multi_reserve(cgp_ctx *ctx, int max_batch, int max_p);
 /* Host buffers, blocks.  A fit whose K_uu fails climbs the jitter ladder of cgp_fit_predict_sparse_batch on K_uu, re-submitted alone
@@ -756,6 +757,86 @@ int cgp_fit_predict_sparse_multi_batch_device(cgp_ctx *ctx, int batch, int N, in
                                               const double *dX, const double *dY, const double *dZ, const double *dXs,
                                               const double *dtheta, const double *djitter, int include_noise,
                                               double *dmean, double *dvar, double *dlogml, int *dinfo, void *hip_stream);
+
+/* ---- sparse fits: gradient and optimiser of P target columns' summed bound --------------------------------
+ * SparseGPRegression(X, Y, Z=Z).optimize() with Y (N, P): ONE theta and ONE Z per fit maximise F = sum_p logml[p] of the section
+ * above.  With its quantities, C = [c_1 ... c_P] (m x P) and Y (P x N):
+ *   Chat = L_B^-T C      M = L_u^-T Chat      Q = P (I - B^-1) - Chat Chat^T
+ *   T = L_u^-T Q L_u^-1 / (2 sigma2) = dF/dPhi      G_uu = 1/2 L_u^-T (Q - P A) L_u^-1 = dF/dK_uu      R = 2 T K_uf + M Y / sigma2 = dF/dK_uf
+ *   dF/dtheta_j  = sum G_uu o dK_uu/dtheta_j + sum R o dK_uf/dtheta_j - P sum_i dk(x_i,x_i)/dtheta_j / (2 sigma2)
+ *   dF/dsigma_n2 = (-N P + (sum_p yty_p + P t) / sigma2 - P tr A + P m - P tr B^-1 - ||C||_F^2 - ||Chat||_F^2) / (2 sigma2)
+ *   dF/dz_rq     = the gradient section's expression with this R and this G_uu
+ * -- at P = 1 the gradient section term for term; eps and the tie conventions are that section's.  Outputs: nll = -F with the P
+ * bounds summed in column order, grad = d nll / d theta (natural parameters, cgp_nll_grad's order), gradZ = d nll / d Z, and
+ * optionally the P bounds.  The only other route is P calls of cgp_sparse_nll_grad_batch at the same (theta, Z): P forward and P
+ * backward passes over N and 6 P block solves on matrices that do not depend on the targets.  Here the forward chain is the
+ * section above's at M = 0, the six block solves run once, and the second pass over N contracts over the m + P rows of the
+ * augmented panel [K_uf; Y] instead of m + 1 (R is never stored): for P <= 16 ceil((m + 1) / 16) - m no 16-row tile more than at
+ * P = 1.  The launches are the gradient section's eight; its kernels take P from the call.
+ *
+ * Layouts.  Host form: as cgp_sparse_nll_grad_batch with Y (batch, P, N), gradZ (batch, m, d) or NULL, logml (batch, P) or NULL,
+ * info (batch) or NULL.  Device form: cgp_sparse_nll_grad_batch_device's with dY (batch, P, N), dgradZ (batch, d, m) or NULL, dlogml
+ * (batch, P) or NULL.  CGP_F64 contexts, all five kernel ids, 1 <= P <= CGP_SPARSE_MAX_P.
+ *
+ * Promises.
+ *  1. Every call of the three sections above -- the forward calls with one and several columns, the single-column gradient and its
+ *     optimiser -- is bitwise what it was before this section existed.
+ *  2. logml[p] is bitwise cgp_fit_predict_sparse_multi_batch_device's at any M; nll is bitwise the negated left-to-right float64
+ *     sum of those P values.
+ *  3. At P = 1, nll, grad and gradZ are bitwise cgp_sparse_nll_grad_batch[_device]'s on that column.
+ *  4. A fit's outputs are a function of its own data and of (N, m, P, d, kernel, whether gradZ was asked) only: bitwise independent
+ *     of the batch size, the slot and the neighbours; no floating-point atomics, every sum in a fixed order.
+ *  5. Host form (for a fit that needed no ladder step), device form and a replayed graph agree bitwise.
+ *  6. grad is bitwise the same with and without gradZ, and with and without logml.
+ *  7. A following sparse forward call or single-column gradient call is bitwise what it is without this call; scratch left full of
+ *     NaN by a call of another shape moves nothing.
+ *  8. NOT promised: bitwise invariance under a permutation of the columns -- the sum over p is the inner dimension of a matrix-core
+ *     loop and of the rank-P term of Q.  nll, grad and gradZ then agree to 1e-9 (the bar two routes of this library are held to);
+ *     logml[p] still permutes bitwise.
+ *  9. A NaN among one column's targets gives NaN in nll, grad and gradZ of that fit, leaves the other columns' logml bitwise what
+ *     they were and info at 0, and does not touch the neighbouring fits.
+ * A fit whose info is not 0 has NaN in nll, grad, gradZ and its P logml entries.
+ *
+ * cgp_sparse_multi_grad_reserve: only what the columns add to the gradient scratch.  Needs a cgp_sparse_reserve, a
+ * cgp_sparse_grad_reserve and a cgp_sparse_multi_reserve that cover it (max_batch within each, max_p within the last), else
+ * CGP_ESTATE, and is sized by the gradient reservation's max_m_ind as it stands at the call: with LD = 16 ceil((max_m_ind + 1) / 16),
+ * mr = ceil(max_m_ind / 16) and k = ceil((max_p - 1) / 16) it allocates
+ *   8 max_batch (16 mr (LD + 16 k) [k > 0] + max_p) bytes
+ * (max_m_ind = 512: max_p = 4 or 16 2.2 MB, max_p = 64 2.4 MB per fit; max_m_ind = 256: 0.6 MB): the matrix-core operand image of
+ * [T | M] / (2 sigma2), 16 mr LDa doubles with LDa = 16 ceil((m + P) / 16), which the single-column call keeps in A's spent LD^2
+ * block and which no longer fits there once the targets add a tile row (m = 512, P = 64: 303 104 against 278 784); a call with LDa
+ * = LD -- every call at P = 1 -- keeps it where it was.  1 <= max_batch <= the context's and 1 <= max_p <= CGP_SPARSE_MAX_P, else
+ * CGP_EINVAL; CGP_ENOMEM leaves no reservation; calling it again replaces the reservation.  A later reservation of the other three
+ * does not widen it: batch, N, m and P of a call must fit all four.  Blocks.  cgp_destroy frees it.
+ *
+ * Status of the calls below, in this order: CGP_EINVAL in a CGP_F32 context, for batch, N, d, P or m < 1, P > CGP_SPARSE_MAX_P, m >
+ * 512, an unknown kernel id or RBF x Brownian with d != 1; without any of the four reservations CGP_ESTATE; batch, N, m or P beyond
+ * any of them, d beyond the context's max_d CGP_ECAPACITY; a NULL required pointer, theta_stride or grad_stride < ntheta CGP_EINVAL;
+ * the optimiser also CGP_EINVAL for a theta <= 0.  All of these return before anything is enqueued.
+ *
+ * cgp_profile_*: the slots of the gradient section (flops of slot 0: N (m + P)(m + P + 1), of slot 3: 2 N (m + P) LDa per fit).
+ *
+ * Not provided: FITC; a trend on the sparse fits; the resident windows; fp32 contexts; a cgp_sweep_* form. */
+int cgp_sparse_multi_grad_reserve(cgp_ctx *ctx, int max_batch, int max_p);
+/* Host buffers, blocks.  A fit whose K_uu fails climbs the jitter ladder of cgp_fit_predict_sparse_batch, re-submitted alone into
+ * its slot with all its columns; the gradient is then that of the summed bound at that jitter.  Returns a negative error, else 0 or
+ * the first non-zero info. */
+int cgp_sparse_multi_nll_grad_batch(cgp_ctx *ctx, int batch, int N, int d, int P, int m, int kernel_id, const double *X,
+                                    const double *Y, const double *Z, const double *theta, int theta_stride, double *nll,
+                                    double *grad, int grad_stride, double *gradZ, double *logml, int *info);
+/* Device-resident variant: the gradient section's eight launches in one linear chain on hip_stream; no allocation, no
+ * synchronisation, no jitter ladder (capturable into a hipGraph with default settings).  dnll, dgrad and dinfo are required. */
+int cgp_sparse_multi_nll_grad_batch_device(cgp_ctx *ctx, int batch, int N, int d, int P, int m, int kernel_id, const double *dX,
+                                           const double *dY, const double *dZ, const double *dtheta, const double *djitter,
+                                           double *dnll, double *dgrad, int grad_stride, double *dgradZ, double *dlogml,
+                                           int *dinfo, void *hip_stream);
+/* cgp_optimize_sparse_batch's L-BFGS on this nll from theta_inout and Z_inout (batch, m, d); optimize_z 0 or 1.  X and Y are
+ * uploaded once, theta and Z per round.  logml_sum (or NULL): the summed bound at the returned point, from one evaluation more --
+ * bitwise the column-order sum of what cgp_fit_predict_sparse_multi_batch returns there when no ladder step was needed; n_evals
+ * (or NULL): evaluations of each fit. */
+int cgp_optimize_sparse_multi_batch(cgp_ctx *ctx, int batch, int N, int d, int P, int m, int kernel_id, const double *X,
+                                    const double *Y, double *Z_inout, double *theta_inout, int theta_stride, int optimize_z,
+                                    int max_evals, double *logml_sum, int *n_evals);
 
 /* ---- multi-target fits: gradient and optimiser of the summed logML ------------------------------------
  * m.optimize() of the multi-column model (gp_slip_node.py:36 with Y (N, P)): ONE theta per fit maximises
